@@ -13,6 +13,11 @@ Launch:  python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 witho
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W               (the driver's form: one rank per GPU over RCCL)
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times EXACTLY K steps once and prints the line.  --full adds what takes work of its own:
+the CPU-baseline legs, up to two more timed regions when wall clock and device clock disagree, the stand-alone
+obs-assembly reference, the one-hipGraph-per-episode loop and (--mode train) the gate kernel timed alone.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import gc
@@ -265,6 +270,53 @@ def mfma_roofline(a, nenvs, step_ms, gate_split=False):
     return out
 
 
+DUMP_MAX_BYTES = 60 << 20      # all arrays of one --dump-outputs together (the limit is 64 MB)
+
+
+def _dump_items(prefix, x):
+    """(name, tensor) pairs of a tensor / tuple / list / dict of them, in a fixed order."""
+    import torch
+    if isinstance(x, torch.Tensor):
+        return [(prefix, x)]
+    if isinstance(x, dict):
+        return [it for k in sorted(x) for it in _dump_items('%s_%s' % (prefix, k), x[k])]
+    if isinstance(x, (list, tuple)):
+        return [it for i, v in enumerate(x) for it in _dump_items('%s%d' % (prefix, i), v)]
+    return []
+
+
+def dump_outputs(dirname, items):
+    """Write every (name, tensor) of `items` as DIR/<name>.npy: float64 stays float64, everything else becomes float32.  An
+    array larger than its share of DUMP_MAX_BYTES is stored as a fixed sample of its leading-dimension rows: the sorted
+    row indices drawn by np.random.RandomState(0) from that dimension's size (the same rows in every run)."""
+    import numpy as np
+    import torch
+    items = [(n, t) for n, t in items if t is not None and t.numel() > 0]
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(items))
+    for name, t in items:
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        row = t[0].numel() * t.element_size()
+        if t.numel() * t.element_size() > share:
+            k = max(1, share // max(1, row))
+            idx = np.sort(np.random.RandomState(0).choice(t.shape[0], size=min(k, t.shape[0]), replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + '.npy'), t.cpu().numpy())
+
+
+def rollout_outputs(trainer, t):
+    """What Trainer.step_episode(t) hands its caller: the policy's log-probabilities and value, the recurrent state it leaves,
+    the drawn actions, the env's reward / done / alive / is_completed and the next observation."""
+    _state, action_out, value, _next = trainer._step_out[t]
+    items = _dump_items('logp', action_out) + _dump_items('value', value) + _dump_items('hidden', trainer._prev_hid)
+    for k in ('action', 'reward', 'done', 'alive', 'is_completed'):
+        items += _dump_items(k, trainer._buf[k][t])
+    return items + _dump_items('next_obs', trainer._state)
+
+
 def train_mode(o, trainer, a, raw_env, rank, world, use_dist, backend, red_dev, barrier, cpu):
     """--mode train: a step = one Trainer.train_batch (trainer.py:245-256: run_batch over max_steps lock-step steps of every
     env, compute_grad, RMSprop; with more than one rank the gradient all-reduce of multi_processing.py:86-97 over RCCL).  W
@@ -295,19 +347,26 @@ def train_mode(o, trainer, a, raw_env, rank, world, use_dist, backend, red_dev, 
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     gc.enable()
+    if o.dump_outputs and rank == 0:          # the last update's statistics and the parameters it left
+        stat = {k: torch.as_tensor(v) for k, v in st.items()
+                if isinstance(v, (int, float, torch.Tensor)) or (hasattr(v, 'dtype') and hasattr(v, 'shape'))}
+        dump_outputs(o.dump_outputs, _dump_items('stat', stat) +
+                     [('param_' + k.replace('.', '_'), v) for k, v in trainer.policy_net.state_dict().items()])
     gate_ms_chain = [s_.elapsed_time(e_) for s_, e_, _t in raw_env.gate_timer]
     # In the timed updates the backward's launches run as TWO concurrent chains of envs (ic3_bptt.two_chains): the events there
-    # bracket the first chain's gate launch while the second chain's kernels share the GPU.  The kernel ALONE: two more updates
-    # behind the timed region with the backward as one chain, every gate launch of them event-timed.
+    # bracket the first chain's gate launch while the second chain's kernels share the GPU.  The kernel ALONE (--full): two
+    # more updates behind the timed region with the backward as one chain, every gate launch of them event-timed.
     two = bool(getattr(a, 'bptt_two_chains', True))
-    a.bptt_two_chains = False
-    raw_env.gate_timer = []
-    for u in range(2):
-        trainer.train_batch(o.warmup + o.steps + u)
-    torch.cuda.synchronize()
-    gate_ms = [s_.elapsed_time(e_) for s_, e_, _t in raw_env.gate_timer]
+    gate_ms = []
+    if o.full:
+        a.bptt_two_chains = False
+        raw_env.gate_timer = []
+        for u in range(2):
+            trainer.train_batch(o.warmup + o.steps + u)
+        torch.cuda.synchronize()
+        gate_ms = [s_.elapsed_time(e_) for s_, e_, _t in raw_env.gate_timer]
+        a.bptt_two_chains = two
     raw_env.gate_timer = None
-    a.bptt_two_chains = two
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -377,7 +436,7 @@ def main():
                         "step = one Trainer.train_batch update (rollout of max_steps steps + backward through time + RMSprop, "
                         "trainer.py:245-256) — the second headline (round-5 verdict), same one-line JSON")
     p.add_argument('--episode-graph', type=int, default=1,
-                   help='1: behind the timed region, also time the Trainer\'s DEFAULT execution mode — Trainer.get_episode with one '
+                   help='1 (with --full): behind the timed region, also time the Trainer\'s DEFAULT execution mode — Trainer.get_episode with one '
                         'hipGraph per episode — and report it as value_episode_graph (what ships; the eager event-timed loop stays '
                         'the headline because the roofline needs its launches timed)')
     p.add_argument('--workload', default='pp_hard', choices=sorted(WORKLOADS))
@@ -389,7 +448,7 @@ def main():
                         '(hipExtLaunchKernel); 0: recorded into the stream before / after it')
     p.add_argument('--time-every', type=int, default=0,
                    help='event-time every N-th step launch of the timed region (stamping both HIP events costs ~10 us per '
-                        'launch, measured: eager launches without events run 3 % faster); 0 = min(4, max(1, steps // 8))')
+                        'launch, measured: eager launches without events run 3 %% faster); 0 = min(4, max(1, steps // 8))')
     p.add_argument('--graph', type=int, default=int(os.environ.get('IC3_BENCH_GRAPH', '1')),
                    help='replay the per-step launch sequence as hipGraphs (Trainer args.hip_graph)')
     p.add_argument('--no-dense-obs', action='store_true',
@@ -420,11 +479,20 @@ def main():
     p.add_argument('--tune-gemm', type=int, default=int(os.environ.get('IC3_BENCH_TUNE_GEMM', '1')),
                    help='let PyTorch TunableOp pick the fastest hipBLASLt/rocBLAS solution for the two policy GEMMs '
                         'during the eager warm-up episode (seconds; selections are kept in memory)')
+    p.add_argument('--full', action='store_true',
+                   help='also measure what takes work of its own: the CPU-baseline legs, repeated timed regions when wall '
+                        'clock and device clock disagree, the stand-alone obs-assembly reference, the episode-graph loop, '
+                        '(--mode train) the gate kernel timed alone.  A plain run times the K steps once and nothing else')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, '
+                        'at most 64 MB in all; rank 0)')
     o = p.parse_args()
     if o.steps is None:
         o.steps = 12 if o.mode == 'train' else 160
     if o.warmup is None:
         o.warmup = 2 if o.mode == 'train' else 16
+    if o.steps < 1 or o.warmup < 0:
+        p.error('--steps must be >= 1 and --warmup >= 0')
 
     if o.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, the
@@ -449,7 +517,7 @@ def main():
                             "or without a launcher (bench.py then starts the ranks itself)" % (world, o.gpus)
 
     cpu = None
-    if rank == 0 and world == 1 and not o.no_cpu_baseline:
+    if o.full and rank == 0 and world == 1 and not o.no_cpu_baseline:
         cpu = cpu_baseline(o.workload)            # before CUDA is initialised (fork-safe)
 
     import torch
@@ -598,9 +666,10 @@ def main():
     # One 6 ms sample (the driver's 20 steps) can be hit by a clock ramp or a host hiccup.  The region is therefore
     # checked against the device's own clock: the event-timed launches inside it must account for the wall time
     # (GPU-bound loop: wall = launches + a few us of gaps per step).  A region whose two clocks disagree by more than
-    # 10 % is measured again (at most 3 attempts, each EXACTLY o.steps steps); the attempt count is reported.
+    # 10 % is measured again under --full (at most 3 attempts, each EXACTLY o.steps steps); the attempt count is reported.
+    # A plain run times one region and reports its `consistent` flag.
     attempts = []
-    for attempt in range(3):
+    for attempt in range(3 if o.full else 1):
         t_in_ep, dt, host_dt, obs_ms, step_all, live_steps = timed_region(t_in_ep)
         # (every N-th step launch is event-timed: the launches of the region = their mean x the steps)
         launch_sum = (sum(ms for ms, _ in step_all) / len(step_all) * o.steps if step_all else 0.0) + sum(obs_ms)
@@ -617,9 +686,12 @@ def main():
         if all_ok:
             break
     gc.enable()
+    if o.dump_outputs and rank == 0:          # what the last timed step computed, before anything else runs
+        torch.cuda.synchronize()
+        dump_outputs(o.dump_outputs, rollout_outputs(trainer, (t_in_ep - 1) % T))
     # the store stream alone, same run: the stand-alone obs-assembly kernel on the same rows (rank 0, default configuration)
     store_ref_ms = []
-    if rank == 0 and step_all and not o.no_dense_obs and not o.incremental_obs:
+    if o.full and rank == 0 and step_all and not o.no_dense_obs and not o.incremental_obs:
         raw_env.obs_timer = []
         for _ in range(12):
             raw_env.observe_timed()
@@ -628,7 +700,7 @@ def main():
     # What SHIPS: Trainer.get_episode in its default execution mode — the episode's max_steps launches as ONE hipGraph, the
     # per-episode statistics read included — timed over whole episodes (>= the steps of the region above), every rank.
     ep_graph = None
-    if o.episode_graph and mega_live and not (o.overlap_obs or o.incremental_obs):
+    if o.full and o.episode_graph and mega_live and not (o.overlap_obs or o.incremental_obs):
         raw_env.obs_timer = None
         raw_env.step_timer = None
         a.hip_graph = True

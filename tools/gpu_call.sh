@@ -57,7 +57,7 @@ evidence)
   # hipGraph variants of the headline, rocprofv3 kernel stats, PMC HBM passes and SQ counter passes -> gpurun_out/evidence/
   B="python bench.py --no-cpu-baseline"
   timeout 300 $B --steps 40 > /dev/null 2>&1
-  timeout 600 python bench.py > $O/bench_pp_hard.json 2> $O/bench_pp_hard.err; summ $O/bench_pp_hard.json "pp_hard (default command)"
+  timeout 600 python bench.py --full > $O/bench_pp_hard.json 2> $O/bench_pp_hard.err; summ $O/bench_pp_hard.json "pp_hard (default command, --full)"
   timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_pp_hard_driver_args.json 2>/dev/null; summ $O/bench_pp_hard_driver_args.json "pp_hard --steps 20 --warmup 5"
   for w in tj_hard tj_medium pp_easy tj_medium_commnet_mlp pp_hard_ic pp_hard_iric; do timeout 300 $B --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; summ $O/bench_$w.json $w; done
   timeout 600 $B --workload pp_scaled --steps 40 > $O/bench_pp_scaled.json 2> $O/bench_pp_scaled.err; summ $O/bench_pp_scaled.json pp_scaled
