@@ -80,7 +80,8 @@ class EpisodeRecord(object):
         self.gate = [None] * T
         self.h_last = None
         self.n = 0
-        # (T, R, 4H) the activated gates of every step's LSTM cell and (T, R, 2H) the inp half of its [inp | h] rows, stored by
+        # (T, R, 4H) the activated gates of every step's LSTM cell and (T, R, 2H) the inp half of its [inp | h] rows (hid 256: (T, R, H),
+        # the inp rows alone — ops.record_xh_width), stored by
         # the step launch itself (ic3_env_set_record_out: Trainer._record_gates) — the backward then skips the gate product and
         # what leads up to it; gates_n = the steps that stored theirs
         self.gates = None
@@ -303,6 +304,10 @@ def backward_episode(args, net, raw, rec, d_out, acc, carry=None):
     # nothing on the host between them; the weight gradient of the window in one launch behind it)
     if given and bool(getattr(args, 'bptt_native_loop', True)) and d_out.shape[-1] <= 16 and ops.bptt_backward_supported(raw, H):
         return _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc)
+    if H == 256:
+        # (ic3_lstm_gates_backward_dx takes hid 64 / 128: at 256 the input gradient's split planes serve the window path alone,
+        #  and its record holds inp rows only (ops.record_xh_width), not the per-step loop's [inp | h] — the recomputing loop)
+        fused_dx = given = False
     if fused_gates:
         bias_parts = torch.zeros(((R + 63) // 64, 4 * H), dtype=torch.float32, device=dev)
     else:
@@ -509,9 +514,12 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
                       mode_avg=mode_avg, comm_zero=mask_zero, detach_gap=gap, row_live=live_flat, row_keep=keep_flat, enc_first=True,
                       gate_events=getattr(raw, 'gate_timer', None),     # (bench.py --mode train: HIP events around the gate launches)
                       two_chains=two)
-    work = acc.setdefault('_work', {})
-    ops.lstm_weight_grad(rec.xh[:T], rec.hs[:T], rec.gates[:T], acc['w_cat_t'], row_live=live_flat, accumulate=True, work=work,
-                         split=bool(getattr(args, 'gate_split', True)))
+    if H == 256:
+        _weight_grad_products(rec, T, R, H, acc['w_cat_t'], live_flat)
+    else:
+        work = acc.setdefault('_work', {})
+        ops.lstm_weight_grad(rec.xh[:T], rec.hs[:T], rec.gates[:T], acc['w_cat_t'], row_live=live_flat, accumulate=True, work=work,
+                             split=bool(getattr(args, 'gate_split', True)))
     dwt, db = raw.encode_backward_window_finish(H, want_bias=True) if ring else raw.encode_backward_finish(H, want_bias=True)
     acc['wt'].add_(dwt)
     acc['enc_bias'].add_(db)
@@ -523,6 +531,18 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
     else:
         _heads_grad_episode(rec, d_out, acc, T, R, H)
     return (dh_rec, dc_rec)
+
+
+def _weight_grad_products(rec, T, R, H, dW, row_live):
+    """The window's [W_ih | W_hh] gradient at hid 256 (ic3_lstm_weight_grad takes 64 / 128): two library products over all T x R
+    rows at once, behind the loop — dW[:H] += inp^T . dgates, dW[H:] += (row_live h)^T . dgates.  Collection mode scales the
+    dgates rows by row_live in place once the inp product has read them (the record is not read again): no T x R x H copy of h."""
+    Q = T * R
+    dg = rec.gates[:T].view(Q, 4 * H)
+    dW[:H].addmm_(rec.xh[:T].reshape(Q, H).t(), dg)
+    if row_live is not None:
+        dg.mul_(row_live.view(Q, 1))
+    dW[H:].addmm_(rec.hs[:T].reshape(Q, H).t(), dg)
 
 
 _SIDE_STREAMS = {}     # per device: the stream the heads' gradient runs on beside the backward's chain

@@ -452,7 +452,7 @@ class CommNetMLP(nn.Module):
                                                     self.f_module.weight_hh))
                     if split:   # the gate product as exact bf16 split products (ruling of round 3's verdict)
                         new['ps_l_wp3'] = ops.policy_pack_split(self.f_module.weight_ih, self.f_module.weight_hh)
-                        if self.hid_size in (64, 128):             # the update half's fused input gradient (bptt)
+                        if self.hid_size in (64, 128, 256):        # the update half's fused input gradient (bptt)
                             new['ps_l_wp3_bwd'] = ops.policy_pack_split_bwd(self.f_module.weight_ih, self.f_module.weight_hh)
                     for i in range(1, self.comm_passes):         # comm_passes > 1: what pass i swaps in (C_modules[i])
                         ci = self.C_modules[i]
@@ -671,7 +671,8 @@ class CommNetMLP(nn.Module):
             if record_out is not None:     # + the cell's activated gates and the inp rows into the record (the backward
                 g_out, x_out = record_out  #   skips the gate product and what leads up to it)
                 assert g_out.is_contiguous() and tuple(g_out.shape) == (R, 4 * H) and g_out.dtype == torch.float32
-                assert x_out is None or (x_out.is_contiguous() and tuple(x_out.shape) == (R, 2 * H) and x_out.dtype == torch.float32)
+                assert x_out is None or (x_out.is_contiguous() and tuple(x_out.shape) == (R, ops.record_xh_width(H))
+                                         and x_out.dtype == torch.float32)
                 env.set_record_out(g_out, x_out)
         else:
             assert record_out is None, "the gate record comes with the in-place episode record (one pass)"

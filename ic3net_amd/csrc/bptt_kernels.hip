@@ -539,7 +539,7 @@ extern "C" int ic3_comm_backward(const float* dxh, int ldd, const float* h_prev,
         return 0;
     }
     if (!h_prev || !c_weight || !dcw_partials) return fail(-22, "ic3_comm_backward: null argument");
-    if (H != 64 && H != 128) return fail(-38, "ic3_comm_backward: hid_size 64 / 128");
+    if (H != 64 && H != 128 && H != 256) return fail(-38, "ic3_comm_backward: hid_size 64 / 128 / 256");
     if (N > 64) return fail(-38, "ic3_comm_backward: at most 64 agents per env");
     const int ept = 64 / N, tiles = (E + ept - 1) / ept;
     if ((long long)64 * ldd * 4 >= (1ll << 31)) return fail(-22, "ic3_comm_backward: row stride too large");
@@ -547,7 +547,12 @@ extern "C" int ic3_comm_backward(const float* dxh, int ldd, const float* h_prev,
                          mode_avg, accumulate };
     const int grid = ic3_comm_backward_partials(E, N);
     const size_t lds = ((size_t)64 * (H + 4) + 128) * sizeof(float);
-    if (H == 128) {
+    if (H == 256) {
+        // (one 512-thread workgroup per CU — dC's 8 accumulator blocks per wave live across the tiles — so the 512 workgroups of
+        //  a large chain run as two rounds)
+        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(comm_bwd_kernel<256>), lds));
+        hipLaunchKernelGGL((comm_bwd_kernel<256>), dim3(grid), dim3(512), lds, s, a);
+    } else if (H == 128) {
         IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(comm_bwd_kernel<128>), lds));
         hipLaunchKernelGGL((comm_bwd_kernel<128>), dim3(grid), dim3(256), lds, s, a);
     } else {
@@ -623,7 +628,7 @@ extern "C" int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_pr
 extern "C" int ic3_bptt_backward_supported(const ic3_env* env, int H)
 {
     using namespace ic3;
-    if (!env || (H != 64 && H != 128) || env->dims.N > 64) return 0;
+    if (!env || (H != 64 && H != 128 && H != 256) || env->dims.N > 64) return 0;
     EncBwdPlan pl;
     if (env->kind == IC3_ENV_PP) {
         const ic3_pp_cfg& c = env->pp;
@@ -677,7 +682,7 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
     const int T = b->T, E = b->E, N = b->N, H = b->H;
     if (T <= 0 || E <= 0 || N <= 0 || E != env->dims.E || N != env->dims.N)
         return fail(-22, "ic3_bptt_backward: T, E, N must be positive and E, N the handle's");
-    if (!ic3_bptt_backward_supported(env, H)) return fail(-38, "ic3_bptt_backward: hid_size 64 / 128, <= 64 agents, a grid whose encoder backward runs in its partial-sums form");
+    if (!ic3_bptt_backward_supported(env, H)) return fail(-38, "ic3_bptt_backward: hid_size 64 / 128 / 256, <= 64 agents, a grid whose encoder backward runs in its partial-sums form");
     if (b->OT < 1 || b->OT > 16) return fail(-22, "ic3_bptt_backward: 1 <= OT <= 16");
     if (!b->gates || !b->hs || !b->cs || !b->dhead || !b->snaps || !b->lstm_wp3_bwd || !b->w_heads || !b->dh || !b->dc || !b->dxh ||
         !b->dbias_partials || !b->enc_work)

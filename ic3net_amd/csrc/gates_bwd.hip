@@ -508,7 +508,7 @@ extern "C" int ic3_lstm_gates_backward_given(const float* gates, float* xh, int 
     if (row_keep && !dc) return ic3::fail(-22, "ic3_lstm_gates_backward_given: row_keep scales dc");
     if ((lstm_wp3_bwd == nullptr) != (dxh == nullptr))
         return ic3::fail(-22, "ic3_lstm_gates_backward_given: lstm_wp3_bwd and dxh come together");
-    if (H != 64 && H != 128) return ic3::fail(-38, "ic3_lstm_gates_backward_given: hid_size 64 / 128");
+    if (H != 64 && H != 128 && H != 256) return ic3::fail(-38, "ic3_lstm_gates_backward_given: hid_size 64 / 128 / 256");
     if ((xh == nullptr) != (h_prev == nullptr))
         return ic3::fail(-22, "ic3_lstm_gates_backward_given: xh and h_prev come together (the copy into xh's h half) or not at all");
     return gates_backward_impl(xh, xh ? ldx : 2 * H, h_prev, nullptr, nullptr, nullptr, c_prev, dh, dc, dgates, dc_prev, dbias_partials,
@@ -532,8 +532,11 @@ static int gates_backward_impl(float* xh, int ldx, const float* h_prev, const fl
     const int tiles = (R + 63) / 64;
     const size_t lds = ((size_t)64 * (2 * H + 4) + 4 * H + (gates ? 64 * 16 : 0)) * sizeof(float);   // (+ the dhead tile)
     hipStream_t s = (hipStream_t)stream;
-    if (gates) {                                                 // (H 64 / 128: checked by the entry point)
-        if (H == 128) {
+    if (gates) {                                                 // (H 64 / 128 / 256: checked by the entry point)
+        if (H == 256) {                                          // (512 threads, one workgroup per CU: 140 KB of LDS)
+            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_gates_bwd_kernel<256, 1, 1>), lds));
+            hipLaunchKernelGGL((lstm_gates_bwd_kernel<256, 1, 1>), dim3(tiles), dim3(512), lds, s, a);
+        } else if (H == 128) {
             IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_gates_bwd_kernel<128, 1, 1>), lds));
             hipLaunchKernelGGL((lstm_gates_bwd_kernel<128, 1, 1>), dim3(tiles), dim3(256), lds, s, a);
         } else {

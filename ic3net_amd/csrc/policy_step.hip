@@ -551,8 +551,11 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
             }
             if constexpr (KIND != 0 && MP == 0) {
                 if (a.xh_out) {   // (uniform; ic3_env_set_record_out) the same values -> the inp half of the record's [inp | h] rows
-                    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.xh_out + r0 * 2 * H, (uint32_t)rows * 2 * H * 4u);
-                    const int xoff = (4 * lh * 2 * H + col) * 4;
+                    // (hid 256: inp rows alone, row stride H — the window backward reads h from the (h, c) record, and the wide
+                    //  layout would not fit beside the gate record at the shapes hid 256 is trained at)
+                    constexpr int XLD = H == 256 ? H : 2 * H;
+                    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.xh_out + r0 * XLD, (uint32_t)rows * XLD * 4u);
+                    const int xoff = (4 * lh * XLD + col) * 4;
 #pragma unroll
                     for (int rt = 0; rt < 2; ++rt) {
                         if (rt == 1 && !two) break;
@@ -560,7 +563,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                         for (int reg = 0; reg < 16; ++reg) {
                             const float xv = accC[rt][reg];           // (a copy: bit_cast of a vector element reads element 0)
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, xv), rx,
-                                                                  xoff + (32 * rt + (reg & 3) + 8 * (reg >> 2)) * 2 * H * 4, 0, PS_ZSTORE_AUX);
+                                                                  xoff + (32 * rt + (reg & 3) + 8 * (reg >> 2)) * XLD * 4, 0, PS_ZSTORE_AUX);
                         }
                     }
                 }
@@ -1424,8 +1427,8 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
         a.c_out = armed_c;
     }
     if (!inner && armed_g) {
-        if (!a.l_wp3 || a.npass > 1 || (H != 64 && H != 128))
-            return fail(-38, "ic3_env_set_record_out: the gate record needs gate_split, one communication pass, hid_size 64 / 128");
+        if (!a.l_wp3 || a.npass > 1 || (H != 64 && H != 128 && H != 256))
+            return fail(-38, "ic3_env_set_record_out: the gate record needs gate_split, one communication pass, hid_size 64 / 128 / 256");
         a.gates_out = armed_g;
         a.xh_out = armed_x;
     }

@@ -349,6 +349,12 @@ def bptt_backward_supported(env, H):
     return bool(_lib.lib().ic3_bptt_backward_supported(env._h, int(H)))
 
 
+def record_xh_width(H):
+    """Row width of the inp record ic3_env_set_record_out writes: 2H ([inp | h] rows, the h half left to the backward) at hid
+    64 / 128, H (inp rows alone) at hid 256."""
+    return H if H == 256 else 2 * H
+
+
 def bptt_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lstm_wp3_bwd, w_heads, c_weight, dh, dc, dxh,
                   dbias_partials, dcw_partials, mode_avg=True, comm_zero=False, detach_gap=0, row_live=None, row_keep=None,
                   enc_first=True, gate_events=None, two_chains=False):

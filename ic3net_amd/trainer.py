@@ -244,7 +244,7 @@ class Trainer(object):
             if rec_gates:
                 try:
                     self._rec.gates = torch.empty((T, E * N, 4 * knet.hid_size), dtype=torch.float32, device=dev)
-                    self._rec.xh = torch.empty((T, E * N, 2 * knet.hid_size), dtype=torch.float32, device=dev)
+                    self._rec.xh = torch.empty((T, E * N, ops.record_xh_width(knet.hid_size)), dtype=torch.float32, device=dev)
                 except torch.cuda.OutOfMemoryError:                # (the budget above is an estimate: recompute instead)
                     self._rec.gates = self._rec.xh = None
         self._ones_comm = self._static['ones'] if args.comm_action_one else None
@@ -269,7 +269,7 @@ class Trainer(object):
     def _record_gates(self, knet, T, R):
         """Native update: let every step launch of the recorded rollout store its cell's activated gates in the episode record
         and the inp rows (ic3_env_set_record_out), so the backward reads them instead of running the gate product again — where the record is
-        the in-place one, the split gate product and its backward planes exist (hid 64 / 128), and the records of the batch stay
+        the in-place one, the split gate product and its backward planes exist (hid 64 / 128 / 256), and the records of the batch stay
         within a third of the device's memory (args.record_gates=False: recompute)."""
         a = self.args
         if not getattr(a, 'record_gates', True) or not getattr(a, 'recurrent', False) or not self._rec_inplace():
@@ -281,15 +281,19 @@ class Trainer(object):
         with torch.no_grad():
             fc = knet._fused_cache()
         H = knet.hid_size
-        if fc.get('ps_l_wp3') is None or fc.get('ps_l_wp3_bwd') is None or H not in (64, 128) \
+        if fc.get('ps_l_wp3') is None or fc.get('ps_l_wp3_bwd') is None or H not in (64, 128, 256) \
                 or not getattr(a, 'fused_input_grad', True):
+            return False
+        # hid 256: the record is read by the window backward alone (ic3_bptt_backward; the per-step loop recomputes there)
+        if H == 256 and (bptt._is_baseline(self.policy_net) or not getattr(a, 'bptt_native_loop', True)
+                         or not ops.bptt_backward_supported(self.env.env, H)):
             return False
         # what this episode's gate / inp records need against what the device can still give: free memory + the blocks torch's
         # allocator holds unused, half of it at most (the backward's own buffers, the graph pools and other ranks on the device
         # need room too); an allocation that fails anyway falls back to the recomputing backward (begin_episode)
         free, _total = torch.cuda.mem_get_info()
         cached = torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
-        return T * R * 6 * H * 4 <= (free + max(cached, 0)) // 2
+        return T * R * (4 * H + ops.record_xh_width(H)) * 4 <= (free + max(cached, 0)) // 2
 
     def _rec_inplace(self):
         """The recorded rollout of a native update reads / writes (h, c) in the episode record (no copies) when every

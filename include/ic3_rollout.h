@@ -371,7 +371,7 @@ int ic3_lstm_gates_backward_dx(float* xh, int ldx, const float* h_prev /* or NUL
  * follows; lstm_wp3_bwd / dxh (both or neither): the input gradient in the same launch.  Collection mode (trainer.py:227-242:
  * a record slot where some envs start an episode, or after which the recurrent gradient must not pass): row_live [R] or NULL —
  * c_prev and the copied h_prev of a row are multiplied by it (0 = the env starts an episode at this slot: zero state);
- * row_keep [R] or NULL — dc of a row is multiplied by it (0 = nothing arrives from the next slot).  hid_size 64 / 128.
+ * row_keep [R] or NULL — dc of a row is multiplied by it (0 = nothing arrives from the next slot).  hid_size 64 / 128 / 256.
  * Round 6: dgates may BE gates (every lane overwrites exactly what it read: the record turns into the weight-gradient
  * product's operand in place); dhead [R][OT] / w_heads [OT][H] (both or neither, OT <= 16): the heads' share of dL/dh_t —
  * dhead . w_heads with dhead = dL/d[logits of every head | value] (comm.py:228,239), w_heads = heads.k.weight stacked, then
@@ -395,7 +395,7 @@ int ic3_lstm_gates_backward_given(const float* gates, float* xh /* or NULL */, i
  * gradient that must not cross an episode boundary or a detach point is dropped where it is produced); dcw_partials
  * [ic3_comm_backward_partials(E, N)][H][H]: one partial per workgroup, written (accumulate == 0) or added to — their sum over dim 0
  * is the gradient.  comm_zero != 0 (comm.py:40-41: C sees zeros): dh_out = d h_direct * out_scale, nothing else is read.
- * Exact fp32 products on the fp32 matrix instruction.  hid_size 64 / 128, <= 64 agents per env.  Returns the number of partials
+ * Exact fp32 products on the fp32 matrix instruction.  hid_size 64 / 128 / 256, <= 64 agents per env.  Returns the number of partials
  * written (0 with comm_zero), negative errno on error. */
 int ic3_comm_backward_partials(int E, int N);
 int ic3_comm_backward(const float* dxh, int ldd, const float* h_prev, const int32_t* alive /* or NULL */,
@@ -410,7 +410,8 @@ int ic3_comm_backward(const float* dxh, int ldd, const float* h_prev, const int3
  * mode: h_prev rows times it).  scratch: ic3_lstm_weight_grad_scratch_floats(Q, H) floats.  split != 0 (what ic3net_amd passes
  * with args.gate_split, the default): every fp32 operand split exactly into three bf16 terms, all nine cross products on the bf16
  * matrix cores, fp32 accumulation — the arithmetic of the rollout's gate product (ic3_policy.gate_split); split == 0: the fp32 matrix
- * instruction.  Exact products either way, split-K over the CUs, slices summed in order (reproducible).  hid_size 64 / 128. */
+ * instruction.  Exact products either way, split-K over the CUs, slices summed in order (reproducible).  hid_size 64 / 128 (at 256
+ * ic3net_amd forms the same two products, inp^T . dgates and (row_live h_prev)^T . dgates, as library GEMMs over the window). */
 size_t ic3_lstm_weight_grad_scratch_floats(long long Q, int H);
 int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const float* dgates, const float* row_live /* or NULL */,
                          long long Q, int H, float* dW, int accumulate, int split, float* scratch, ic3_stream stream);
@@ -418,7 +419,7 @@ int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const f
 /* The backward through a window of T recorded steps (trainer.py:128-225 over comm.py:134-244, one communication pass, recorded
  * gates), last step first, as ONE host call — per step: ic3_lstm_gates_backward_given (in place on the gate record, the heads'
  * share folded in, the input gradient in the same launch) -> ic3_comm_backward -> ic3_env_encode_backward_accumulate on the step's
- * snapshot; nothing runs on the host between the launches.  Afterwards the caller runs ic3_lstm_weight_grad over the window
+ * snapshot; nothing runs on the host between the launches.  Afterwards the caller runs ic3_lstm_weight_grad (hid 64 / 128) over the window
  * (gates now holds dgates), ic3_heads_grad, ic3_env_encode_backward_finish and sums the partials.
  *   gates [T][R][4H] in: the recorded activated gates, out: dgates;  hs, cs [>= T][R][H] the state ENTERING every step;
  *   dhead [T][R][OT];  snaps: T snapshots, snap_words int32 apart;  alive / gate: HOST arrays of T device pointers ([E][N] int32,
@@ -428,7 +429,7 @@ int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const f
  *   window's last step, out: leaving its first;  dxh [R][2H] scratch (or a ring of T of them: dxh_step);  dbias_partials [ceil(R / 64)][4H] and dcw_partials
  *   [ic3_comm_backward_partials][H][H] are ADDED to (zero them before the first window);  enc_work as
  *   ic3_env_encode_backward_accumulate, enc_first != 0: this window starts the accumulation;  gate_events: see the struct.
- * ic3_bptt_backward_supported(env, H): 1 when every step can run (hid_size 64 / 128, <= 64 agents, the encoder backward in its
+ * ic3_bptt_backward_supported(env, H): 1 when every step can run (hid_size 64 / 128 / 256, <= 64 agents, the encoder backward in its
  * partial-sums form) — the loop overwrites the record as it goes, so ask first. */
 typedef struct ic3_bptt {
     uint32_t struct_size;   /* sizeof(ic3_bptt) of the caller's header (checked: -EINVAL on mismatch) */
@@ -639,8 +640,9 @@ int ic3_env_set_hidden_out(ic3_env* env, float* h_out, float* c_out);
  * (trainer.py:128-225 over a recorded rollout): `gates` [E*N][4H] = the activated gates of its LSTM cell — sigmoid(i) |
  * sigmoid(f) | tanh(g) | sigmoid(o), exactly the values its cell update used — for ic3_lstm_gates_backward_given; and, when
  * `xh` is not NULL, the inp half of the rows of xh [E*N][2H] (row stride 2H; inp = encoder(obs) + C(comm) + both biases, the
- * left operand of the gate product — the h half is not touched: ic3_lstm_gates_backward_given copies h_prev there).
- * Needs ic3_policy.gate_split, one communication pass per launch, hid_size 64 / 128 (-38 from the step call otherwise);
+ * left operand of the gate product — the h half is not touched: ic3_lstm_gates_backward_given copies h_prev there); at hid_size
+ * 256 xh is [E*N][H], the inp rows alone (row stride H: the window backward reads h_prev from the recorded hidden states).
+ * Needs ic3_policy.gate_split, one communication pass per launch, hid_size 64 / 128 / 256 (-38 from the step call otherwise);
  * gates = NULL disarms.  Costs 16 H (+ 4 H) bytes of stores per agent row in the launch; nothing when not armed. */
 int ic3_env_set_record_out(ic3_env* env, float* gates, float* xh /* or NULL */);
 int ic3_policy_step_supported(const ic3_env* env, int H); /* 0, or the LDS bytes per workgroup */
