@@ -79,6 +79,16 @@ class Bptt(C.Structure):
                 ("dxh_step", C.c_int64), ("two_chains", C.c_int32), ("gate_events", C.POINTER(C.c_void_p))]
 
 
+class RnnBptt(C.Structure):
+    """ic3_rnn_bptt (include/ic3_rollout.h): one window of the tanh-recurrence baseline's backward through time."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "detach_gap", "enc_first",
+                                                                        "enc_window")] + \
+               [("hs", C.c_void_p), ("h_last", C.c_void_p), ("dhead", C.c_void_p), ("snaps", C.c_void_p), ("snap_words", C.c_int64),
+                ("a2", C.c_void_p), ("w_heads", C.c_void_p), ("row_live", C.c_void_p), ("row_keep", C.c_void_p), ("dh", C.c_void_p),
+                ("dz", C.c_void_p), ("dbias_partials", C.c_void_p), ("enc_work", C.c_void_p), ("a2_grad", C.c_void_p),
+                ("wgrad_scratch", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "ic3_version": (C.c_int, []),
@@ -138,6 +148,13 @@ EXPORTS = {
     "ic3_bptt_first_chain_envs": (C.c_int, [C.c_int, C.c_int]),
     "ic3_bptt_backward_supported": (C.c_int, [C.c_void_p, C.c_int]),
     "ic3_bptt_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ic3_rnn_backward_supported": (C.c_int, [C.c_void_p, C.c_int]),
+    "ic3_rnn_backward_partials": (C.c_int, [C.c_longlong, C.c_int]),
+    "ic3_rnn_tanh_backward_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
+    "ic3_rnn_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ic3_rnn_weight_grad_scratch_floats": (C.c_size_t, [C.c_longlong, C.c_int]),
+    "ic3_rnn_weight_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
     "ic3_env_set_record_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ic3_lstm_gates_backward_dx": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ic3_commnet_forward_supported": (C.c_int, [C.c_int, C.c_int]),

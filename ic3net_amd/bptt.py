@@ -275,6 +275,8 @@ def backward_episode(args, net, raw, rec, d_out, acc, carry=None):
         si = standin_for_backward(args, net, rec)
         if si is not None:
             return _backward_episode_standin(net, si, raw, rec, d_out, acc, carry)
+        if _rnn_window_ok(args, net, raw, rec, d_out):
+            return _backward_window_rnn(args, net, raw, rec, d_out, acc, carry)
         return _backward_episode_baseline(args, net, raw, rec, d_out, acc, carry)
     if not rec.recurrent:
         return _backward_episode_commnet(args, net, raw, rec, d_out, acc)
@@ -840,6 +842,77 @@ def fold_standin(acc):
     acc['l_b'].add_(acc2['b_cat'])
     acc['w_heads'].add_(acc2['w_heads'])
     acc['b_heads'].add_(acc2['b_heads'])
+
+
+RNN_WINDOW_SIZES = (64, 128)     # ic3_rnn_backward
+
+
+def _rnn_window_ok(args, net, raw, rec, d_out):
+    """models.RNN with the tanh recurrence on a record at its own hid_size (64 / 128), at most 16 output columns, the native loop
+    on (args.bptt_native_loop), the library's answer and the room for the T x R x H ring of dz: _backward_window_rnn."""
+    H = args.hid_size
+    if not rec.recurrent or getattr(args, 'rnn_type', 'MLP') != 'MLP' or not hasattr(net, 'affine2') or H not in RNN_WINDOW_SIZES:
+        return False
+    if rec.hs.shape[2] != H or d_out.shape[-1] > 16 or not bool(getattr(args, 'bptt_native_loop', True)) or not rec.hs.is_cuda:
+        return False
+    if not hasattr(raw, '_h') or not ops.rnn_backward_supported(raw, H):
+        return False
+    return _ring_fits(rec.hs.device, rec.n * rec.hs.shape[1] * H * 4)
+
+
+def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
+    """_backward_episode_baseline's tanh branch for a whole window through ic3_rnn_backward (csrc/bptt_kernels.hip).  Per step, last
+    to first, ONE launch: dh_t = dh + d_t . W_heads, dz_t = dh_t (1 - h_t^2) into a ring of T slots, dh <- (dz_t . A2) * keep_{t-1},
+    the column sums of dz_t as per-workgroup partials; then the sparse encoder's first stage over the ring, and affine2's weight
+    gradient sum_t dz_t^T (live_t h_{t-1}) over all T x R rows in one launch.  Behind it: the encoder's expansion (affine1.weight),
+    the partials' sum (both biases: affine1(obs) + affine2(h) share dz), the heads' pass beside the chain.  Same cuts as the loop
+    (detach points; collection mode: keep / row_live, the carry in and out); the record is read, never written."""
+    T, R, H = rec.n, rec.hs.shape[1], rec.hs.shape[2]
+    N = net.args.nagents
+    E = R // N
+    dev = rec.hs.device
+    dh = torch.zeros((R, H), dtype=torch.float32, device=dev)
+    dz = torch.empty((T, R, H), dtype=torch.float32, device=dev)
+    parts = torch.zeros((ops.rnn_backward_partials(R, H), H), dtype=torch.float32, device=dev)
+    live_flat = keep_flat = None
+    gap = int(getattr(args, 'detach_gap', 10000))
+    if rec.stream is not None:
+        if carry is not None:
+            dh.copy_(carry[0])
+        fresh, keep = rec.stream['fresh'][:T], rec.stream['keep'][:T]
+        live_flat = (~fresh).to(torch.float32).repeat_interleave(N, dim=1).contiguous()
+        keep_flat = keep.to(torch.float32).repeat_interleave(N, dim=1).contiguous()
+        dh.mul_(keep_flat[T - 1].unsqueeze(1))                            # what the next window handed over, cut at its border
+        gap = 0                                                           # (the env's OWN detach points are in `keep`)
+    elif gap > T:
+        gap = 0
+    dhead = d_out[:T] if d_out[:T].is_contiguous() else d_out[:T].contiguous()
+    h_last = None if (rec.h_last is None or (rec.hs.shape[0] > T and rec.h_last.data_ptr() == rec.hs[T].data_ptr())) else rec.h_last
+    w_heads = torch.cat([hd.weight for hd in net.heads] + [net.value_head.weight], 0).detach().contiguous()
+    a2 = net.affine2.weight.detach().contiguous()
+    enc_window = bool(getattr(args, 'enc_window', True)) and raw.encode_window_work(H) is not None
+    side = None                                                           # the heads' gradient beside the chain (_backward_window_native)
+    if dev.type == 'cuda' and bool(getattr(args, 'heads_grad_beside', True)) and not torch.cuda.is_current_stream_capturing():
+        main = torch.cuda.current_stream(dev)
+        side = _SIDE_STREAMS.get(dev.index)
+        if side is None:
+            side = _SIDE_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            _heads_grad_episode(rec, d_out, acc, T, R, H)
+    ops.rnn_backward(raw, T, E, N, H, rec.hs, dhead, rec.snaps, a2, w_heads, dh, dz, parts, h_last=h_last, detach_gap=gap,
+                     row_live=live_flat, row_keep=keep_flat, enc_first=True, enc_window=enc_window, a2_grad=acc['a2_w'],
+                     work=acc.setdefault('_work', {}))
+    dwt, _ = raw.encode_backward_window_finish(H, want_bias=False) if enc_window else raw.encode_backward_finish(H, want_bias=False)
+    acc['wt'].add_(dwt)
+    bsum = parts.sum(0)
+    acc['a1_b'].add_(bsum)
+    acc['a2_b'].add_(bsum)
+    if side is not None:
+        torch.cuda.current_stream(dev).wait_stream(side)
+    else:
+        _heads_grad_episode(rec, d_out, acc, T, R, H)
+    return (dh, dh)
 
 
 def _backward_episode_baseline(args, net, raw, rec, d_out, acc, carry=None):

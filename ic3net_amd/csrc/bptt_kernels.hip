@@ -750,3 +750,357 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
                                               stream);
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// ic3_rnn_backward: the IC / IRIC baselines' tanh recurrence (models.py:68-92, rnn_type 'MLP'),
+//     h_t = tanh(affine1(obs_t) + affine2(h_{t-1})),   [logits | value]_t = W_heads h_t + b,
+// differentiated over a window of recorded steps, last to first.  Per step ONE launch (rnn_tanh_bwd_kernel):
+//     dh_t   = dh_in + d_t . W_heads                      (dh_in: what step t + 1 sent back; zeros at a detach point)
+//     dz_t   = dh_t * (1 - h_t^2)                          -> the ring slot t (the affine1 / affine2 pre-activation gradient)
+//     dh_out = (dz_t . A2) * out_scale                     (A2 = affine2.weight; out_scale = row_keep[t - 1] in collection mode)
+//     per-workgroup column sums of dz_t                    (d affine1.bias = d affine2.bias; fixed-order reduction by the caller)
+// and behind the loop ONE launch for dA2 += sum_t dz_t^T . (row_live_t h_{t-1}) over all T x R rows (rnn_wgrad_kernel).
+//
+// rnn_tanh_bwd_kernel<H>: 4H threads (H / 8 waves), persistent over tiles of 64 rows.  A2 sits in LDS for the workgroup's life,
+// in fragment order: float4 (kb, hi, col) = A2[8 kb + 4 hi + j][col], j = 0..3 — the B operand of four 32 x 32 x 2 MFMAs is one
+// conflict-free ds_read_b128.  Per tile: phase 0 — thread (row group, 4-column chunk) forms dz for 4 rows (its W_heads chunk and
+// the tile's d rows from LDS), writes it to the ring and to the LDS tile, adds it to its column sums; phase 1 — wave (rb, cb)
+// multiplies tile rows [32 rb, +32) by A2's columns [32 cb, +32) and writes dh_out.  dh_out may be dh_in: a workgroup reads all
+// of its tile's dh_in rows before the barrier in front of the product, and no other workgroup touches those rows.
+// LDS: H^2 + 64 (H + 4) + 16 H + 1024 floats (110 KB at H = 128: one workgroup of 8 waves per CU; 41 KB at 64: two of 4).
+// HBM per row: dh_in, h_t in, dz, dh_out out (4 H floats) + OT; MFMA 2 H^2 flop per row on the fp32 instruction.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace ic3 {
+
+struct RnnBwdArgs {
+    const float* dh_in;      // [R][H] or null (zeros)
+    const float* h;          // [R][H] h_t
+    const float* dhead;      // [R][OT]
+    const float* w_heads;    // [OT][H]
+    const float* a2;         // [H][H] affine2.weight (out, in): dh_out = dz . A2
+    const float* out_scale;  // [R] or null
+    float* dz;               // [R][H]
+    float* dh_out;           // [R][H]
+    float* db_part;          // [gridDim.x][H]
+    int R, OT, tiles, accumulate;
+};
+
+template <int H>
+__global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void rnn_tanh_bwd_kernel(const RnnBwdArgs a)
+{
+    constexpr int NT = 4 * H, H4 = H / 4, LDA = H + 4, LDA4 = LDA / 4, CB = H / 32, RPP = NT / H4, PER = 64 / RPP;
+    static_assert(RPP * PER == 64 && NT / 64 == 2 * CB, "tile split");
+    IC3_DYNAMIC_LDS(float, smem);
+    const bp_f32x4* const Bf4 = reinterpret_cast<const bp_f32x4*>(smem);     // [H / 8][2][H] float4
+    float* const Dz = smem + H * H;                                          // [64][LDA] the tile's dz
+    bp_f32x4* const Dz4 = reinterpret_cast<bp_f32x4*>(Dz);
+    float* const Wh = Dz + 64 * LDA;                                         // [16][H] W_heads
+    const bp_f32x4* const Wh4 = reinterpret_cast<const bp_f32x4*>(Wh);
+    float* const Sd = Wh + 16 * H;                                           // [64][OT] the tile's d rows
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
+    const int cb = w % CB, rb = w / CB;
+    const int c4 = tid % H4, rg = tid / H4;                      // phase 0: column chunk c4 of rows rg + RPP i
+    const int OT = a.OT;
+    for (int i = tid; i < H * H; i += NT) {
+        const int k = i / H, col = i - k * H;
+        smem[(((k >> 3) * 2 + ((k >> 2) & 1)) * H + col) * 4 + (k & 3)] = a.a2[i];
+    }
+    for (int i = tid; i < OT * H; i += NT) Wh[i] = a.w_heads[i];
+    bp_f32x4 bsum = { 0.f, 0.f, 0.f, 0.f };
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        const long long r0 = (long long)tile * 64;
+        const int rows = (a.R - r0) < 64 ? (int)(a.R - r0) : 64;
+        // (rows past the tile read 0 and their stores are dropped: the ranges of the buffer descriptors)
+        const __amdgpu_buffer_rsrc_t rdi = bp_rsrc(a.dh_in ? a.dh_in + r0 * H : a.h, a.dh_in ? (long long)rows * H * 4 : 0);
+        const __amdgpu_buffer_rsrc_t rh = bp_rsrc(a.h + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rd = bp_rsrc(a.dhead + r0 * OT, (long long)rows * OT * 4);
+        const __amdgpu_buffer_rsrc_t rz = bp_rsrc(a.dz + r0 * H, (long long)rows * H * 4);
+        bp_f32x4 dv[PER], hv[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int off = ((rg + RPP * i) * H + 4 * c4) * 4;
+            dv[i] = bp_load4(rdi, off);
+            hv[i] = bp_load4(rh, off);
+        }
+        for (int i = tid; i < 64 * OT; i += NT) Sd[i] = bp_load1(rd, i * 4);
+        __syncthreads();
+        // ---- phase 0: dz of the tile -> ring, LDS, column sums
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int row = rg + RPP * i;
+            bp_f32x4 v = dv[i];
+            for (int o = 0; o < OT; ++o) v += Sd[row * OT + o] * Wh4[o * H4 + c4];
+            const bp_f32x4 z = v * (1.0f - hv[i] * hv[i]);
+            bsum += z;
+            Dz4[row * LDA4 + c4] = z;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, z), rz, (row * H + 4 * c4) * 4, 0, 0);
+        }
+        __syncthreads();
+        // ---- phase 1: dh_out = dz . A2 on the fp32 matrix instruction (k = 8 kb + 4 lh + j: A fragment and B slot agree)
+        bp_f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+#pragma unroll 4
+        for (int kb = 0; kb < H / 8; ++kb) {
+            const bp_f32x4 a4 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
+            const bp_f32x4 b4 = Bf4[(2 * kb + lh) * H + 32 * cb + li];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bp_mfma(acc, a4[j], b4[j]);
+        }
+        const __amdgpu_buffer_rsrc_t rout = bp_rsrc(a.dh_out + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rsc = bp_rsrc(a.out_scale ? a.out_scale + r0 : a.dh_out, a.out_scale ? (long long)rows * 4 : 0);
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int lr = 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+            float o = acc[reg];
+            if (a.out_scale) o *= bp_load1(rsc, lr * 4);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o), rout, (lr * H + 32 * cb + li) * 4, 0, 0);
+        }
+        __syncthreads();                                         // every wave is done with the tile's LDS
+    }
+    // column sums of the workgroup: the RPP row groups of a chunk added in group order (reproducible)
+    Dz4[rg * H4 + c4] = bsum;
+    __syncthreads();
+    if (tid < H4) {
+        bp_f32x4 s = Dz4[tid];
+        for (int g = 1; g < RPP; ++g) s += Dz4[g * H4 + tid];
+        bp_f32x4* dst = reinterpret_cast<bp_f32x4*>(a.db_part + (size_t)blockIdx.x * H) + tid;
+        *dst = a.accumulate ? *dst + s : s;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// ic3_rnn_weight_grad.  dA2[m][n] = sum_q dz[q][m] (row_live[q] h_prev[q][n]) over Q = T x R rows.  Workgroup = K slice of the
+// rows, all H x H outputs; 4 waves as 2 (m) x 2 (n), a wave holds (H / 2) x (H / 2) of the result (MB x MB blocks of 32 x 32).
+// Both operands row-major with q outermost — the K-major pair v_mfma_f32_32x32x2_f32 wants: lane (i, kk) supplies dz[q0 + kk][m(i)]
+// and h[q0 + kk][n(i)].  Staging: KT = 16 rows of each per stage, global -> registers -> LDS, double-buffered, one barrier per
+// stage (the shape of lstm_wgrad_kernel).  Bound: HBM (2 H floats per row) against MFMA (2 H^2 flop per row) — about even at 128.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct RnnWGradArgs {
+    const float* dz;         // [Q][H]
+    const float* h;          // [Q][H] h_prev
+    const float* row_live;   // [Q] or null: h rows times it
+    float* part;             // [gridDim.x][H][H]
+    long long Q;
+    int rows_per_wg;         // rows per K slice (a multiple of 16)
+};
+
+template <int H>
+__global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
+{
+    constexpr int KT = 16, NT = 256, H4 = H / 4, MB = H / 64, HH = H / 2;
+    constexpr int RPS = NT / H4, PT = KT / RPS;                  // rows staged per pass, passes per stage (2 at H = 128, 1 at 64)
+    constexpr int SW = 2 * KT * H;                               // stage b: dz rows at smem + b * SW, h rows behind them
+    static_assert(PT >= 1 && RPS * PT == KT, "staging split");
+    IC3_DYNAMIC_LDS(float, smem);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
+    const int wm = w & 1, wn = w >> 1;
+    const long long q0 = (long long)blockIdx.x * a.rows_per_wg;
+    long long nq = a.Q - q0;
+    if (nq > a.rows_per_wg) nq = a.rows_per_wg;
+    if (nq < 0) nq = 0;
+    const __amdgpu_buffer_rsrc_t rz = bp_rsrc(nq > 0 ? a.dz + q0 * H : a.dz, nq * H * 4);
+    const __amdgpu_buffer_rsrc_t rh = bp_rsrc(nq > 0 ? a.h + q0 * H : a.h, nq * H * 4);
+    const __amdgpu_buffer_rsrc_t rl = bp_rsrc(a.row_live && nq > 0 ? a.row_live + q0 : a.h, a.row_live ? nq * 4 : 0);
+    const int nstages = (int)((nq + KT - 1) / KT);
+    const int srow = tid / H4, sc4 = tid - srow * H4;            // a thread stages rows srow + RPS i, column chunk sc4
+    bp_f32x4 zr[PT], hr[PT];
+    auto fetch = [&](int s) {
+        const int qb = s * KT;
+#pragma unroll
+        for (int i = 0; i < PT; ++i) {
+            const int off = ((srow + RPS * i) * H + 4 * sc4) * 4;
+            zr[i] = __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, off, qb * H * 4, 0));
+            hr[i] = __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, off, qb * H * 4, 0));
+            if (a.row_live) hr[i] *= bp_load1(rl, (srow + RPS * i) * 4, qb * 4);
+        }
+    };
+    auto stash = [&](int b) {
+        bp_f32x4* Z4 = reinterpret_cast<bp_f32x4*>(smem + b * SW);
+        bp_f32x4* P4 = Z4 + KT * H4;
+#pragma unroll
+        for (int i = 0; i < PT; ++i) {
+            Z4[tid + i * NT] = zr[i];
+            P4[tid + i * NT] = hr[i];
+        }
+    };
+    bp_f32x16 acc[MB][MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < MB; ++nb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[mb][nb][i] = 0.0f;
+    if (nstages > 0) {
+        fetch(0);
+        stash(0);
+    }
+    __syncthreads();
+    for (int s = 0; s < nstages; ++s) {
+        const bool more = s + 1 < nstages;
+        if (more) fetch(s + 1);
+        const float* Zs = smem + (s & 1) * SW;
+        const float* Ps = Zs + KT * H;
+#pragma unroll
+        for (int ks = 0; ks < KT / 2; ++ks) {
+            const int kr = 2 * ks + lh;
+            float av[MB], bv[MB];
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb) {
+                av[mb] = Zs[kr * H + wm * HH + 32 * mb + li];
+                bv[mb] = Ps[kr * H + wn * HH + 32 * mb + li];
+            }
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < MB; ++nb) bp_mfma(acc[mb][nb], av[mb], bv[nb]);
+        }
+        if (more) stash((s + 1) & 1);
+        __syncthreads();
+    }
+    // block (mb, nb), register reg, lane (li, lh): m = wm H / 2 + 32 mb + (reg & 3) + 8 (reg >> 2) + 4 lh, n = wn H / 2 + 32 nb + li
+    float* dst = a.part + (size_t)blockIdx.x * H * H;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < MB; ++nb)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int m = wm * HH + 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                dst[(size_t)m * H + wn * HH + 32 * nb + li] = acc[mb][nb][reg];
+            }
+}
+
+}  // namespace ic3
+
+// ---- ic3_rnn_backward --------------------------------------------------------------------------------------------------------
+// Tile plan of the per-step launch: tiles of 64 rows, at most one round of workgroup slots (one per CU at hid 128, two at 64), and
+// every workgroup the same number of tiles — the launch lasts as long as the workgroup with the most tiles either way, and every
+// workgroup fewer is one partial less to sum (PP-hard, E = 8192: 1280 tiles on 256 CUs = 256 workgroups x 5, no thin last round).
+extern "C" int ic3_rnn_backward_partials(long long R, int H)
+{
+    if (R <= 0 || (H != 64 && H != 128)) return 0;
+    const long long tiles = (R + 63) / 64;
+    const long long cap = (long long)ic3::bp_cus() * (H == 64 ? 2 : 1);
+    const long long rounds = (tiles + cap - 1) / cap;
+    return (int)((tiles + rounds - 1) / rounds);
+}
+
+extern "C" int ic3_rnn_backward_supported(const ic3_env* env, int H)
+{
+    if (!env || (H != 64 && H != 128)) return 0;
+    return ic3_bptt_backward_supported(env, H);    // (the sparse encoder's backward in its partial-sums form)
+}
+
+static int rnn_wgrad_slices(long long Q)
+{
+    int ks = 2 * ic3::bp_cus();                                  // two workgroups per CU
+    const long long most = (Q + 15) / 16;
+    if (ks > most) ks = (int)most;
+    return ks < 1 ? 1 : ks;
+}
+
+extern "C" size_t ic3_rnn_weight_grad_scratch_floats(long long Q, int H)
+{
+    if (Q <= 0 || (H != 64 && H != 128)) return 0;
+    return (size_t)rnn_wgrad_slices(Q) * H * H;
+}
+
+extern "C" int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const float* row_live, long long Q, int H, float* dA2,
+                                   int accumulate, float* scratch, ic3_stream stream)
+{
+    using namespace ic3;
+    if (!dz || !h_prev || !dA2 || !scratch || Q <= 0) return fail(-22, "ic3_rnn_weight_grad: null argument");
+    if (H != 64 && H != 128) return fail(-38, "ic3_rnn_weight_grad: hid_size 64 / 128");
+    const int ks = rnn_wgrad_slices(Q);
+    long long per = (Q + ks - 1) / ks;
+    per = (per + 15) / 16 * 16;
+    if (per * H * 4 >= (1ll << 31)) return fail(-22, "ic3_rnn_weight_grad: a K slice must stay below 2 GB (32-bit buffer offsets)");
+    const RnnWGradArgs a{ dz, h_prev, row_live, scratch, Q, (int)per };
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lds = (size_t)2 * 2 * 16 * H * sizeof(float);
+    if (H == 128) {
+        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_wgrad_kernel<128>), lds));
+        hipLaunchKernelGGL((rnn_wgrad_kernel<128>), dim3(ks), dim3(256), lds, s, a);
+    } else {
+        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_wgrad_kernel<64>), lds));
+        hipLaunchKernelGGL((rnn_wgrad_kernel<64>), dim3(ks), dim3(256), lds, s, a);
+    }
+    IC3_HIP(hipGetLastError());
+    const int n = H * H;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, scratch, ks, n, dA2, accumulate);
+    IC3_HIP(hipGetLastError());
+    return ks;
+}
+
+// one step of the chain (also the unit the tests drive): returns the number of partials written / added to
+extern "C" int ic3_rnn_tanh_backward_step(const float* dh_in, const float* h_t, const float* dhead, const float* w_heads, int OT,
+                                          const float* a2, const float* out_scale, float* dz, float* dh_out, float* dbias_partials,
+                                          int accumulate, long long R, int H, ic3_stream stream)
+{
+    using namespace ic3;
+    if (!h_t || !dhead || !w_heads || !a2 || !dz || !dh_out || !dbias_partials || R <= 0)
+        return fail(-22, "ic3_rnn_tanh_backward_step: null argument");
+    if (H != 64 && H != 128) return fail(-38, "ic3_rnn_tanh_backward_step: hid_size 64 / 128");
+    if (OT < 1 || OT > 16) return fail(-22, "ic3_rnn_tanh_backward_step: 1 <= OT <= 16");
+    if (R >= (1ll << 31)) return fail(-22, "ic3_rnn_tanh_backward_step: R < 2^31");
+    const int grid = ic3_rnn_backward_partials(R, H);
+    const RnnBwdArgs a{ dh_in, h_t, dhead, w_heads, a2, out_scale, dz, dh_out, dbias_partials, (int)R, OT, (int)((R + 63) / 64),
+                        accumulate };
+    const size_t lds = ((size_t)H * H + 64 * (H + 4) + 16 * H + 64 * 16) * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    if (H == 128) {
+        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_tanh_bwd_kernel<128>), lds));
+        hipLaunchKernelGGL((rnn_tanh_bwd_kernel<128>), dim3(grid), dim3(512), lds, s, a);
+    } else {
+        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_tanh_bwd_kernel<64>), lds));
+        hipLaunchKernelGGL((rnn_tanh_bwd_kernel<64>), dim3(grid), dim3(256), lds, s, a);
+    }
+    IC3_HIP(hipGetLastError());
+    return grid;
+}
+
+extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream)
+{
+    using namespace ic3;
+    if (!env || !b) return fail(-22, "ic3_rnn_backward: null argument");
+    if (b->struct_size != sizeof(ic3_rnn_bptt))
+        return fail(-22, "ic3_rnn_backward: ic3_rnn_bptt has " + std::to_string(b->struct_size) + " bytes, this library's has " +
+                             std::to_string(sizeof(ic3_rnn_bptt)) + " (header / library version mismatch)");
+    const int T = b->T, E = b->E, N = b->N, H = b->H;
+    if (T <= 0 || E <= 0 || N <= 0 || E != env->dims.E || N != env->dims.N)
+        return fail(-22, "ic3_rnn_backward: T, E, N must be positive and E, N the handle's");
+    if (!ic3_rnn_backward_supported(env, H)) return fail(-38, "ic3_rnn_backward: hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form");
+    if (b->OT < 1 || b->OT > 16) return fail(-22, "ic3_rnn_backward: 1 <= OT <= 16");
+    if (!b->hs || !b->dhead || !b->snaps || !b->a2 || !b->w_heads || !b->dh || !b->dz || !b->dbias_partials || !b->enc_work)
+        return fail(-22, "ic3_rnn_backward: null argument");
+    if (b->a2_grad && !b->wgrad_scratch) return fail(-22, "ic3_rnn_backward: a2_grad needs wgrad_scratch");
+    if (b->enc_window && ic3_env_encode_backward_window_work(env, H) <= 0)
+        return fail(-22, "ic3_rnn_backward: enc_window on a configuration without ic3_env_encode_backward_window");
+    const long long R = (long long)E * N;
+    int enc_first = b->enc_first;
+    for (int t = T - 1; t >= 0; --t) {
+        // trainer.py:56-60: h_t was handed on detached — the launch reads zeros for dL/dh_t (a null input, no memset)
+        const bool detached = b->detach_gap > 0 && (t + 1) % b->detach_gap == 0;
+        const float* h_t = (t + 1 < T || !b->h_last) ? b->hs + (size_t)(t + 1) * R * H : b->h_last;
+        float* dz = b->dz + (size_t)t * R * H;
+        int rc = ic3_rnn_tanh_backward_step(detached ? nullptr : b->dh, h_t, b->dhead + (size_t)t * R * b->OT, b->w_heads, b->OT, b->a2,
+                                            (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R : nullptr, dz, b->dh,
+                                            b->dbias_partials, 1, R, H, stream);
+        if (rc < 0) return rc;
+        if (b->enc_window) continue;                             // (the encoder's first stage: once, behind the loop)
+        rc = ic3_env_encode_backward_accumulate(env, b->snaps + (size_t)t * b->snap_words, dz, H, H, b->enc_work, enc_first, stream);
+        if (rc < 0) return rc;
+        enc_first = 0;
+    }
+    if (b->enc_window) {
+        const int rc = ic3_env_encode_backward_window(env, b->snaps, b->snap_words, T, b->dz, H, R * H, H, b->enc_work, enc_first, stream);
+        if (rc < 0) return rc;
+    }
+    if (b->a2_grad) {
+        const int rc = ic3_rnn_weight_grad(b->dz, b->hs, b->row_live, (long long)T * R, H, b->a2_grad, 1, b->wgrad_scratch, stream);
+        if (rc < 0) return rc;
+    }
+    return 0;
+}

@@ -421,6 +421,98 @@ def bptt_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lst
         gate_events.extend((evs[2 * t], evs[2 * t + 1], t) for t in range(T))
 
 
+def rnn_backward_supported(env, H):
+    """ic3_rnn_backward_supported: the tanh-recurrence baseline's window backward runs for this env handle at hid_size H."""
+    return bool(_lib.lib().ic3_rnn_backward_supported(env._h, int(H)))
+
+
+def rnn_backward_partials(R, H):
+    """Rows of ic3_rnn_bptt.dbias_partials (ic3_rnn_backward_partials)."""
+    return int(_lib.lib().ic3_rnn_backward_partials(int(R), int(H)))
+
+
+def rnn_tanh_backward_step(dh_in, h_t, dhead, w_heads, a2, dz, dh_out, dbias_partials, out_scale=None, accumulate=False):
+    """ic3_rnn_tanh_backward_step: one step of the tanh recurrence's chain — dz = (dh_in + dhead . w_heads) * (1 - h_t^2),
+    dh_out = (dz . a2) * out_scale, column sums of dz into dbias_partials (rnn_backward_partials(R, H) rows).  dh_in None: zeros;
+    dh_out may be dh_in."""
+    _need_cuda(h_t, "rnn_tanh_backward_step")
+    R, H = h_t.shape
+    OT = dhead.shape[-1]
+    for v in (h_t, dz, dh_out) + ((dh_in,) if dh_in is not None else ()):
+        assert v.is_contiguous() and tuple(v.shape) == (R, H) and v.dtype == torch.float32
+    assert dhead.is_contiguous() and tuple(dhead.shape) == (R, OT) and dhead.dtype == torch.float32
+    assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and a2.is_contiguous() and tuple(a2.shape) == (H, H)
+    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (rnn_backward_partials(R, H), H)
+    n = _lib.lib().ic3_rnn_tanh_backward_step(ptr(dh_in), ptr(h_t), ptr(dhead), ptr(w_heads), OT, ptr(a2), _rowvec(out_scale, R),
+                                              ptr(dz), ptr(dh_out), ptr(dbias_partials), int(bool(accumulate)), R, H, stream())
+    return check(n)
+
+
+def rnn_weight_grad(dz, h_prev, dA2, row_live=None, accumulate=True, work=None):
+    """ic3_rnn_weight_grad: dA2 (H, H) (+)= dz^T @ (row_live h_prev) over all Q rows of a window in one launch.  dz, h_prev (Q, H)
+    contiguous (leading dims may be (T, R)), row_live (Q,) or None."""
+    _need_cuda(dz, "rnn_weight_grad")
+    H = dz.shape[-1]
+    Q = dz.numel() // H
+    assert dz.is_contiguous() and dz.dtype == torch.float32 and h_prev.is_contiguous() and h_prev.numel() >= Q * H
+    assert h_prev.shape[-1] == H and h_prev.dtype == torch.float32
+    assert dA2.is_contiguous() and tuple(dA2.shape) == (H, H)
+    if row_live is not None:
+        assert row_live.is_contiguous() and row_live.dtype == torch.float32 and row_live.numel() == Q
+    n = int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(Q, H))
+    if n == 0:
+        raise NotImplementedError("rnn_weight_grad: hid_size 64 / 128")
+    work = work if work is not None else dict()
+    key = ('rnn_wgrad', str(dz.device))
+    if key not in work or work[key].numel() < n:
+        work[key] = torch.empty((n,), dtype=torch.float32, device=dz.device)
+    check(_lib.lib().ic3_rnn_weight_grad(ptr(dz), ptr(h_prev), ptr(row_live), Q, H, ptr(dA2), int(bool(accumulate)), ptr(work[key]),
+                                         stream()))
+
+
+def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_partials, h_last=None, detach_gap=0, row_live=None,
+                 row_keep=None, enc_first=True, enc_window=True, a2_grad=None, work=None):
+    """ic3_rnn_backward: the backward through a window of T recorded steps of the tanh-recurrence baseline as one host call (one
+    launch per step, the encoder's first stage over the dz ring — enc_window — or per step, and with a2_grad affine2's weight
+    gradient over the window).  hs (>= T, R, H) the states entering the steps (slot T, or h_last, the state leaving the last one),
+    dhead (T, R, OT), dz (T, R, H) the ring, dbias_partials (rnn_backward_partials(R, H), H) added to."""
+    import ctypes as C
+    _need_cuda(hs, "rnn_backward")
+    R = E * N
+    OT = dhead.shape[-1]
+    assert hs.is_contiguous() and hs.dtype == torch.float32 and tuple(hs.shape[1:]) == (R, H)
+    assert hs.shape[0] >= T + 1 or (hs.shape[0] >= T and h_last is not None)
+    assert h_last is None or (h_last.is_contiguous() and tuple(h_last.shape) == (R, H))
+    assert dhead.is_contiguous() and dhead.numel() == T * R * OT and dhead.dtype == torch.float32
+    assert snaps.is_contiguous() and snaps.dtype == torch.int32 and snaps.shape[0] >= T
+    assert dh.is_contiguous() and tuple(dh.shape) == (R, H) and dz.is_contiguous() and tuple(dz.shape) == (T, R, H)
+    assert a2.is_contiguous() and tuple(a2.shape) == (H, H) and w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H)
+    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (rnn_backward_partials(R, H), H)
+    for v in (row_live, row_keep):
+        assert v is None or (v.is_contiguous() and v.dtype == torch.float32 and tuple(v.shape) == (T, R))
+    b = _lib.RnnBptt()
+    b.struct_size = C.sizeof(b)
+    b.T, b.E, b.N, b.H, b.OT = T, E, N, H, OT
+    b.detach_gap, b.enc_first, b.enc_window = int(detach_gap), int(bool(enc_first)), int(bool(enc_window))
+    b.hs, b.dhead, b.snaps = hs.data_ptr(), dhead.data_ptr(), snaps.data_ptr()
+    b.h_last = h_last.data_ptr() if h_last is not None else None
+    b.snap_words = snaps.stride(0)
+    b.a2, b.w_heads = a2.data_ptr(), w_heads.data_ptr()
+    b.row_live = row_live.data_ptr() if row_live is not None else None
+    b.row_keep = row_keep.data_ptr() if row_keep is not None else None
+    b.dh, b.dz, b.dbias_partials = dh.data_ptr(), dz.data_ptr(), dbias_partials.data_ptr()
+    b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
+    if a2_grad is not None:
+        assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
+        work = work if work is not None else dict()
+        n = int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H))
+        key = ('rnn_wgrad', str(hs.device))
+        if key not in work or work[key].numel() < n:
+            work[key] = torch.empty((n,), dtype=torch.float32, device=hs.device)
+        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), work[key].data_ptr()
+    check(_lib.lib().ic3_rnn_backward(env._h, C.byref(b), stream()))
+
+
 HEADS_GRAD_MAX_OT = 16      # ic3_heads_grad: at most 16 output columns (the heads' actions in total + the value)
 
 

@@ -468,6 +468,61 @@ typedef struct ic3_bptt {
 int ic3_bptt_backward_supported(const ic3_env* env, int H);
 int ic3_bptt_first_chain_envs(int E, int N);
 int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream stream);
+
+/* The backward through a window of T recorded steps of the IC / IRIC baselines' tanh recurrence (models.py:68-92, rnn_type 'MLP':
+ * h_t = tanh(affine1(obs_t) + affine2(h_{t-1})), heads and value on h_t), last step first, as ONE host call — per step ONE launch:
+ *   dh_t = dh + d_t . W_heads;  dz_t = dh_t * (1 - h_t^2) -> dz slot t;  dh <- (dz_t . A2) * row_keep[t - 1];  column sums of dz_t
+ *   -> dbias_partials
+ * (A2 = affine2.weight, on the fp32 matrix instruction), then the encoder's first stage — once over the dz ring behind the loop
+ * (enc_window != 0: ic3_env_encode_backward_window, finish with ic3_env_encode_backward_window_finish) or per step
+ * (ic3_env_encode_backward_accumulate, finish with ic3_env_encode_backward_finish) — and, with a2_grad, ic3_rnn_weight_grad over
+ * the window.  Nothing runs on the host between the launches.  The caller adds the partials' sum to BOTH biases (affine1, affine2)
+ * and runs ic3_heads_grad.
+ *   hs [>= T (+1)][R][H]: slot t = h_{t-1}, the state entering step t; h_t of the last step is hs slot T, or h_last when not NULL;
+ *   dhead [T][R][OT] (OT <= 16);  snaps: T snapshots, snap_words int32 apart;  row_live / row_keep [T][R] or NULL (collection mode:
+ *   h_{t-1} rows of the weight gradient times row_live[t]; what crosses from step t back to t - 1 times row_keep[t - 1]);
+ *   detach_gap > 0: the gradient arriving at step t is dropped when (t + 1) % detach_gap == 0 (trainer.py:56-60, lock-step);
+ *   dh [R][H] in: dL/dh arriving at the window's last step, out: leaving its first;  dz [T][R][H] the ring (written);
+ *   dbias_partials [ic3_rnn_backward_partials(R, H)][H] ADDED to (zero them first);  enc_work as the encoder form asks, enc_first
+ *   != 0: this window starts the accumulation;  a2_grad [H][H] ADDED to (or NULL: no weight gradient here), wgrad_scratch
+ *   ic3_rnn_weight_grad_scratch_floats(T * R, H) floats.
+ * No float atomics: dz, dh, the partials and a2_grad are identical run to run.  hid_size 64 / 128.
+ * ic3_rnn_backward_supported(env, H): 1 when every step can run (hid_size 64 / 128, the encoder backward in its partial-sums form).
+ * ic3_rnn_tanh_backward_step: one step of the chain on its own (dh_in NULL: zeros; dh_out may be dh_in; out_scale [R] or NULL);
+ * returns the number of partials written (accumulate == 0) or added to. */
+typedef struct ic3_rnn_bptt {
+    uint32_t struct_size;   /* sizeof(ic3_rnn_bptt) of the caller's header (checked first: -EINVAL on mismatch) */
+    int32_t T, E, N, H, OT;
+    int32_t detach_gap, enc_first, enc_window;
+    const float* hs;
+    const float* h_last;
+    const float* dhead;
+    const int32_t* snaps;
+    int64_t snap_words;
+    const float* a2;
+    const float* w_heads;
+    const float* row_live;
+    const float* row_keep;
+    float* dh;
+    float* dz;
+    float* dbias_partials;
+    float* enc_work;
+    float* a2_grad;
+    float* wgrad_scratch;
+} ic3_rnn_bptt;
+int ic3_rnn_backward_supported(const ic3_env* env, int H);
+int ic3_rnn_backward_partials(long long R, int H);
+int ic3_rnn_tanh_backward_step(const float* dh_in /* or NULL */, const float* h_t, const float* dhead, const float* w_heads, int OT,
+                               const float* a2, const float* out_scale /* or NULL */, float* dz, float* dh_out, float* dbias_partials,
+                               int accumulate, long long R, int H, ic3_stream stream);
+int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream);
+/* affine2's weight gradient over a whole window in one launch (+ a fixed-order reduction): dA2 [H][H] (+)= dz^T . (row_live h_prev)
+ * over Q = steps x rows pairs — dz [Q][H] (ic3_rnn_backward's ring), h_prev [Q][H] (slots 0..T-1 of the recorded states), row_live
+ * [Q] or NULL.  Exact fp32 products on the fp32 matrix instruction, split-K over the CUs, slices summed in order (reproducible).
+ * scratch: ic3_rnn_weight_grad_scratch_floats(Q, H) floats.  hid_size 64 / 128. */
+size_t ic3_rnn_weight_grad_scratch_floats(long long Q, int H);
+int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const float* row_live /* or NULL */, long long Q, int H, float* dA2,
+                        int accumulate, float* scratch, ic3_stream stream);
 /* The weight / bias gradient of the heads + value head over a whole episode in one pass (trainer.py:128-225 through
  * comm.py:228,239): dW [OT][H] += sum_m d[m][o] h[m][c], db [OT] += sum_m d[m][o] over the M = steps x rows pairs
  * (d [M][OT], h [M][H]: h_t of every step, i.e. the recorded hidden states shifted by one step).  scratch:
