@@ -19,6 +19,8 @@ pointwise or sparse is a HIP kernel of libic3rollout.
 Cost per step (PP-hard): forward 0.30 GFLOP-equivalents of one gate GEMM, backward = recompute (1x) + input gradient (1x)
 + weight gradient (1x): fp32 arithmetic bounds the update at ~4x the rollout's matrix work.
 """
+import contextlib
+
 import torch
 
 from . import ops
@@ -121,6 +123,14 @@ class EpisodeRecord(object):
 
     def slot(self, t):
         return (self.hs[t], self.cs[t])
+
+    def h_out(self, t):
+        """h LEAVING step t: the state entering step t + 1, or what the rollout ended with"""
+        return self.hs[t + 1] if t + 1 < self.n else self.h_last
+
+    def h_last_is_slot(self, T):
+        """h_last IS slot T of the record (the in-place rollout wrote it there): h leaving the steps is hs[1:T + 1] then"""
+        return self.h_last is not None and self.hs.shape[0] > T and self.h_last.data_ptr() == self.hs[T].data_ptr()
 
     def record(self, t, net, raw, prev_hid, info):
         if self.recurrent:
@@ -265,12 +275,10 @@ def backward_episode(args, net, raw, rec, d_out, acc, carry=None):
     """Backward through one recorded episode; parameter gradients are ADDED into `acc` (fp32 tensors keyed like the
     fused weight cache).
 
-    Collection mode (`rec.stream`, Trainer._run_batch_streams: the record is a WINDOW of consecutive slots of E streams of
-    episodes; every policy family — the non-recurrent ones have no state to cut, only the masks of a starting env): `fresh[t]` marks the envs that start an episode at slot t — their
-    rows of (h, c) entering the slot are zero, nobody is dead and the gate is 0 (trainer.py:38-51, quirks Q21 / Q22), as
-    the step launch had it — and `keep[t]` the envs whose state leaving slot t reaches slot t + 1 with its gradient (no
-    episode end, not a detach point of the env's own step count: trainer.py:56-60); `carry` = (dL/dh, dL/dc) arriving at
-    the window's last slot from the next window, and the pair leaving the window's first slot is returned."""
+    The recurrence is cut where `_Cuts` says — detach points, and in collection mode (`rec.stream`, every policy family: the
+    non-recurrent ones have no state to cut, only the masks of a starting env) the starting envs and episode ends inside the
+    window; there `carry` = (dL/dh, dL/dc) arriving at the window's last slot from the next window, and the pair leaving the
+    window's first slot is returned."""
     if _is_baseline(net):
         si = standin_for_backward(args, net, rec)
         if si is not None:
@@ -314,58 +322,25 @@ def backward_episode(args, net, raw, rec, d_out, acc, carry=None):
         bias_parts = torch.zeros(((R + 63) // 64, 4 * H), dtype=torch.float32, device=dev)
     else:
         gates, bias_parts, bsum = z(R, 4 * H), z(ops.LSTM_BWD_MAX_PARTIALS, 4 * H), z(4 * H)
-    # the weight gradient dgates^T . [inp | h] has K = R: as NB products over row blocks (batched, then summed) the
-    # library fills the chip (tools/exp/microbench_bptt_gemms.py: 118 instead of 83 TFLOP/s at R = 81920)
-    NB = 8 if R % 8 == 0 and R >= 8192 else 1
-    wpart = torch.zeros((NB, 2 * H, 4 * H), dtype=torch.float32, device=dev) if NB > 1 else None
-    # C.weight's gradient d inp^T . comm has an H x H result over K = R: a single product is 24 workgroups of split-K; as
-    # NBC products over row blocks, summed behind the loop, it fills the chip too
-    NBC = 32 if R % 32 == 0 and R >= 8192 and not mask_zero else 1
-    cpart = torch.zeros((NBC, H, H), dtype=torch.float32, device=dev) if NBC > 1 else None
+    wgrad = _RowBlockGrad(acc['w_cat_t'], R, 8)                           # xh^T . dgates
+    cgrad = None if mask_zero else _RowBlockGrad(acc['c_w'], R, 32)       # d inp^T . comm
     dh_rec = torch.zeros((R, H), dtype=torch.float32, device=dev)         # dL/dh_t, dL/dc_t arriving from step t + 1
     dc_rec = torch.zeros((R, H), dtype=torch.float32, device=dev)
-    gap = int(getattr(args, 'detach_gap', 10000))
-    enc_acc = None        # None: no state accumulated yet; True: partial sums hold the steps so far; False: per-step form
-    stream = rec.stream
-    if stream is not None:
-        if carry is not None:
-            dh_rec.copy_(carry[0])
-            dc_rec.copy_(carry[1])
-        _heads_grad_episode(rec, d_out, acc, T, R, H)                     # (reads h_t of every slot: before rows are zeroed)
-        fresh_rows = stream['fresh'].to(torch.float32).repeat_interleave(N, dim=1)     # (T, R)
-        keep_rows = stream['keep'].to(torch.float32).repeat_interleave(N, dim=1).unsqueeze(2)   # (T, R, 1)
-        ones_mask = torch.ones((E, N), dtype=torch.int32, device=dev)
-        zeros_mask = torch.zeros((E, N), dtype=torch.int32, device=dev)
+    enc_grad = _EncoderGrad(raw, acc, 'wt', 'enc_bias')
+    cuts = _Cuts(args, rec, T, E, N, dev)
     # collection mode on recorded gates: the per-row cuts ride inside the launches that touch the rows anyway
-    # (ic3_lstm_gates_backward_given: row_live, row_keep; ic3_comm_masked_mean_add: out_row_scale) — no passes of their own
-    cut_in_kernel = stream is not None and given
-    if cut_in_kernel:
-        keep_flat = keep_rows.squeeze(2).contiguous()                     # (T, R)
-        live_flat = (1.0 - fresh_rows).contiguous()
-        dh_rec.mul_(keep_rows[T - 1])                                     # what the next window handed over, cut at its border
+    # (ic3_lstm_gates_backward_given: row_live, row_keep; ic3_comm_masked_mean_add: out_row_scale) — no passes of their own;
+    # the state that entered a starting env stays in the record (the launch multiplies it by row_live)
+    cut_in_kernel = cuts.on and given
+    cuts.carry_in(carry, dh_rec, dc_rec, at_border=cut_in_kernel)
+    if cuts.on:
+        _heads_grad_episode(rec, d_out, acc, T, R, H)                     # (reads h_t of every slot: before rows are zeroed)
     for t in reversed(range(T)):
-        if cut_in_kernel:
-            pass
-        elif stream is not None:
-            dh_rec.mul_(keep_rows[t])                                     # the cuts of the env's OWN episode / detach points
-            dc_rec.mul_(keep_rows[t])
-        elif (t + 1) % gap == 0:                                          # trainer.py:56-60: (h_t, c_t) handed on detached
-            dh_rec.zero_()
-            dc_rec.zero_()
         h_prev, c_prev = rec.hs[t], rec.cs[t]
-        h_t = rec.hs[t + 1] if t + 1 < T else rec.h_last
-        alive, gate = rec.alive[t], rec.gate[t]
-        if stream is not None:
-            fr = stream['fresh'][t].unsqueeze(1)                          # (E, 1) the env starts an episode at this slot
-            alive = torch.where(fr, ones_mask, alive) if alive is not None else None
-            if cut_in_kernel:
-                # (the state that entered stays in the record; the launch multiplies it by row_live, and the communication
-                #  block must not see it either: the env's agents are gated off — what zero hidden states amount to)
-                gate = torch.where(fr, zeros_mask, gate if gate is not None else ones_mask)
-            else:
-                h_prev.mul_((1.0 - fresh_rows[t]).unsqueeze(1))           # in place: the record is not read again
-                c_prev.mul_((1.0 - fresh_rows[t]).unsqueeze(1))
-                gate = torch.where(fr, zeros_mask, gate) if gate is not None else None
+        if not cut_in_kernel:
+            cuts.cut(t, dh_rec, dc_rec)
+            cuts.entering(t, h_prev, c_prev)
+        alive, gate = cuts.masks(t, rec.alive[t], rec.gate[t], fill_gate=cut_in_kernel)
         # ---- the forward of step t again: enc + C.bias -> inp, comm, gate pre-activations (comm.py:119,181-215)
         if given:                                                         # inp as the step launch stored it; comm for C's gradient
             xh = rec.xh[t]
@@ -390,60 +365,43 @@ def backward_episode(args, net, raw, rec, d_out, acc, carry=None):
         if given:                                                         # dc_rec <- dL/dc_{t-1}
             ops.lstm_gates_backward_given(rec.gates[t], c_prev, dh, dc_rec, dgates, dc_rec, bias_parts, True, xh=xh, h_prev=h_prev,
                                           lstm_wp3_bwd=fc['ps_l_wp3_bwd'], dxh=dxh,
-                                          row_live=live_flat[t] if cut_in_kernel else None,
-                                          row_keep=keep_flat[t] if cut_in_kernel else None)
+                                          row_live=cuts.live_flat[t] if cut_in_kernel else None,
+                                          row_keep=cuts.keep_flat[t] if cut_in_kernel else None)
         elif fused_gates:
             # (the heads' own weight gradient is one pass over the whole episode behind the loop: ic3_heads_grad)
             ops.lstm_gates_backward(xh, fc['ps_l_wp'], fc['b_cat'], c_prev, dh, dc_rec, dgates, dc_rec, bias_parts, True,
                                     h_prev=h_prev, lstm_wp3=fc.get('ps_l_wp3'), lstm_wp3_bwd=fc.get('ps_l_wp3_bwd') if fused_dx else None,
                                     dxh=dxh if fused_dx else None)
         else:
-            if stream is None:
-                acc['w_heads'].addmm_(d.t(), h_t)
+            if not cuts.on:
+                acc['w_heads'].addmm_(d.t(), rec.h_out(t))
                 acc['b_heads'].add_(d.sum(0))
             parts = ops.lstm_cell_backward(gates, c_prev, dh, dc_rec, dgates, dc_rec, bias_parts)
             torch.sum(parts, 0, out=bsum)
             acc['b_cat'].add_(bsum)
         # ---- [W_ih | W_hh] (torch.nn.LSTMCell): weight gradient and input gradient, one product each
-        if NB > 1:                            # wpart_b (2H, 4H) += xh_b^T . dgates_b; the NB partials are summed behind the loop
-            wpart.baddbmm_(xh.view(NB, R // NB, 2 * H).transpose(1, 2), dgates.view(NB, R // NB, 4 * H))
-        else:
-            acc['w_cat_t'].addmm_(xh.t(), dgates)                         # (2H, R) x (R, 4H)
+        wgrad.add(xh, dgates)                                             # (2H, R) x (R, 4H)
         if not fused_dx:
             torch.mm(dgates, w_cat_t.t(), out=dxh)                        # (R, 4H) x (4H, 2H) -> [d inp | d h_{t-1}]
         # ---- inp = encoder(obs) + C(comm) (+ both biases)
         if not mask_zero:
-            if NBC > 1:
-                cpart.baddbmm_(dinp.view(NBC, R // NBC, H).transpose(1, 2), comm.view(NBC, R // NBC, H))
-            else:
-                acc['c_w'].addmm_(dinp.t(), comm.view(R, H))
+            cgrad.add(dinp, comm.view(R, H))
             torch.mm(dinp, fc['c_wt'].t(), out=dcomm)                     # d comm = d inp . C.weight
             # dL/dh_{t-1} (what step t - 1 receives) = d h of the gate product + the communication block's share, one pass
             ops.comm_masked_mean_raw(dcomm.view(E, N, H), alive, gate, mode_avg, True, out=dh_rec.view(E, N, H), addend=dxh[:, H:],
-                                     row_scale=keep_flat[t - 1] if cut_in_kernel and t > 0 else None)
+                                     row_scale=cuts.keep_flat[t - 1] if cut_in_kernel and t > 0 else None)
         elif cut_in_kernel and t > 0:
-            torch.mul(dxh[:, H:], keep_rows[t - 1], out=dh_rec)
+            torch.mul(dxh[:, H:], cuts.keep_rows[t - 1], out=dh_rec)
         else:
             dh_rec.copy_(dxh[:, H:])
-        # encoder: the first stage per step adds to partial sums, the expansion into (obs_dim, H) runs once behind the loop
-        if enc_acc is not False:
-            enc_acc = raw.encode_backward_accumulate(dinp, rec.snaps[t], first=(enc_acc is None)) \
-                if hasattr(raw, 'encode_backward_accumulate') else False
-        if enc_acc is False:
-            dwt, db = raw.encode_backward(dinp, rec.snaps[t], want_bias=True)    # db = sum of the d inp rows: both biases
-            acc['wt'].add_(dwt)
-            acc['enc_bias'].add_(db)
-    if enc_acc:
-        dwt, db = raw.encode_backward_finish(H, want_bias=True)
-        acc['wt'].add_(dwt)
-        acc['enc_bias'].add_(db)
-    if NB > 1:
-        acc['w_cat_t'].add_(wpart.sum(0))
-    if NBC > 1:
-        acc['c_w'].add_(cpart.sum(0))
+        enc_grad.step(dinp, rec.snaps[t])
+    enc_grad.finish(H)
+    wgrad.finish()
+    if cgrad is not None:
+        cgrad.finish()
     if fused_gates:
         acc['b_cat'].add_(bias_parts.sum(0))
-        if stream is None:
+        if not cuts.on:
             _heads_grad_episode(rec, d_out, acc, T, R, H)
     return (dh_rec, dc_rec)       # dL/d(h, c) entering the record's first slot (collection mode: the previous window's carry)
 
@@ -476,62 +434,29 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
     # two chains of launches (envs [0, E1) and [E1, E) on two streams): one fills the ragged last round of the other's launches
     two = ring and bool(getattr(args, 'bptt_two_chains', True)) and ops.first_chain_envs(E, N) < E
     dcw_parts = None if mask_zero else zeros(ops.bptt_dcw_partials(E, N, two), H, H)
-    alive, gate = list(rec.alive[:T]), list(rec.gate[:T])
-    live_flat = keep_flat = None
-    stream = rec.stream
-    gap = int(getattr(args, 'detach_gap', 10000))
-    if stream is not None:
-        if carry is not None:
-            dh_rec.copy_(carry[0])
-            dc_rec.copy_(carry[1])
-        fresh, keep = stream['fresh'], stream['keep']                     # (T, E) bool
-        live_flat = (~fresh).to(torch.float32).repeat_interleave(N, dim=1).contiguous()
-        keep_flat = keep.to(torch.float32).repeat_interleave(N, dim=1).contiguous()
-        ones = torch.ones((E, N), dtype=torch.int32, device=dev)
-        fr = fresh.unsqueeze(2)
-        if any(m is not None for m in alive):                             # an env that starts an episode: nobody is dead (Q21)
-            al = torch.where(fr, ones, torch.stack([m if m is not None else ones for m in alive]))
-            alive = list(al.unbind(0))
-        # ... and its agents are gated off: what the zero state entering the slot amounts to for the communication block (Q22)
-        gt = torch.where(fr, torch.zeros_like(ones), torch.stack([m if m is not None else ones for m in gate]))
-        gate = list(gt.unbind(0))
-        dh_rec.mul_(keep_flat[T - 1].unsqueeze(1))                        # what the next window handed over, cut at its border
-        gap = 0                                                           # (the env's OWN detach points are in `keep`)
-    elif gap > T:
-        gap = 0
+    cuts = _Cuts(args, rec, T, E, N, dev)
+    cuts.carry_in(carry, dh_rec, dc_rec, at_border=True)
+    alive, gate = cuts.masks_window(rec.alive[:T], rec.gate[:T])
     dhead = d_out if d_out.is_contiguous() else d_out.contiguous()
-    # the heads' weight gradient reads only d_out and the recorded h: it runs on a second stream BESIDE the chain (no LDS, a few
-    # waves per CU: it fits next to the chain's workgroups and rides their idle issue slots instead of taking 0.7 ms of its own)
-    side = None
-    if dev.type == 'cuda' and bool(getattr(args, 'heads_grad_beside', True)) and not torch.cuda.is_current_stream_capturing():
-        main = torch.cuda.current_stream(dev)
-        side = _SIDE_STREAMS.get(dev.index)
-        if side is None:
-            side = _SIDE_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            _heads_grad_episode(rec, d_out, acc, T, R, H)
-    ops.bptt_backward(raw, T, E, N, H, rec.gates, rec.hs, rec.cs, dhead, rec.snaps, alive, gate, fc['ps_l_wp3_bwd'], fc['w_heads'],
-                      None if mask_zero else net.C_modules[0].weight.detach(), dh_rec, dc_rec, dxh, bias_parts, dcw_parts,
-                      mode_avg=mode_avg, comm_zero=mask_zero, detach_gap=gap, row_live=live_flat, row_keep=keep_flat, enc_first=True,
-                      gate_events=getattr(raw, 'gate_timer', None),     # (bench.py --mode train: HIP events around the gate launches)
-                      two_chains=two)
-    if H == 256:
-        _weight_grad_products(rec, T, R, H, acc['w_cat_t'], live_flat)
-    else:
-        work = acc.setdefault('_work', {})
-        ops.lstm_weight_grad(rec.xh[:T], rec.hs[:T], rec.gates[:T], acc['w_cat_t'], row_live=live_flat, accumulate=True, work=work,
-                             split=bool(getattr(args, 'gate_split', True)))
-    dwt, db = raw.encode_backward_window_finish(H, want_bias=True) if ring else raw.encode_backward_finish(H, want_bias=True)
-    acc['wt'].add_(dwt)
-    acc['enc_bias'].add_(db)
-    acc['b_cat'].add_(bias_parts.sum(0))
-    if not mask_zero:
-        acc['c_w'].add_(dcw_parts.sum(0))
-    if side is not None:
-        torch.cuda.current_stream(dev).wait_stream(side)
-    else:
-        _heads_grad_episode(rec, d_out, acc, T, R, H)
+    with _heads_grad_beside(args, rec, d_out, acc, T, R, H):
+        ops.bptt_backward(raw, T, E, N, H, rec.gates, rec.hs, rec.cs, dhead, rec.snaps, alive, gate, fc['ps_l_wp3_bwd'], fc['w_heads'],
+                          None if mask_zero else net.C_modules[0].weight.detach(), dh_rec, dc_rec, dxh, bias_parts, dcw_parts,
+                          mode_avg=mode_avg, comm_zero=mask_zero, detach_gap=cuts.gap, row_live=cuts.live_flat,
+                          row_keep=cuts.keep_flat, enc_first=True,
+                          gate_events=getattr(raw, 'gate_timer', None),     # (bench.py --mode train: HIP events around the gate launches)
+                          two_chains=two)
+        if H == 256:
+            _weight_grad_products(rec, T, R, H, acc['w_cat_t'], cuts.live_flat)
+        else:
+            work = acc.setdefault('_work', {})
+            ops.lstm_weight_grad(rec.xh[:T], rec.hs[:T], rec.gates[:T], acc['w_cat_t'], row_live=cuts.live_flat, accumulate=True,
+                                 work=work, split=bool(getattr(args, 'gate_split', True)))
+        dwt, db = raw.encode_backward_window_finish(H, want_bias=True) if ring else raw.encode_backward_finish(H, want_bias=True)
+        acc['wt'].add_(dwt)
+        acc['enc_bias'].add_(db)
+        acc['b_cat'].add_(bias_parts.sum(0))
+        if not mask_zero:
+            acc['c_w'].add_(dcw_parts.sum(0))
     return (dh_rec, dc_rec)
 
 
@@ -550,38 +475,109 @@ def _weight_grad_products(rec, T, R, H, dW, row_live):
 _SIDE_STREAMS = {}     # per device: the stream the heads' gradient runs on beside the backward's chain
 
 
-def _ring_fits(dev, nbytes):
-    """Room for the ring of per-step input gradients: a quarter of what the device has free (+ what the caching allocator holds)."""
-    if dev.type != 'cuda':
-        return True
+@contextlib.contextmanager
+def _heads_grad_beside(args, rec, d_out, acc, T, R, H):
+    """The heads' weight gradient of a window backward.  It reads only d_out and the recorded h, so it runs on a second stream
+    BESIDE the chain issued in the `with` body (no LDS, a few waves per CU: it fits next to the chain's workgroups and rides their
+    idle issue slots instead of taking 0.7 ms of its own).  The current stream waits for it on the way out WHETHER OR NOT the body
+    raised: the caller releases the record then, and the side stream must be done reading hs / d_out and writing acc['w_heads'].
+    Without a second stream (CPU, args.heads_grad_beside off, a graph capture) the pass runs behind the body, if that succeeded."""
+    dev = rec.hs.device
+    side = None
+    try:
+        if dev.type == 'cuda' and bool(getattr(args, 'heads_grad_beside', True)) and not torch.cuda.is_current_stream_capturing():
+            side = _SIDE_STREAMS.get(dev.index)
+            if side is None:
+                side = _SIDE_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                _heads_grad_episode(rec, d_out, acc, T, R, H)
+        yield
+    finally:
+        if side is not None:
+            torch.cuda.current_stream(dev).wait_stream(side)
+    if side is None:
+        _heads_grad_episode(rec, d_out, acc, T, R, H)
+
+
+def device_room(dev):
+    """Bytes the device can still give: what it has free + the blocks the caching allocator holds unused."""
     free, _ = torch.cuda.mem_get_info(dev)
-    cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-    return nbytes <= (free + cached) // 4
+    return free + max(torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev), 0)
+
+
+def _ring_fits(dev, nbytes):
+    """Room for the ring of per-step input gradients: a quarter of what the device can still give."""
+    return dev.type != 'cuda' or nbytes <= device_room(dev) // 4
 
 
 class _Cuts(object):
-    """Collection mode (rec.stream) for the per-step Python loops: the masks of an env that STARTS an episode at slot t (nobody
-    is dead, the gate is 0: trainer.py:38-51, quirks Q21 / Q22), the rows of its entering state (zero), and what of the
-    gradient of the recurrent state crosses from slot t + 1 back to slot t (`keep`: no episode end, no detach point of the env's
-    own step counter)."""
+    """Where the recurrence of a record of T steps is cut, for every backward driver.
+    Lock-step: the gradient of the state leaving step t is dropped where the Trainer hands the state on detached, (t + 1) %
+    detach_gap == 0 (trainer.py:56-60).
+    Collection mode (rec.stream, Trainer._run_batch_streams: the record is a WINDOW of consecutive slots of E streams of
+    episodes): an env that STARTS an episode at slot t has nobody dead, its agents gated off and a zero state entering
+    (trainer.py:38-51, quirks Q21 / Q22), as the step launch had it; `keep[t]` marks the envs whose state leaving slot t reaches
+    slot t + 1 with its gradient (no episode end, no detach point of the env's OWN step counter).
+    `live_flat` / `keep_flat`: the (T, R) row factors the kernels take (None in lock-step); `gap`: the detach_gap left for the
+    host calls and `cut` to apply — 0 where the cuts ride in `keep` or none falls inside the record."""
 
-    def __init__(self, rec, E, N, dev):
+    def __init__(self, args, rec, T, E, N, dev):
         st = rec.stream
         self.on = st is not None
+        gap = int(getattr(args, 'detach_gap', 10000))
+        self.gap = 0 if self.on or gap > T else gap
+        self.live_flat = self.keep_flat = None
         if not self.on:
             return
-        self.fresh = st['fresh']
-        self.live_rows = (~st['fresh']).to(torch.float32).repeat_interleave(N, dim=1).unsqueeze(2)   # (T, R, 1)
-        self.keep_rows = st['keep'].to(torch.float32).repeat_interleave(N, dim=1).unsqueeze(2)
-        self.ones = torch.ones((E, N), dtype=torch.int32, device=dev)
-        self.zeros = torch.zeros((E, N), dtype=torch.int32, device=dev)
+        self.T, self.shape, self.dev, self._consts = T, (E, N), dev, None
+        self.fresh = st['fresh'][:T]                                                     # (T, E) bool
+        self.live_flat = (~self.fresh).to(torch.float32).repeat_interleave(N, dim=1).contiguous()
+        self.keep_flat = st['keep'][:T].to(torch.float32).repeat_interleave(N, dim=1).contiguous()
+        self.live_rows, self.keep_rows = self.live_flat.unsqueeze(2), self.keep_flat.unsqueeze(2)   # (T, R, 1)
 
-    def masks(self, t, alive, gate):
+    def _ones_zeros(self):
+        if self._consts is None:
+            ones = torch.ones(self.shape, dtype=torch.int32, device=self.dev)
+            self._consts = (ones, torch.zeros_like(ones))
+        return self._consts
+
+    def carry_in(self, carry, dh, dc=None, at_border=False):
+        """Collection mode: (dL/dh, dL/dc) arriving at the window's last slot from the next window; `at_border`: cut where it
+        crosses into the window (the drivers whose kernels apply keep[t - 1] on the way OUT of slot t — the loops cut per step)."""
+        if not self.on:
+            return
+        if carry is not None:
+            dh.copy_(carry[0])
+            if dc is not None:
+                dc.copy_(carry[1])
+        if at_border:
+            dh.mul_(self.keep_rows[self.T - 1])
+
+    def masks(self, t, alive, gate, fill_gate=False):
+        """The step's masks with the starting envs' rows set: nobody is dead (Q21), the agents are gated off — what the zero state
+        entering the slot amounts to for the communication block (Q22).  `fill_gate`: a missing gate counts as all ones first
+        (the entering state stays in the record there, so gating off is what hides it)."""
         if not self.on:
             return alive, gate
+        ones, zeros = self._ones_zeros()
         fr = self.fresh[t].unsqueeze(1)
-        return (torch.where(fr, self.ones, alive) if alive is not None else None,
-                torch.where(fr, self.zeros, gate) if gate is not None else None)
+        if gate is None and fill_gate:
+            gate = ones
+        return (torch.where(fr, ones, alive) if alive is not None else None,
+                torch.where(fr, zeros, gate) if gate is not None else None)
+
+    def masks_window(self, alive, gate):
+        """`masks` (fill_gate) for all T steps at once — one `where` per mask over (T, E, N); returns the two lists of T"""
+        alive, gate = list(alive), list(gate)
+        if not self.on:
+            return alive, gate
+        ones, zeros = self._ones_zeros()
+        fr = self.fresh.unsqueeze(2)
+        if any(m is not None for m in alive):
+            alive = list(torch.where(fr, ones, torch.stack([m if m is not None else ones for m in alive])).unbind(0))
+        gate = list(torch.where(fr, zeros, torch.stack([m if m is not None else ones for m in gate])).unbind(0))
+        return alive, gate
 
     def entering(self, t, h, c=None):
         """(h, c) entering slot t with the rows of starting envs zeroed (in place: the record is not read again)"""
@@ -591,14 +587,72 @@ class _Cuts(object):
                 c.mul_(self.live_rows[t])
         return h, c
 
-    def cut(self, t, gap, *grads):
+    def cut(self, t, *grads):
         """the gradient of the state LEAVING slot t: lock-step — zero at the episode's detach points; collection — times keep"""
         if self.on:
             for g in grads:
                 g.mul_(self.keep_rows[t])
-        elif (t + 1) % gap == 0:
+        elif self.gap and (t + 1) % self.gap == 0:
             for g in grads:
                 g.zero_()
+
+    def h_out(self, rec):
+        """h leaving every step of the record, for the heads' gradient inside a loop — copies in collection mode, taken before
+        `entering` zeroes rows of the record"""
+        return [rec.h_out(t).clone() if self.on else rec.h_out(t) for t in range(rec.n)]
+
+
+class _EncoderGrad(object):
+    """The sparse encoder's weight gradient over the steps of a loop, added to acc[wkey] / acc[bkey]: the first stage per step
+    into partial sums and the expansion into (obs_dim, H) once behind the loop (encode_backward_accumulate / _finish), or
+    — where the env has no such form or declines — the whole gradient per step."""
+
+    def __init__(self, raw, acc, wkey, bkey):
+        self.raw, self.acc, self.keys = raw, acc, (wkey, bkey)
+        self.partial = None       # None: nothing accumulated yet; True: partial sums hold the steps so far; False: per-step form
+
+    def _add(self, dwt, db):      # (db = the sum of the rows of d: every bias that adds to the encoder's output sees it)
+        self.acc[self.keys[0]].add_(dwt)
+        self.acc[self.keys[1]].add_(db)
+
+    def step(self, d, snap):
+        if self.partial is not False:
+            self.partial = self.raw.encode_backward_accumulate(d, snap, first=(self.partial is None)) \
+                if hasattr(self.raw, 'encode_backward_accumulate') else False
+        if self.partial is False:
+            self._add(*self.raw.encode_backward(d, snap, want_bias=True))
+
+    def finish(self, H):
+        if self.partial:
+            self._add(*self.raw.encode_backward_finish(H, want_bias=True))
+
+
+class _RowBlockGrad(object):
+    """dst += a^T . b summed over the steps of a loop, a (R, m) and b (R, n) — a weight gradient with K = R.  As `nb` batched
+    products over row blocks, summed once behind the loop, the library fills the chip (a single (H, H) result is 24 workgroups of
+    split-K; the (2H, 4H) one: 118 instead of 83 TFLOP/s at R = 81920, tools/exp/microbench_bptt_gemms.py); the plain product
+    where R is small or does not divide."""
+
+    def __init__(self, dst, R, nb):
+        self.dst, self.R = dst, R
+        self.nb = nb if R % nb == 0 and R >= 8192 else 1
+        self.part = torch.zeros((self.nb,) + tuple(dst.shape), dtype=torch.float32, device=dst.device) if self.nb > 1 else None
+
+    def add(self, a, b):
+        if self.part is None:
+            self.dst.addmm_(a.t(), b)
+        else:
+            rows = self.R // self.nb
+            self.part.baddbmm_(a.view(self.nb, rows, a.shape[1]).transpose(1, 2), b.view(self.nb, rows, b.shape[1]))
+
+    def finish(self):
+        if self.part is not None:
+            self.dst.add_(self.part.sum(0))
+
+
+def _baseline_w_heads(net):
+    """(OT, H): the action heads' weights over the value head's, the column order of d_out"""
+    return torch.cat([hd.weight for hd in net.heads] + [net.value_head.weight], 0).detach().contiguous()
 
 
 def _heads_grad_episode(rec, d_out, acc, T, R, H):
@@ -611,7 +665,7 @@ def _heads_grad_episode(rec, d_out, acc, T, R, H):
         else:                                                             # (more than 15 actions in total)
             acc['w_heads'].addmm_(d.t(), h)
             acc['b_heads'].add_(d.sum(0))
-    if rec.h_last is not None and rec.h_last.data_ptr() == rec.hs[T].data_ptr():
+    if rec.h_last_is_slot(T):
         grad(d_out[:T].reshape(T * R, -1), rec.hs[1:T + 1].reshape(T * R, H))
     else:
         if T > 1:
@@ -645,16 +699,11 @@ def _backward_episode_multipass(args, net, raw, rec, d_out, acc, carry=None):
     dinp = dxh[:, :H]
     dh_rec = torch.zeros((R, H), dtype=torch.float32, device=dev)
     dc_rec = torch.zeros((R, H), dtype=torch.float32, device=dev)
-    gap = int(getattr(args, 'detach_gap', 10000))
-    cuts = _Cuts(rec, E, N, dev)
-    if cuts.on and carry is not None:
-        dh_rec.copy_(carry[0])
-        dc_rec.copy_(carry[1])
-    if cuts.on:                                                   # (reads h_t of every slot: before the starting envs' rows are zeroed)
-        heads_first = [(rec.hs[t + 1] if t + 1 < T else rec.h_last).clone() for t in range(T)]
+    cuts = _Cuts(args, rec, T, E, N, dev)
+    cuts.carry_in(carry, dh_rec, dc_rec)
+    h_out = cuts.h_out(rec)
     for t in reversed(range(T)):
-        cuts.cut(t, gap, dh_rec, dc_rec)
-        h_t = heads_first[t] if cuts.on else (rec.hs[t + 1] if t + 1 < T else rec.h_last)
+        cuts.cut(t, dh_rec, dc_rec)
         alive, gate = cuts.masks(t, rec.alive[t], rec.gate[t])
         # ---- forward: enc (+ encoder.bias + C_0.bias), then the passes
         raw.encode_at(rec.snaps[t], fc['wt'], fc['enc_bias'], out=enc, loc_table=fc['loc_table'])
@@ -676,7 +725,7 @@ def _backward_episode_multipass(args, net, raw, rec, d_out, acc, carry=None):
         # ---- backward: heads on the last pass's h, then the passes in reverse
         d = d_out[t]
         torch.addmm(dh_rec, d, fc['w_heads'], out=dh)
-        acc['w_heads'].addmm_(d.t(), h_t)
+        acc['w_heads'].addmm_(d.t(), h_out[t])
         acc['b_heads'].add_(d.sum(0))
         denc.zero_()
         for i in reversed(range(P)):
@@ -729,14 +778,10 @@ def _backward_episode_commnet(args, net, raw, rec, d_out, acc):
     dz, dh, dx, tmp, mixed = z(R, H), z(R, H), z(R, H), z(R, H), z(E, N, H)
     w_heads = cn['w_heads']
     tanh_bwd = torch.ops.aten.tanh_backward.grad_input            # grad (1 - out^2) in one launch
-    # the H x H weight gradients have K = R: as NB products over row blocks, summed behind the loop, they fill the chip
-    # (as in backward_episode)
-    NB = 32 if R % 32 == 0 and R >= 8192 else 1
-    fpart = [torch.zeros((NB, H, H), dtype=torch.float32, device=dev) for _ in range(P)] if NB > 1 else None
-    cpart = [torch.zeros((NB, H, H), dtype=torch.float32, device=dev) for _ in range(P)] if NB > 1 and not mask_zero else None
-    blk = lambda v: v.view(NB, R // NB, H)
-    enc_acc = None        # None: nothing accumulated yet; True: partial sums hold the steps so far; False: per-step form
-    cuts = _Cuts(rec, E, N, dev)      # collection mode: no state crosses a step — only the masks of an env that starts an episode
+    fgrad = [_RowBlockGrad(acc['f_w'][i], R, 32) for i in range(P)]                                  # dz_i^T . h_i
+    cgrad = [None if mask_zero else _RowBlockGrad(acc['c_w_p'][i], R, 32) for i in range(P)]         # dz_i^T . comm_i
+    enc_grad = _EncoderGrad(raw, acc, 'wt', 'enc_bias')
+    cuts = _Cuts(args, rec, T, E, N, dev)  # collection mode: no state crosses a step — only the masks of an env that starts an episode
     for t in reversed(range(T)):
         alive, gate = cuts.masks(t, rec.alive[t], rec.gate[t])
         # ---- forward of step t again
@@ -763,40 +808,23 @@ def _backward_episode_commnet(args, net, raw, rec, d_out, acc):
                 dx.copy_(dz)
             else:
                 dx.add_(dz)
-            if NB > 1:
-                fpart[i].baddbmm_(blk(dz).transpose(1, 2), blk(hs[i]))
-            else:
-                acc['f_w'][i].addmm_(dz.t(), hs[i])
+            fgrad[i].add(dz, hs[i])
             acc['cf_b'][i].add_(dz.sum(0))
             torch.mm(dz, Fw[i], out=dh)
             if not mask_zero:
-                if NB > 1:
-                    cpart[i].baddbmm_(blk(dz).transpose(1, 2), blk(comm[i].view(R, H)))
-                else:
-                    acc['c_w_p'][i].addmm_(dz.t(), comm[i].view(R, H))
+                cgrad[i].add(dz, comm[i].view(R, H))
                 torch.mm(dz, Cw[i], out=tmp)
                 # dh += mix(dz C_i): the mixing matrix is symmetric — the same kernel on the gradient, the addend along
                 ops.comm_masked_mean_raw(tmp.view(E, N, H), alive, gate, mode_avg, True, out=mixed, addend=dh)
                 dh, mixed = mixed.view(R, H), dh.view(E, N, H)
         dx.add_(dh)                                               # h_0 = x
         tanh_bwd(dx, x, grad_input=tmp)                           # through x = tanh(enc)
-        # encoder: the first stage per step adds to partial sums, the expansion runs once behind the loop (as in backward_episode)
-        if enc_acc is not False:
-            enc_acc = raw.encode_backward_accumulate(tmp, rec.snaps[t], first=(enc_acc is None)) \
-                if hasattr(raw, 'encode_backward_accumulate') else False
-        if enc_acc is False:
-            dwt, db = raw.encode_backward(tmp, rec.snaps[t], want_bias=True)
-            acc['wt'].add_(dwt)
-            acc['enc_bias'].add_(db)
-    if enc_acc:
-        dwt, db = raw.encode_backward_finish(H, want_bias=True)
-        acc['wt'].add_(dwt)
-        acc['enc_bias'].add_(db)
-    if NB > 1:
-        for i in range(P):
-            acc['f_w'][i].add_(fpart[i].sum(0))
-            if cpart is not None:
-                acc['c_w_p'][i].add_(cpart[i].sum(0))
+        enc_grad.step(tmp, rec.snaps[t])
+    enc_grad.finish(H)
+    for i in range(P):
+        fgrad[i].finish()
+        if cgrad[i] is not None:
+            cgrad[i].finish()
 
 
 def standin_for_backward(args, net, rec=None):
@@ -874,44 +902,21 @@ def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
     dh = torch.zeros((R, H), dtype=torch.float32, device=dev)
     dz = torch.empty((T, R, H), dtype=torch.float32, device=dev)
     parts = torch.zeros((ops.rnn_backward_partials(R, H), H), dtype=torch.float32, device=dev)
-    live_flat = keep_flat = None
-    gap = int(getattr(args, 'detach_gap', 10000))
-    if rec.stream is not None:
-        if carry is not None:
-            dh.copy_(carry[0])
-        fresh, keep = rec.stream['fresh'][:T], rec.stream['keep'][:T]
-        live_flat = (~fresh).to(torch.float32).repeat_interleave(N, dim=1).contiguous()
-        keep_flat = keep.to(torch.float32).repeat_interleave(N, dim=1).contiguous()
-        dh.mul_(keep_flat[T - 1].unsqueeze(1))                            # what the next window handed over, cut at its border
-        gap = 0                                                           # (the env's OWN detach points are in `keep`)
-    elif gap > T:
-        gap = 0
+    cuts = _Cuts(args, rec, T, E, N, dev)
+    cuts.carry_in(carry, dh, at_border=True)
     dhead = d_out[:T] if d_out[:T].is_contiguous() else d_out[:T].contiguous()
-    h_last = None if (rec.h_last is None or (rec.hs.shape[0] > T and rec.h_last.data_ptr() == rec.hs[T].data_ptr())) else rec.h_last
-    w_heads = torch.cat([hd.weight for hd in net.heads] + [net.value_head.weight], 0).detach().contiguous()
-    a2 = net.affine2.weight.detach().contiguous()
+    h_last = None if rec.h_last_is_slot(T) else rec.h_last
+    w_heads, a2 = _baseline_w_heads(net), net.affine2.weight.detach().contiguous()
     enc_window = bool(getattr(args, 'enc_window', True)) and raw.encode_window_work(H) is not None
-    side = None                                                           # the heads' gradient beside the chain (_backward_window_native)
-    if dev.type == 'cuda' and bool(getattr(args, 'heads_grad_beside', True)) and not torch.cuda.is_current_stream_capturing():
-        main = torch.cuda.current_stream(dev)
-        side = _SIDE_STREAMS.get(dev.index)
-        if side is None:
-            side = _SIDE_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            _heads_grad_episode(rec, d_out, acc, T, R, H)
-    ops.rnn_backward(raw, T, E, N, H, rec.hs, dhead, rec.snaps, a2, w_heads, dh, dz, parts, h_last=h_last, detach_gap=gap,
-                     row_live=live_flat, row_keep=keep_flat, enc_first=True, enc_window=enc_window, a2_grad=acc['a2_w'],
-                     work=acc.setdefault('_work', {}))
-    dwt, _ = raw.encode_backward_window_finish(H, want_bias=False) if enc_window else raw.encode_backward_finish(H, want_bias=False)
-    acc['wt'].add_(dwt)
-    bsum = parts.sum(0)
-    acc['a1_b'].add_(bsum)
-    acc['a2_b'].add_(bsum)
-    if side is not None:
-        torch.cuda.current_stream(dev).wait_stream(side)
-    else:
-        _heads_grad_episode(rec, d_out, acc, T, R, H)
+    with _heads_grad_beside(args, rec, d_out, acc, T, R, H):
+        ops.rnn_backward(raw, T, E, N, H, rec.hs, dhead, rec.snaps, a2, w_heads, dh, dz, parts, h_last=h_last,
+                         detach_gap=cuts.gap, row_live=cuts.live_flat, row_keep=cuts.keep_flat, enc_first=True,
+                         enc_window=enc_window, a2_grad=acc['a2_w'], work=acc.setdefault('_work', {}))
+        dwt, _ = raw.encode_backward_window_finish(H, want_bias=False) if enc_window else raw.encode_backward_finish(H, want_bias=False)
+        acc['wt'].add_(dwt)
+        bsum = parts.sum(0)
+        acc['a1_b'].add_(bsum)
+        acc['a2_b'].add_(bsum)
     return (dh, dh)
 
 
@@ -928,11 +933,10 @@ def _backward_episode_baseline(args, net, raw, rec, d_out, acc, carry=None):
     z = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
     wt = net.affine1.weight.detach().t().contiguous()
     b1 = net.affine1.bias.detach()
-    w_heads = torch.cat([hd.weight for hd in net.heads] + [net.value_head.weight], 0).detach().contiguous()
+    w_heads = _baseline_w_heads(net)
     enc, dh, dz = z(R, H), z(R, H), z(R, H)
     recurrent = rec.recurrent
     lstm = recurrent and getattr(args, 'rnn_type', 'MLP') == 'LSTM'
-    gap = int(getattr(args, 'detach_gap', 10000))
     if recurrent:
         dh_rec = torch.zeros((R, H), dtype=torch.float32, device=dev)
     if lstm:
@@ -948,17 +952,12 @@ def _backward_episode_baseline(args, net, raw, rec, d_out, acc, carry=None):
         A2, b2 = net.affine2.weight.detach(), net.affine2.bias.detach()
         x1, hcur = z(R, H), z(R, H)
     tanh_bwd = torch.ops.aten.tanh_backward.grad_input            # grad (1 - out^2) in one launch
-    NB = 32 if R % 32 == 0 and R >= 8192 else 1                   # affine2's weight gradient (K = R) as row-block products
-    a2part = torch.zeros((NB, H, H), dtype=torch.float32, device=dev) if NB > 1 and not lstm else None
-    blk = lambda v: v.view(NB, R // NB, H)
-    enc_acc = None
-    cuts = _Cuts(rec, R // net.args.nagents, net.args.nagents, dev)
-    if cuts.on and recurrent:
-        if carry is not None:
-            dh_rec.copy_(carry[0])
-            if lstm:
-                dc_rec.copy_(carry[1])
-        heads_first = [(rec.hs[t + 1] if t + 1 < T else rec.h_last).clone() for t in range(T)]   # (before rows are zeroed)
+    a2grad = None if lstm else _RowBlockGrad(acc['a2_w'], R, 32)  # dz^T . x1 / dz^T . h_{t-1}
+    enc_grad = _EncoderGrad(raw, acc, 'wt', 'a1_b')
+    cuts = _Cuts(args, rec, T, R // net.args.nagents, net.args.nagents, dev)
+    if recurrent:
+        cuts.carry_in(carry, dh_rec, dc_rec if lstm else None)
+        h_out = cuts.h_out(rec)
     for t in reversed(range(T)):
         d = d_out[t]
         raw.encode_at(rec.snaps[t], wt, b1, out=enc)              # affine1(obs_t)
@@ -971,17 +970,14 @@ def _backward_episode_baseline(args, net, raw, rec, d_out, acc, carry=None):
             acc['b_heads'].add_(d.sum(0))
             torch.mm(d, w_heads, out=dh)
             tanh_bwd(dh, hcur, grad_input=dz)                                     # through the outer tanh
-            if a2part is not None:
-                a2part.baddbmm_(blk(dz).transpose(1, 2), blk(x1))
-            else:
-                acc['a2_w'].addmm_(dz.t(), x1)
+            a2grad.add(dz, x1)
             acc['a2_b'].add_(dz.sum(0))
             torch.addmm(dz, dz, A2, out=dh)                                       # d x1 = dz A2 + dz (the skip)
             tanh_bwd(dh, x1, grad_input=dz)                                       # through x1 = tanh(enc)
         else:
-            cuts.cut(t, gap, *((dh_rec, dc_rec) if lstm else (dh_rec,)))     # (h_t, c_t) were handed on detached / the episode ended
+            cuts.cut(t, *((dh_rec, dc_rec) if lstm else (dh_rec,)))          # (h_t, c_t) were handed on detached / the episode ended
             h_prev, c_prev = cuts.entering(t, rec.hs[t], rec.cs[t] if lstm else None)
-            h_t = heads_first[t] if cuts.on else (rec.hs[t + 1] if t + 1 < T else rec.h_last)
+            h_t = h_out[t]
             acc['w_heads'].addmm_(d.t(), h_t)
             acc['b_heads'].add_(d.sum(0))
             torch.addmm(dh_rec, d, w_heads, out=dh)
@@ -997,25 +993,13 @@ def _backward_episode_baseline(args, net, raw, rec, d_out, acc, carry=None):
                 torch.mm(dgates, w_hh, out=dh_rec)                # dL/dh_{t-1}
             else:                                                 # ---- RNN, tanh recurrence
                 tanh_bwd(dh, h_t, grad_input=dz)
-                if a2part is not None:
-                    a2part.baddbmm_(blk(dz).transpose(1, 2), blk(h_prev))
-                else:
-                    acc['a2_w'].addmm_(dz.t(), h_prev)
+                a2grad.add(dz, h_prev)
                 acc['a2_b'].add_(dz.sum(0))
                 torch.mm(dz, A2, out=dh_rec)
-        if enc_acc is not False:                                  # first stage per step, the expansion once behind the loop
-            enc_acc = raw.encode_backward_accumulate(dz, rec.snaps[t], first=(enc_acc is None)) \
-                if hasattr(raw, 'encode_backward_accumulate') else False
-        if enc_acc is False:
-            dwt, db = raw.encode_backward(dz, rec.snaps[t], want_bias=True)
-            acc['wt'].add_(dwt)
-            acc['a1_b'].add_(db)
-    if enc_acc:
-        dwt, db = raw.encode_backward_finish(H, want_bias=True)
-        acc['wt'].add_(dwt)
-        acc['a1_b'].add_(db)
-    if a2part is not None:
-        acc['a2_w'].add_(a2part.sum(0))
+        enc_grad.step(dz, rec.snaps[t])
+    enc_grad.finish(H)
+    if a2grad is not None:
+        a2grad.finish()
     if recurrent:
         return (dh_rec, dc_rec if lstm else dh_rec)
 

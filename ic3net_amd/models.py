@@ -42,7 +42,8 @@ class _KernelStandIn(object):
     baseline keeps a CommNetMLP of that shape whose parameters are COPIES of its own (C: zeros), refreshed when a parameter's
     version changes (like the zero-padded twin of comm.CommNetMLP), and its rollout steps run ic3_commnet_step /
     ic3_policy_step on that stand-in: sparse encoder, layer(s), heads, Philox draws, env.step and the obs rows in one launch.
-    The tanh recurrence of models.RNN (rnn_type 'MLP') has no such kernel and stays a launch chain."""
+    The tanh recurrence of models.RNN (rnn_type 'MLP'), h_t = tanh(affine1(obs) + affine2(h_{t-1})), is the non-recurrent stand-in's
+    layer with x = enc (no tanh) and h_0 = h_{t-1}: it runs ic3_commnet_step with `h_in` on a stand-in of that shape (RNN.__init__)."""
 
     def __init__(self, owner, recurrent):
         self.owner, self.recurrent, self.net, self.key = owner, recurrent, None, None

@@ -291,9 +291,7 @@ class Trainer(object):
         # what this episode's gate / inp records need against what the device can still give: free memory + the blocks torch's
         # allocator holds unused, half of it at most (the backward's own buffers, the graph pools and other ranks on the device
         # need room too); an allocation that fails anyway falls back to the recomputing backward (begin_episode)
-        free, _total = torch.cuda.mem_get_info()
-        cached = torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
-        return T * R * (4 * H + ops.record_xh_width(H)) * 4 <= (free + max(cached, 0)) // 2
+        return T * R * (4 * H + ops.record_xh_width(H)) * 4 <= bptt.device_room(torch.cuda.current_device()) // 2
 
     def _rec_inplace(self):
         """The recorded rollout of a native update reads / writes (h, c) in the episode record (no copies) when every

@@ -183,3 +183,27 @@ def test_weight_gradient_products_at_hid_256():
         gates = rec.gates.clone()
         bptt._weight_grad_products(SimpleNamespace(xh=rec.xh, hs=rec.hs, gates=gates), T, R, H, dW, lv)
         assert float((dW.double() - want).abs().max()) <= 2e-5 * max(1.0, float(want.abs().max()))
+
+
+def test_heads_gradient_without_a_side_stream_runs_behind_a_body_that_succeeded():
+    """bptt._heads_grad_beside on CPU tensors (nothing to fork onto): the heads' pass runs on the way out of the `with` body — and
+    not at all when the body raised."""
+    import torch
+    from types import SimpleNamespace
+    from ic3net_amd import bptt
+    T, R, Hh, OT = 3, 10, 8, 17                                  # (more than 16 columns: the library products, no HIP launch)
+    g = torch.Generator().manual_seed(3)
+    rec = bptt.EpisodeRecord(T, R, Hh, 1, 'cpu')
+    rec.hs.copy_(torch.randn(T + 1, R, Hh, generator=g))
+    rec.n, rec.h_last = T, rec.hs[T]
+    d_out = torch.randn(T, R, OT, generator=g)
+    acc = dict(w_heads=torch.zeros(OT, Hh), b_heads=torch.zeros(OT))
+    with pytest.raises(ZeroDivisionError):
+        with bptt._heads_grad_beside(SimpleNamespace(), rec, d_out, acc, T, R, Hh):
+            1 // 0
+    assert not acc['w_heads'].any() and not acc['b_heads'].any()
+    with bptt._heads_grad_beside(SimpleNamespace(), rec, d_out, acc, T, R, Hh):
+        assert not acc['w_heads'].any()
+    want = d_out.double().reshape(T * R, OT).t() @ rec.hs[1:].double().reshape(T * R, Hh)
+    assert float((acc['w_heads'].double() - want).abs().max()) <= 1e-5 * float(want.abs().max())
+    assert float((acc['b_heads'].double() - d_out.double().sum((0, 1))).abs().max()) <= 1e-5 * T * R

@@ -223,3 +223,45 @@ def test_dispatch(monkeypatch):
     del seen[:]
     _grads(tr, batch, recs, True)
     assert seen == ['_backward_episode_standin']
+
+
+def test_heads_gradient_is_joined_when_the_backward_raises():
+    """bptt._heads_grad_beside (both window drivers issue their chain inside it): the heads' gradient forked onto the side stream is
+    waited for by the current stream on the way out even when the body raises — the caller releases the record next.  The side
+    stream is kept busy first, so the pass is still pending when the body raises: once the CURRENT stream is synchronised the side
+    stream has nothing left, and the heads' accumulators are those of a run whose body did not raise, bit for bit."""
+    from ic3net_amd import bptt
+    tr, a, batch, recs = _recorded('pp_hard_iric_tanh', 64, 8)
+    _, d_out = bptt.loss_gradients(a, batch, recs)
+    net, rec = tr.policy_net, recs[0]
+    T, R, H = rec.n, rec.hs.shape[1], rec.hs.shape[2]
+    dev = rec.hs.device
+    side = bptt._SIDE_STREAMS.setdefault(dev.index, torch.cuda.Stream(device=dev))
+    busy = torch.randn(4096, 4096, device=dev)
+
+    class Boom(Exception):
+        pass
+
+    def run(fail):
+        acc = bptt.new_accumulators(net)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(side):
+            for _ in range(30):
+                busy @ busy
+        try:
+            with torch.no_grad(), bptt._heads_grad_beside(a, rec, d_out, acc, T, R, H):
+                assert bptt._SIDE_STREAMS[dev.index] is side
+                if fail:
+                    raise Boom()
+        except Boom:
+            assert fail
+        else:
+            assert not fail
+        torch.cuda.current_stream(dev).synchronize()
+        assert side.query(), "the current stream did not wait for the side stream"
+        return acc['w_heads'].clone(), acc['b_heads'].clone()
+
+    w0, b0 = run(False)
+    w1, b1 = run(True)
+    assert float(w0.abs().max()) > 0 and float(b0.abs().max()) > 0
+    assert torch.equal(w1, w0) and torch.equal(b1, b0)
