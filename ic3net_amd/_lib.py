@@ -89,6 +89,15 @@ class RnnBptt(C.Structure):
                 ("wgrad_scratch", C.c_void_p)]
 
 
+class MlpBptt(C.Structure):
+    """ic3_mlp_bptt (include/ic3_rollout.h): one window of the IC baseline's (models.MLP) backward."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "enc_first", "enc_window")] + \
+               [("h", C.c_void_p), ("dhead", C.c_void_p), ("snaps", C.c_void_p), ("snap_words", C.c_int64), ("enc_wt", C.c_void_p),
+                ("enc_bias", C.c_void_p), ("loc_table", C.c_void_p), ("a2", C.c_void_p), ("w_heads", C.c_void_p), ("x1", C.c_void_p),
+                ("dz", C.c_void_p), ("de", C.c_void_p), ("dbias_partials", C.c_void_p), ("enc_work", C.c_void_p),
+                ("a2_grad", C.c_void_p), ("wgrad_scratch", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "ic3_version": (C.c_int, []),
@@ -121,6 +130,8 @@ EXPORTS = {
     "ic3_env_encode_backward_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                                  C.c_void_p, C.c_int, C.c_void_p]),
     "ic3_env_encode_backward_window_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ic3_env_encode_backward_window_finish_scratch": (C.c_int64, [C.c_void_p, C.c_int]),
+    "ic3_env_encode_backward_window_finish_ordered": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "ic3_env_check": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ic3_env_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ic3_env_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -155,6 +166,10 @@ EXPORTS = {
     "ic3_rnn_weight_grad_scratch_floats": (C.c_size_t, [C.c_longlong, C.c_int]),
     "ic3_rnn_weight_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_void_p]),
+    "ic3_mlp_backward_supported": (C.c_int, [C.c_void_p, C.c_int]),
+    "ic3_mlp_backward_partials": (C.c_int, [C.c_longlong, C.c_int]),
+    "ic3_mlp_backward_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
+    "ic3_mlp_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ic3_env_set_record_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ic3_lstm_gates_backward_dx": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ic3_commnet_forward_supported": (C.c_int, [C.c_int, C.c_int]),

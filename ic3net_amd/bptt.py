@@ -94,12 +94,16 @@ class EpisodeRecord(object):
         # as their `out`); out_n = the steps that did
         self.out = None
         self.out_n = 0
+        # (T, R, H) the hidden state every step of a NON-recurrent baseline (models.MLP) ended with, written by the step launch itself
+        # (Trainer hands slot t as ic3_commnet_step's h_out); h_fin_n = the steps that did — _backward_window_mlp reads it
+        self.h_fin = None
+        self.h_fin_n = 0
 
     def release(self):
         """Drop the record's tensors now (tens of GB with recorded gates): the update is done with them, and whatever still
         refers to the record object — a reference cycle waiting for the garbage collector — must not keep them alive beside
         the next update's record."""
-        self.hs = self.cs = self.gates = self.xh = self.snaps = self.h_last = self.out = None
+        self.hs = self.cs = self.gates = self.xh = self.snaps = self.h_last = self.out = self.h_fin = None
         self.alive, self.gate, self.stream = [], [], None
 
     def start_from(self, h, c):
@@ -482,7 +486,7 @@ def _heads_grad_beside(args, rec, d_out, acc, T, R, H):
     idle issue slots instead of taking 0.7 ms of its own).  The current stream waits for it on the way out WHETHER OR NOT the body
     raised: the caller releases the record then, and the side stream must be done reading hs / d_out and writing acc['w_heads'].
     Without a second stream (CPU, args.heads_grad_beside off, a graph capture) the pass runs behind the body, if that succeeded."""
-    dev = rec.hs.device
+    dev = rec.hs.device if rec.hs is not None else rec.h_fin.device
     side = None
     try:
         if dev.type == 'cuda' and bool(getattr(args, 'heads_grad_beside', True)) and not torch.cuda.is_current_stream_capturing():
@@ -657,15 +661,17 @@ def _baseline_w_heads(net):
 
 def _heads_grad_episode(rec, d_out, acc, T, R, H):
     """heads + value head over a whole record: dW += sum_t d_t^T h_t, db += sum_t sum_rows d_t — h_t of step t is the state
-    ENTERING step t + 1 (slot t + 1 of the record).  ONE pass (ic3_heads_grad) for up to 16 output columns, a library product
-    otherwise."""
+    ENTERING step t + 1 (slot t + 1 of the record), or slot t of h_fin where the record keeps no recurrent state (models.MLP).
+    ONE pass (ic3_heads_grad) for up to 16 output columns, a library product otherwise."""
     def grad(d, h):
         if d.shape[-1] <= ops.HEADS_GRAD_MAX_OT:
             ops.heads_grad(d, h, acc['w_heads'], acc['b_heads'], acc.setdefault('_work', {}))
         else:                                                             # (more than 15 actions in total)
             acc['w_heads'].addmm_(d.t(), h)
             acc['b_heads'].add_(d.sum(0))
-    if rec.h_last_is_slot(T):
+    if rec.hs is None:
+        grad(d_out[:T].reshape(T * R, -1), rec.h_fin[:T].reshape(T * R, H))
+    elif rec.h_last_is_slot(T):
         grad(d_out[:T].reshape(T * R, -1), rec.hs[1:T + 1].reshape(T * R, H))
     else:
         if T > 1:
@@ -920,13 +926,77 @@ def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
     return (dh, dh)
 
 
+MLP_WINDOW_SIZES = (64, 128)     # ic3_mlp_backward
+
+
+def mlp_window_wanted(args, net, raw):
+    """What a rollout must hold for _backward_window_mlp before it records h_fin: the IC baseline itself (models.MLP, not its
+    recurrent subclass) at hid 64 / 128 — no zero-padded twin —, the native loop on, and the library's answer for this env."""
+    from . import models
+    H = args.hid_size
+    if type(net) is not models.MLP or getattr(args, 'recurrent', False) or H not in MLP_WINDOW_SIZES:
+        return False
+    if not bool(getattr(args, 'bptt_native_loop', True)) or ops.padded_hidden(H) is not None:
+        return False
+    return hasattr(raw, '_h') and ops.mlp_backward_supported(raw, H)
+
+
+def _mlp_window_ok(args, net, raw, rec, d_out):
+    """models.MLP on a record whose step launches stored h of every step (h_fin), hid_size 64 / 128, at most 16 output columns, the
+    native loop on (args.bptt_native_loop), the library's answer and the room for the three T x R x H rings (x1, dz, de):
+    _backward_window_mlp."""
+    if rec.recurrent or not mlp_window_wanted(args, net, raw):
+        return False
+    H, T = args.hid_size, rec.n
+    h = getattr(rec, 'h_fin', None)
+    if h is None or T < 1 or rec.h_fin_n != T or h.shape[0] < T or tuple(h.shape[1:]) != (rec.rows, H) or not h.is_cuda:
+        return False
+    if d_out.shape[-1] > 16:
+        return False
+    return _ring_fits(h.device, 3 * T * rec.rows * H * 4)
+
+
+def _backward_window_mlp(args, net, raw, rec, d_out, acc):
+    """_backward_episode_baseline's non-recurrent branch for a whole window through ic3_mlp_backward (csrc/bptt_kernels.hip).  No
+    state crosses a step, so the window is T x R independent rows: e of every snapshot into a ring (T encoder launches), then ONE
+    launch — x1 = tanh(e) over e, dz = (d . W_heads)(1 - h^2) with the h the step launches recorded (rec.h_fin), de = (dz . A2 +
+    dz)(1 - x1^2), the column sums of dz as per-workgroup partials —, the sparse encoder's first stage over the de ring and affine2's
+    weight gradient sum dz^T x1 over all rows in one launch.  Behind it: the encoder's expansion (affine1.weight; its bias sum is
+    affine1.bias's gradient), the partials' sum (affine2.bias), the heads' pass beside the chain.  Collection mode needs no cuts
+    (the loop applies none either); the record is read, never written."""
+    T, R, H = rec.n, rec.rows, args.hid_size
+    N = net.args.nagents
+    E = R // N
+    dev = rec.h_fin.device
+    x1, dz, de = (torch.empty((T, R, H), dtype=torch.float32, device=dev) for _ in range(3))
+    parts = torch.empty((ops.mlp_backward_partials(T * R, H), H), dtype=torch.float32, device=dev)
+    dhead = d_out[:T] if d_out[:T].is_contiguous() else d_out[:T].contiguous()
+    wt = net.affine1.weight.detach().t().contiguous()
+    w_heads, a2 = _baseline_w_heads(net), net.affine2.weight.detach().contiguous()
+    enc_window = bool(getattr(args, 'enc_window', True)) and raw.encode_window_work(H) is not None
+    with _heads_grad_beside(args, rec, d_out, acc, T, R, H):
+        ops.mlp_backward(raw, T, E, N, H, rec.h_fin, dhead, rec.snaps, wt, net.affine1.bias.detach().contiguous(), a2, w_heads,
+                         x1, dz, de, parts, enc_first=True, enc_window=enc_window, a2_grad=acc['a2_w'],
+                         work=acc.setdefault('_work', {}))
+        # (the ordered finish: affine1's gradient identical run to run, like everything else on this path — where the env has the
+        #  window form; the per-step form's finish adds with float atomics, so there affine1.weight's last bits may move)
+        dwt, db = raw.encode_backward_window_finish_ordered(H, want_bias=True) if enc_window \
+            else raw.encode_backward_finish(H, want_bias=True)
+        acc['wt'].add_(dwt)
+        acc['a1_b'].add_(db)
+        acc['a2_b'].add_(parts.sum(0))
+
+
 def _backward_episode_baseline(args, net, raw, rec, d_out, acc, carry=None):
     """The IC / IRIC baselines of models.py:8-97 (no communication), differentiated by hand over the recorded rollout:
       MLP  (models.py:23-34)   x1 = tanh(affine1(obs));  h = tanh(affine2(x1) + x1)         every step on its own
       RNN  (models.py:68-92)   rnn_type 'MLP':  h_t = tanh(affine2(h_{t-1}) + affine1(obs))
                                rnn_type 'LSTM': (h_t, c_t) = LSTMCell(affine1(obs), (h_{t-1}, c_{t-1}))
     heads / value on h.  affine1 is the sparse encoder (ic3_env_encode_at on the step's snapshot, ic3_env_encode_backward);
-    the recurrent gradient is cut where the Trainer detaches the hidden state (trainer.py:56-60)."""
+    the recurrent gradient is cut where the Trainer detaches the hidden state (trainer.py:56-60).  The MLP branch of a record
+    that holds h of every step goes to _backward_window_mlp (one launch over the window) instead of the loop below."""
+    if not rec.recurrent and _mlp_window_ok(args, net, raw, rec, d_out):
+        return _backward_window_mlp(args, net, raw, rec, d_out, acc)
     T, H = rec.n, args.hid_size
     R = rec.rows if not rec.recurrent else rec.hs.shape[1]
     dev = net.affine1.weight.device

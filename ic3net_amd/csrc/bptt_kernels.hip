@@ -1104,3 +1104,239 @@ extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream 
     }
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// ic3_mlp_backward: the IC baseline (models.py:23-34, models.MLP), every step on its own:
+//     e = affine1(obs),   x1 = tanh(e),   h = tanh(affine2(x1) + x1),   [logits | value] = W_heads h + b
+// differentiated over a window of recorded steps.  No state crosses a step, so the window is Q = T x R independent rows and the
+// backward is ONE launch over all of them (mlp_bwd_kernel):
+//     x1  = tanh(e)                                        -> over e (the ring slot holds x1 afterwards)
+//     dz  = (d . W_heads) (1 - h^2)                        -> the dz ring (affine2's pre-activation gradient)
+//     de  = (dz . A2 + dz) (1 - x1^2)                      -> the de ring (affine1's; the `+ dz` is the skip)
+//     per-workgroup column sums of dz                      (d affine2.bias; fixed-order reduction by the caller)
+// behind it the encoder's first stage over the de ring and ONE rnn_wgrad_kernel launch for dA2 += dz^T . x1 over all Q rows.
+//
+// mlp_bwd_kernel<H>: the shape of rnn_tanh_bwd_kernel — 4H threads, persistent over tiles of 64 rows, A2 in LDS in fragment order
+// for the workgroup's life.  Per tile: phase 0 — thread (row group, 4-column chunk) forms x1 and dz for 4 rows, stores both with
+// 16-byte stores, dz also to the LDS tile and into its column sums; phase 1 — wave (rb, cb) multiplies tile rows [32 rb, +32) by
+// A2's columns [32 cb, +32); epilogue — the accumulators go back through the LDS tile (over the dz rows every wave is done with)
+// and thread (row group, chunk) combines them with the dz / x1 it still holds and stores de 16 bytes per lane (4-byte stores from
+// the accumulator layout cost 1.3 x the write traffic in lstm_gates_bwd_kernel).  The next tile's rows are requested before the
+// product, so the matrix phase of a tile covers the loads of the next.  Row offsets in 64 bits (TJ-hard: 13.1 M rows x 512 B).
+// LDS as rnn_tanh_bwd_kernel (110 KB at H = 128: one workgroup of 8 waves per CU; 41 KB at 64: two of 4).
+// HBM per row: e, h in, x1, dz, de out (5 H floats) + OT; MFMA 2 H^2 flop per row on the fp32 instruction.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace ic3 {
+
+struct MlpBwdArgs {
+    float* x1;               // [Q][H] in: e, out: x1 = tanh(e)
+    const float* h;          // [Q][H]
+    const float* dhead;      // [Q][OT]
+    const float* w_heads;    // [OT][H]
+    const float* a2;         // [H][H] affine2.weight (out, in): d x1 = dz . A2 + dz
+    float* dz;               // [Q][H]
+    float* de;               // [Q][H]
+    float* db_part;          // [gridDim.x][H]
+    long long Q;
+    int OT, tiles, accumulate;
+};
+
+template <int H>
+__global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void mlp_bwd_kernel(const MlpBwdArgs a)
+{
+    constexpr int NT = 4 * H, H4 = H / 4, LDA = H + 4, LDA4 = LDA / 4, CB = H / 32, RPP = NT / H4, PER = 64 / RPP;
+    constexpr int DPT = 64 * 16 / NT;                            // d values a thread stages per tile, at most
+    static_assert(RPP * PER == 64 && NT / 64 == 2 * CB && DPT * NT == 64 * 16, "tile split");
+    IC3_DYNAMIC_LDS(float, smem);
+    const bp_f32x4* const Bf4 = reinterpret_cast<const bp_f32x4*>(smem);     // [H / 8][2][H] float4
+    float* const Dz = smem + H * H;                                          // [64][LDA] the tile's dz, then its dz . A2
+    bp_f32x4* const Dz4 = reinterpret_cast<bp_f32x4*>(Dz);
+    float* const Wh = Dz + 64 * LDA;                                         // [16][H] W_heads
+    const bp_f32x4* const Wh4 = reinterpret_cast<const bp_f32x4*>(Wh);
+    float* const Sd = Wh + 16 * H;                                           // [64][OT] the tile's d rows
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
+    const int cb = w % CB, rb = w / CB;
+    const int c4 = tid % H4, rg = tid / H4;                      // phase 0 / epilogue: column chunk c4 of rows rg + RPP i
+    const int OT = a.OT;
+    for (int i = tid; i < H * H; i += NT) {
+        const int k = i / H, col = i - k * H;
+        smem[(((k >> 3) * 2 + ((k >> 2) & 1)) * H + col) * 4 + (k & 3)] = a.a2[i];
+    }
+    for (int i = tid; i < OT * H; i += NT) Wh[i] = a.w_heads[i];
+    bp_f32x4 bsum = { 0.f, 0.f, 0.f, 0.f };
+    bp_f32x4 ev[PER], hv[PER];
+    float dp[DPT];
+    // (rows past the window read 0 and their stores are dropped: the ranges of the buffer descriptors)
+    auto fetch = [&](int tile) {
+        const long long r0 = (long long)tile * 64;
+        const int rows = (a.Q - r0) < 64 ? (int)(a.Q - r0) : 64;
+        const __amdgpu_buffer_rsrc_t re = bp_rsrc(a.x1 + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rh = bp_rsrc(a.h + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rd = bp_rsrc(a.dhead + r0 * OT, (long long)rows * OT * 4);
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int off = ((rg + RPP * i) * H + 4 * c4) * 4;
+            ev[i] = bp_load4(re, off);
+            hv[i] = bp_load4(rh, off);
+        }
+#pragma unroll
+        for (int i = 0; i < DPT; ++i) dp[i] = bp_load1(rd, (tid + i * NT) * 4);      // (past 64 OT: past the range, 0)
+    };
+    if ((int)blockIdx.x < a.tiles) fetch(blockIdx.x);
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        const long long r0 = (long long)tile * 64;
+        const int rows = (a.Q - r0) < 64 ? (int)(a.Q - r0) : 64;
+        const __amdgpu_buffer_rsrc_t rx = bp_rsrc(a.x1 + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rz = bp_rsrc(a.dz + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rde = bp_rsrc(a.de + r0 * H, (long long)rows * H * 4);
+#pragma unroll
+        for (int i = 0; i < DPT; ++i) Sd[tid + i * NT] = dp[i];
+        __syncthreads();
+        // ---- phase 0: x1 over e; dz of the tile -> ring, LDS, column sums
+        bp_f32x4 xv[PER], zv[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int row = rg + RPP * i;
+            bp_f32x4 x;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) x[q] = fast_tanh(ev[i][q]);
+            bp_f32x4 v = { 0.f, 0.f, 0.f, 0.f };
+            for (int o = 0; o < OT; ++o) v += Sd[row * OT + o] * Wh4[o * H4 + c4];
+            const bp_f32x4 z = v * (1.0f - hv[i] * hv[i]);
+            bsum += z;
+            xv[i] = x;
+            zv[i] = z;
+            Dz4[row * LDA4 + c4] = z;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, x), rx, (row * H + 4 * c4) * 4, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, z), rz, (row * H + 4 * c4) * 4, 0, 0);
+        }
+        if (tile + (int)gridDim.x < a.tiles) fetch(tile + gridDim.x);       // the next tile's rows, in flight under the product
+        __syncthreads();
+        // ---- phase 1: dz . A2 on the fp32 matrix instruction (k = 8 kb + 4 lh + j: A fragment and B slot agree)
+        bp_f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+#pragma unroll 4
+        for (int kb = 0; kb < H / 8; ++kb) {
+            const bp_f32x4 a4 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
+            const bp_f32x4 b4 = Bf4[(2 * kb + lh) * H + 32 * cb + li];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bp_mfma(acc, a4[j], b4[j]);
+        }
+        __syncthreads();                                         // every wave has read the tile's dz rows
+        // ---- epilogue: the product back through the LDS tile, de = (dz . A2 + dz)(1 - x1^2) in the phase-0 layout
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg)
+            Dz[(32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh) * LDA + 32 * cb + li] = acc[reg];
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int row = rg + RPP * i;
+            const bp_f32x4 g = (Dz4[row * LDA4 + c4] + zv[i]) * (1.0f - xv[i] * xv[i]);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, g), rde, (row * H + 4 * c4) * 4, 0, 0);
+        }
+        __syncthreads();                                         // every thread is done with the tile's LDS
+    }
+    // column sums of the workgroup: the RPP row groups of a chunk added in group order (reproducible)
+    Dz4[rg * H4 + c4] = bsum;
+    __syncthreads();
+    if (tid < H4) {
+        bp_f32x4 s = Dz4[tid];
+        for (int g = 1; g < RPP; ++g) s += Dz4[g * H4 + tid];
+        bp_f32x4* dst = reinterpret_cast<bp_f32x4*>(a.db_part + (size_t)blockIdx.x * H) + tid;
+        *dst = a.accumulate ? *dst + s : s;
+    }
+}
+
+}  // namespace ic3
+
+// Tile plan of the launch: as ic3_rnn_backward_partials, over the Q rows of the window (one launch, not one per step).
+extern "C" int ic3_mlp_backward_partials(long long Q, int H)
+{
+    if (Q <= 0 || (H != 64 && H != 128)) return 0;
+    const long long tiles = (Q + 63) / 64;
+    const long long cap = (long long)ic3::bp_cus() * (H == 64 ? 2 : 1);
+    const long long rounds = (tiles + cap - 1) / cap;
+    return (int)((tiles + rounds - 1) / rounds);
+}
+
+extern "C" int ic3_mlp_backward_supported(const ic3_env* env, int H)
+{
+    if (!env || (H != 64 && H != 128)) return 0;
+    return ic3_bptt_backward_supported(env, H);    // (the sparse encoder's backward in its partial-sums form)
+}
+
+// the launch alone (also the unit the tests drive): returns the number of partials written / added to
+extern "C" int ic3_mlp_backward_step(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT, const float* a2,
+                                     float* dz, float* de, float* dbias_partials, int accumulate, long long Q, int H,
+                                     ic3_stream stream)
+{
+    using namespace ic3;
+    if (!x1_inout || !h || !dhead || !w_heads || !a2 || !dz || !de || !dbias_partials || Q <= 0)
+        return fail(-22, "ic3_mlp_backward_step: null argument");
+    if (H != 64 && H != 128) return fail(-38, "ic3_mlp_backward_step: hid_size 64 / 128");
+    if (OT < 1) return fail(-22, "ic3_mlp_backward_step: OT >= 1");
+    if (OT > 16) return fail(-38, "ic3_mlp_backward_step: at most 16 output columns");
+    if (Q >= (1ll << 36)) return fail(-22, "ic3_mlp_backward_step: Q < 2^36");
+    const int grid = ic3_mlp_backward_partials(Q, H);
+    const MlpBwdArgs a{ x1_inout, h, dhead, w_heads, a2, dz, de, dbias_partials, Q, OT, (int)((Q + 63) / 64), accumulate };
+    const size_t lds = ((size_t)H * H + 64 * (H + 4) + 16 * H + 64 * 16) * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    if (H == 128) {
+        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(mlp_bwd_kernel<128>), lds));
+        hipLaunchKernelGGL((mlp_bwd_kernel<128>), dim3(grid), dim3(512), lds, s, a);
+    } else {
+        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(mlp_bwd_kernel<64>), lds));
+        hipLaunchKernelGGL((mlp_bwd_kernel<64>), dim3(grid), dim3(256), lds, s, a);
+    }
+    IC3_HIP(hipGetLastError());
+    return grid;
+}
+
+extern "C" int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream)
+{
+    using namespace ic3;
+    if (!env || !b) return fail(-22, "ic3_mlp_backward: null argument");
+    if (b->struct_size != sizeof(ic3_mlp_bptt))
+        return fail(-22, "ic3_mlp_backward: ic3_mlp_bptt has " + std::to_string(b->struct_size) + " bytes, this library's has " +
+                             std::to_string(sizeof(ic3_mlp_bptt)) + " (header / library version mismatch)");
+    const int T = b->T, E = b->E, N = b->N, H = b->H;
+    if (T <= 0 || E <= 0 || N <= 0 || E != env->dims.E || N != env->dims.N)
+        return fail(-22, "ic3_mlp_backward: T, E, N must be positive and E, N the handle's");
+    if (!ic3_mlp_backward_supported(env, H)) return fail(-38, "ic3_mlp_backward: hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form");
+    if (b->OT < 1) return fail(-22, "ic3_mlp_backward: OT >= 1");
+    if (b->OT > 16) return fail(-38, "ic3_mlp_backward: at most 16 output columns");
+    if (!b->h || !b->dhead || !b->snaps || !b->enc_wt || !b->enc_bias || !b->a2 || !b->w_heads || !b->x1 || !b->dz || !b->de ||
+        !b->dbias_partials || !b->enc_work)
+        return fail(-22, "ic3_mlp_backward: null argument");
+    if (b->a2_grad && !b->wgrad_scratch) return fail(-22, "ic3_mlp_backward: a2_grad needs wgrad_scratch");
+    if (b->enc_window && ic3_env_encode_backward_window_work(env, H) <= 0)
+        return fail(-22, "ic3_mlp_backward: enc_window on a configuration without ic3_env_encode_backward_window");
+    const long long R = (long long)E * N, Q = (long long)T * R;
+    // e of every recorded step -> the slots of the x1 ring (the step launch does not record its encoder rows)
+    for (int t = 0; t < T; ++t) {
+        const int rc = ic3_env_encode_at(env, b->snaps + (size_t)t * b->snap_words, b->enc_wt, b->enc_bias, b->loc_table,
+                                         b->x1 + (size_t)t * R * H, H, H, stream);
+        if (rc < 0) return rc;
+    }
+    int rc = ic3_mlp_backward_step(b->x1, b->h, b->dhead, b->w_heads, b->OT, b->a2, b->dz, b->de, b->dbias_partials, 0, Q, H, stream);
+    if (rc < 0) return rc;
+    if (b->enc_window) {
+        rc = ic3_env_encode_backward_window(env, b->snaps, b->snap_words, T, b->de, H, R * H, H, b->enc_work, b->enc_first, stream);
+        if (rc < 0) return rc;
+    } else {
+        int enc_first = b->enc_first;
+        for (int t = T - 1; t >= 0; --t) {                       // (last step first: the order of the per-step loop)
+            rc = ic3_env_encode_backward_accumulate(env, b->snaps + (size_t)t * b->snap_words, b->de + (size_t)t * R * H, H, H,
+                                                    b->enc_work, enc_first, stream);
+            if (rc < 0) return rc;
+            enc_first = 0;
+        }
+    }
+    if (b->a2_grad) {
+        rc = ic3_rnn_weight_grad(b->dz, b->x1, nullptr, Q, H, b->a2_grad, 1, b->wgrad_scratch, stream);
+        if (rc < 0) return rc;
+    }
+    return 0;
+}

@@ -549,4 +549,22 @@ __device__ __forceinline__ float enc_bwd_pfold(const float* __restrict__ P, int 
 }
 __host__ __device__ inline long long enc_bwd_pfold_threads(long long items) { return 64 * ((items + 15) / 16); }
 
+// The ORDERED finish of the window form (ic3_env_encode_backward_window_finish_ordered): the same expansion as the expand kernels
+// with every sum in a fixed order and no atomic, so that dWt / dbias are identical run to run.  First the `np` partials are folded
+// in partial order — out [nP + nD] = [sum_k P[k] | sum_k D[k]] —, then one thread per element of dWt gathers what lands on it
+// (pp_ / tj_encode_bwd_gather_kernel).  (A template so that every file that launches it has its own copy.)
+template <int UNROLL>
+__global__ __launch_bounds__(256) void enc_bwd_fold_kernel(const float* __restrict__ P, const float* __restrict__ D, int np,
+                                                           long long nP, long long nD, float* __restrict__ out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nP + nD) return;
+    const float* src = i < nP ? P + i : D + (i - nP);
+    const size_t stride = (size_t)(i < nP ? nP : nD);
+    float v = 0.f;
+#pragma unroll UNROLL
+    for (int k = 0; k < np; ++k) v += src[(size_t)k * stride];
+    out[i] = v;
+}
+
 }  // namespace ic3

@@ -489,6 +489,20 @@ int ic3_env_encode_backward_window_finish(ic3_env* env, int H, float* dWt, float
                                    : tj_encode_bwd_window_finish(env, H, dWt, dbias, work, (hipStream_t)stream);
 }
 
+int64_t ic3_env_encode_backward_window_finish_scratch(const ic3_env* env, int H)
+{
+    if (!env || H <= 0) return fail(-22, "ic3_env_encode_backward_window_finish_scratch: null handle or hid_size <= 0");
+    return env->kind == IC3_ENV_PP ? pp_encode_bwd_window_finish_scratch(env, H) : tj_encode_bwd_window_finish_scratch(env, H);
+}
+
+int ic3_env_encode_backward_window_finish_ordered(ic3_env* env, int H, float* dWt, float* dbias, float* work, float* scratch,
+                                                  ic3_stream stream)
+{
+    if (!env || !dWt || !work || !scratch || H <= 0) return fail(-22, "ic3_env_encode_backward_window_finish_ordered: null argument");
+    return env->kind == IC3_ENV_PP ? pp_encode_bwd_window_finish_ordered(env, H, dWt, dbias, work, scratch, (hipStream_t)stream)
+                                   : tj_encode_bwd_window_finish_ordered(env, H, dWt, dbias, work, scratch, (hipStream_t)stream);
+}
+
 int ic3_env_step(ic3_env* env, const int32_t* actions, float* obs, float* reward, int32_t* done, int32_t* alive,
                  int32_t* is_completed, ic3_stream stream)
 {

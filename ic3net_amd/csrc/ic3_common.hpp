@@ -227,6 +227,11 @@ int tj_encode_bwd_window(ic3_env* env, const int32_t* snaps, long long snap_word
                          int H, float* work, int first, hipStream_t s);
 int pp_encode_bwd_window_finish(ic3_env* env, int H, float* dWt, float* dbias, float* work, hipStream_t s);
 int tj_encode_bwd_window_finish(ic3_env* env, int H, float* dWt, float* dbias, float* work, hipStream_t s);
+// the same expansion with every sum in a fixed order (no atomics); scratch: *_finish_scratch floats
+int64_t pp_encode_bwd_window_finish_scratch(const ic3_env* env, int H);
+int64_t tj_encode_bwd_window_finish_scratch(const ic3_env* env, int H);
+int pp_encode_bwd_window_finish_ordered(ic3_env* env, int H, float* dWt, float* dbias, float* work, float* scratch, hipStream_t s);
+int tj_encode_bwd_window_finish_ordered(ic3_env* env, int H, float* dWt, float* dbias, float* work, float* scratch, hipStream_t s);
 // tj_tables.cpp (host)
 int tj_build_tables(int dim, int vision, int difficulty, int* h, int* w, int* base, int* npath, int* narrival,
                     int* routes_per_arrival, std::vector<int32_t>& grid, std::vector<int32_t>& route_off,

@@ -482,6 +482,64 @@ int pp_encode_bwd_window_finish(ic3_env* env, int H, float* dWt, float* dbias, f
     return 0;
 }
 
+// Stage 2 for PP in a fixed order (pp_encode_bwd_expand_kernel without its atomics): thread (row, h) of dWt — row = cell * vocab +
+// id — takes the folded position sum of the ONE position whose window cell `cell` shows grid id `id`, or, for the OUTSIDE id, the
+// sum over the positions whose cell falls off the grid, in position order; the class columns and dbias come from the folded slots.
+__global__ __launch_bounds__(256) void pp_encode_bwd_gather_kernel(const float* __restrict__ Psum, const float* __restrict__ Dsum,
+                                                                   float* __restrict__ dWt, float* __restrict__ dbias, int dim,
+                                                                   int v, int H)
+{
+    const int W = 2 * v + 1, WW = W * W, nslots = 2 * WW, npos = dim * dim, vocab = dim * dim + 4;
+    const int OUTSIDE = dim * dim + 1;
+    const long long n = (long long)WW * vocab * H;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n + H) return;
+    if (i >= n) {
+        if (dbias) dbias[i - n] = Dsum[(size_t)nslots * H + (i - n)];
+        return;
+    }
+    const int h = (int)(i % H), row = (int)(i / H), cell = row / vocab, id = row - cell * vocab;
+    const int dr = cell / W - v, dc = cell % W - v;
+    float val = 0.f;
+    if (id < npos) {
+        const int pr = id / dim - dr, pc = id % dim - dc;
+        if (pr >= 0 && pr < dim && pc >= 0 && pc < dim) val = Psum[(size_t)(pr * dim + pc) * H + h];
+    } else if (id == OUTSIDE) {
+        for (int pos = 0; pos < npos; ++pos) {
+            const int gr = pos / dim + dr, gc = pos % dim + dc;
+            if (gr < 0 || gr >= dim || gc < 0 || gc >= dim) val += Psum[(size_t)pos * H + h];
+        }
+    } else if (id == vocab - 1) {
+        val = Dsum[(size_t)(2 * cell) * H + h];
+    } else if (id == vocab - 2) {
+        val = Dsum[(size_t)(2 * cell + 1) * H + h];
+    }
+    dWt[i] = val;
+}
+
+int64_t pp_encode_bwd_window_finish_scratch(const ic3_env* env, int H)
+{
+    const ic3_pp_cfg& c = env->pp;
+    const int W = 2 * c.vision + 1;
+    return pp_win_plan(env, H).MBP ? (int64_t)(c.dim * c.dim + 2 * W * W + 1) * H : 0;
+}
+int pp_encode_bwd_window_finish_ordered(ic3_env* env, int H, float* dWt, float* dbias, float* work, float* scratch, hipStream_t s)
+{
+    const ic3_pp_cfg& c = env->pp;
+    const int W = 2 * c.vision + 1, npos = c.dim * c.dim;
+    const EncWinPlan pl = pp_win_plan(env, H);
+    if (!pl.MBP) return fail(-38, "ic3_env_encode_backward_window_finish_ordered: this configuration has no window form");
+    const long long nP = (long long)npos * H, nD = (long long)(2 * W * W + 1) * H;
+    hipLaunchKernelGGL(enc_bwd_fold_kernel<8>, dim3((unsigned)((nP + nD + 255) / 256)), dim3(256), 0, s, work,
+                       work + (size_t)pl.nrg * npos * H, pl.nrg, nP, nD, scratch);
+    IC3_HIP(hipGetLastError());
+    const long long n = (long long)env->dims.obs_dim * H + H;
+    hipLaunchKernelGGL(pp_encode_bwd_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, scratch + nP, dWt,
+                       dbias, c.dim, c.vision, H);
+    IC3_HIP(hipGetLastError());
+    return 0;
+}
+
 int pp_reset(ic3_env* env, hipStream_t s)
 {
     const ic3_pp_cfg& c = env->pp;

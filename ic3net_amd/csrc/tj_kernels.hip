@@ -632,6 +632,63 @@ int tj_encode_bwd_window_finish(ic3_env* env, int H, float* dWt, float* dbias, f
     return 0;
 }
 
+// Stage 2 for TJ in a fixed order (tj_encode_bwd_expand_kernel without its atomics): thread (row, c) of dWt.  A header row takes
+// its folded slot; row = hdr + cell * vocab + id takes the folded position sums of every position whose window cell `cell` shows
+// road id `id` (or falls off the grid, for `outside`), in position order, and the car class's row the cell's folded slot on top.
+__global__ __launch_bounds__(256) void tj_encode_bwd_gather_kernel(const float* __restrict__ Psum, const float* __restrict__ Dsum,
+                                                                   const int32_t* __restrict__ grid, float* __restrict__ dWt,
+                                                                   float* __restrict__ dbias, int h, int w, int v, int vocab,
+                                                                   int outside, int car_class, int H, int hdr)
+{
+    const int W = 2 * v + 1, WW = W * W, nslots = hdr + WW, npos = h * w;
+    const long long n = ((long long)hdr + (long long)WW * vocab) * H;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n + H) return;
+    if (i >= n) {
+        if (dbias) dbias[i - n] = Dsum[(size_t)nslots * H + (i - n)];
+        return;
+    }
+    const int c = (int)(i % H), row = (int)(i / H);
+    if (row < hdr) {
+        dWt[i] = Dsum[(size_t)row * H + c];
+        return;
+    }
+    const int cell = (row - hdr) / vocab, id = (row - hdr) - cell * vocab;
+    const int dr = cell / W - v, dc = cell % W - v;
+    float val = 0.f;
+    for (int pos = 0; pos < npos; ++pos) {
+        const int gr = pos / w + dr, gc = pos % w + dc;
+        const int here = (gr >= 0 && gr < h && gc >= 0 && gc < w) ? grid[gr * w + gc] : outside;
+        if (here == id) val += Psum[(size_t)pos * H + c];
+    }
+    if (id == car_class) val += Dsum[(size_t)(hdr + cell) * H + c];
+    dWt[i] = val;
+}
+
+int64_t tj_encode_bwd_window_finish_scratch(const ic3_env* env, int H)
+{
+    const ic3_dims& d = env->dims;
+    const int hdr = env->tj.vocab_type ? 4 : 2;
+    return tj_win_plan(env, H).MBP ? (int64_t)(d.grid_h * d.grid_w + hdr + d.window * d.window + 1) * H : 0;
+}
+int tj_encode_bwd_window_finish_ordered(ic3_env* env, int H, float* dWt, float* dbias, float* work, float* scratch, hipStream_t s)
+{
+    const ic3_tj_cfg& c = env->tj;
+    const ic3_dims& d = env->dims;
+    const int hdr = c.vocab_type ? 4 : 2, npos = d.grid_h * d.grid_w, WW = d.window * d.window;
+    const EncWinPlan pl = tj_win_plan(env, H);
+    if (!pl.MBP) return fail(-38, "ic3_env_encode_backward_window_finish_ordered: this configuration has no window form");
+    const long long nP = (long long)npos * H, nD = (long long)(hdr + WW + 1) * H;
+    hipLaunchKernelGGL(enc_bwd_fold_kernel<8>, dim3((unsigned)((nP + nD + 255) / 256)), dim3(256), 0, s, work,
+                       work + (size_t)pl.nrg * npos * H, pl.nrg, nP, nD, scratch);
+    IC3_HIP(hipGetLastError());
+    const long long n = (long long)d.obs_dim * H + H;
+    hipLaunchKernelGGL(tj_encode_bwd_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, scratch + nP,
+                       env->d_grid, dWt, dbias, d.grid_h, d.grid_w, c.vision, d.vocab, d.vocab - 3, d.vocab - 1, H, hdr);
+    IC3_HIP(hipGetLastError());
+    return 0;
+}
+
 __global__ void set_i32_kernel(int32_t* p, int32_t v) { *p = v; }
 
 int tj_reset(ic3_env* env, hipStream_t s)

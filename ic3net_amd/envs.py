@@ -296,6 +296,25 @@ class _BatchedEnv(object):
                                                                ptr(self.encode_window_work(H)), stream()))
         return dwt, dbias
 
+    def encode_backward_window_finish_ordered(self, H, want_bias=True):
+        """encode_backward_window_finish with every sum in a fixed order (ic3_env_encode_backward_window_finish_ordered): the
+        same (dWt, dbias), identical run to run."""
+        self._require()
+        key = ('encw_fold', H)
+        if not hasattr(self, '_scratch'):
+            self._scratch = {}
+        if key not in self._scratch:
+            n = _lib.lib().ic3_env_encode_backward_window_finish_scratch(self._h, H)
+            if n <= 0:
+                check(int(n) if n < 0 else -38)
+            self._scratch[key] = torch.empty((n,), dtype=torch.float32, device=self.device)
+        dwt = torch.empty((self.obs_dim, H), dtype=torch.float32, device=self.device)
+        dbias = torch.empty((H,), dtype=torch.float32, device=self.device) if want_bias else None
+        check(_lib.lib().ic3_env_encode_backward_window_finish_ordered(self._h, H, ptr(dwt), ptr(dbias) if want_bias else None,
+                                                                      ptr(self.encode_window_work(H)), ptr(self._scratch[key]),
+                                                                      stream()))
+        return dwt, dbias
+
     def set_auto_reset(self, max_steps):
         """max_steps > 0: an env whose episode ends (episode_over, or max_steps steps played) starts its next episode
         inside the same step launch (ic3_env_set_auto_reset); 0: lock-step episodes (finished envs freeze)."""

@@ -513,6 +513,75 @@ def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_p
     check(_lib.lib().ic3_rnn_backward(env._h, C.byref(b), stream()))
 
 
+def mlp_backward_supported(env, H):
+    """ic3_mlp_backward_supported: the IC baseline's (models.MLP) window backward runs for this env handle at hid_size H."""
+    return bool(_lib.lib().ic3_mlp_backward_supported(env._h, int(H)))
+
+
+def mlp_backward_partials(Q, H):
+    """Rows of ic3_mlp_bptt.dbias_partials for a window of Q = T x R rows (ic3_mlp_backward_partials)."""
+    return int(_lib.lib().ic3_mlp_backward_partials(int(Q), int(H)))
+
+
+def mlp_backward_step(x1, h, dhead, w_heads, a2, dz, de, dbias_partials, accumulate=False):
+    """ic3_mlp_backward_step: the IC baseline's backward over Q independent rows in one launch — x1 (Q, H) holds e = affine1(obs)
+    on entry and tanh(e) on return, dz = (dhead . w_heads) * (1 - h^2), de = (dz . a2 + dz) * (1 - x1^2), column sums of dz into
+    dbias_partials (mlp_backward_partials(Q, H) rows).  Leading dims may be (T, R)."""
+    _need_cuda(h, "mlp_backward_step")
+    H = h.shape[-1]
+    Q = h.numel() // H
+    OT = dhead.shape[-1]
+    for v in (x1, h, dz, de):
+        assert v.is_contiguous() and v.numel() == Q * H and v.shape[-1] == H and v.dtype == torch.float32
+    assert dhead.is_contiguous() and dhead.numel() == Q * OT and dhead.dtype == torch.float32
+    assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and a2.is_contiguous() and tuple(a2.shape) == (H, H)
+    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (mlp_backward_partials(Q, H), H)
+    n = _lib.lib().ic3_mlp_backward_step(ptr(x1), ptr(h), ptr(dhead), ptr(w_heads), OT, ptr(a2), ptr(dz), ptr(de),
+                                         ptr(dbias_partials), int(bool(accumulate)), Q, H, stream())
+    return check(n)
+
+
+def mlp_backward(env, T, E, N, H, h, dhead, snaps, enc_wt, enc_bias, a2, w_heads, x1, dz, de, dbias_partials, loc_table=None,
+                 enc_first=True, enc_window=True, a2_grad=None, work=None):
+    """ic3_mlp_backward: the backward through a window of T recorded steps of the IC baseline (models.MLP) as one host call —
+    T encoder launches into the x1 ring, ONE launch over all T x R rows, the encoder's first stage over the de ring (enc_window,
+    or per step) and with a2_grad affine2's weight gradient over the window.  h (>= T, R, H) the state every step ended with,
+    dhead (T, R, OT), x1 / dz / de (T, R, H) the rings, dbias_partials (mlp_backward_partials(T * R, H), H) written."""
+    import ctypes as C
+    _need_cuda(h, "mlp_backward")
+    R = E * N
+    OT = dhead.shape[-1]
+    assert h.is_contiguous() and h.dtype == torch.float32 and tuple(h.shape[1:]) == (R, H) and h.shape[0] >= T
+    assert dhead.is_contiguous() and dhead.numel() == T * R * OT and dhead.dtype == torch.float32
+    assert snaps.is_contiguous() and snaps.dtype == torch.int32 and snaps.shape[0] >= T
+    for v in (x1, dz, de):
+        assert v.is_contiguous() and tuple(v.shape) == (T, R, H) and v.dtype == torch.float32
+    assert enc_wt.is_contiguous() and enc_wt.dtype == torch.float32 and tuple(enc_wt.shape) == (env.obs_dim, H)
+    assert enc_bias.is_contiguous() and enc_bias.numel() == H
+    assert a2.is_contiguous() and tuple(a2.shape) == (H, H) and w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H)
+    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (mlp_backward_partials(T * R, H), H)
+    b = _lib.MlpBptt()
+    b.struct_size = C.sizeof(b)
+    b.T, b.E, b.N, b.H, b.OT = T, E, N, H, OT
+    b.enc_first, b.enc_window = int(bool(enc_first)), int(bool(enc_window))
+    b.h, b.dhead, b.snaps = h.data_ptr(), dhead.data_ptr(), snaps.data_ptr()
+    b.snap_words = snaps.stride(0)
+    b.enc_wt, b.enc_bias = enc_wt.data_ptr(), enc_bias.data_ptr()
+    b.loc_table = loc_table.data_ptr() if loc_table is not None else None
+    b.a2, b.w_heads = a2.data_ptr(), w_heads.data_ptr()
+    b.x1, b.dz, b.de, b.dbias_partials = x1.data_ptr(), dz.data_ptr(), de.data_ptr(), dbias_partials.data_ptr()
+    b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
+    if a2_grad is not None:
+        assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
+        work = work if work is not None else dict()
+        n = int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H))
+        key = ('rnn_wgrad', str(h.device))
+        if key not in work or work[key].numel() < n:
+            work[key] = torch.empty((n,), dtype=torch.float32, device=h.device)
+        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), work[key].data_ptr()
+    check(_lib.lib().ic3_mlp_backward(env._h, C.byref(b), stream()))
+
+
 HEADS_GRAD_MAX_OT = 16      # ic3_heads_grad: at most 16 output columns (the heads' actions in total + the value)
 
 

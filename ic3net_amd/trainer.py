@@ -247,6 +247,11 @@ class Trainer(object):
                     self._rec.xh = torch.empty((T, E * N, ops.record_xh_width(knet.hid_size)), dtype=torch.float32, device=dev)
                 except torch.cuda.OutOfMemoryError:                # (the budget above is an estimate: recompute instead)
                     self._rec.gates = self._rec.xh = None
+            if self._record_h_fin(T, E * N):
+                try:
+                    self._rec.h_fin = torch.empty((T, E * N, args.hid_size), dtype=torch.float32, device=dev)
+                except torch.cuda.OutOfMemoryError:                # (no record of h: the per-step loop)
+                    self._rec.h_fin = None
         self._ones_comm = self._static['ones'] if args.comm_action_one else None
         self._zeros_comm = self._static['zeros']
         if self._use_graph() and self._graphs and getattr(self.policy_net, '_fc', None) is not None:
@@ -292,6 +297,21 @@ class Trainer(object):
         # allocator holds unused, half of it at most (the backward's own buffers, the graph pools and other ranks on the device
         # need room too); an allocation that fails anyway falls back to the recomputing backward (begin_episode)
         return T * R * (4 * H + ops.record_xh_width(H)) * 4 <= bptt.device_room(torch.cuda.current_device()) // 2
+
+    def _record_h_fin(self, T, R):
+        """Native update of the IC baseline (models.MLP): let every step launch of the recorded rollout store the hidden state it
+        ends with in the episode record (ic3_commnet_step's h_out), so the backward runs over the whole window in one launch
+        (bptt._backward_window_mlp) — where that path can run at all (bptt.mlp_window_wanted: hid 64 / 128, no padded twin, the
+        native loop on, the library's answer) and the buffer stays within half of what the device can still give."""
+        a = self.args
+        raw = getattr(self.env, 'env', None)
+        if raw is None or not bptt.mlp_window_wanted(a, self.policy_net, raw):
+            return False
+        # (only ic3_commnet_step writes h: not the launch chain of mega_policy=False, an autograd rollout or a foreign sampler)
+        if not getattr(a, 'mega_policy', True) or getattr(a, 'rollout_grad', False) or select_action is not _select_action_default \
+                or not self.policy_net.affine1.weight.is_cuda:
+            return False
+        return T * R * a.hid_size * 4 <= bptt.device_room(torch.cuda.current_device()) // 2
 
     def _rec_inplace(self):
         """The recorded rollout of a native update reads / writes (h, c) in the episode record (no copies) when every
@@ -596,9 +616,15 @@ class Trainer(object):
             e0, e1 = DispatchEvent(), DispatchEvent()
             raw.set_step_events(e0, e1)
             timer.append((e0, e1, t))
+        kw = dict()
+        rec = self._rec
+        if rec is not None and rec.h_fin is not None and rec.h_fin_n == t:   # (models.MLP's record: h of step t -> slot t)
+            kw['h_out'] = rec.h_fin[t]
         action_out, value = self.policy_net.step_env_commnet(
             raw, state, info, action=buf['action'][t], reward=buf['reward'][t], done=buf['done'][t], alive=buf['alive'][t],
-            is_completed=buf['is_completed'][t], obs=raw._obs if observe else None, out=self._static_out(t, state))
+            is_completed=buf['is_completed'][t], obs=raw._obs if observe else None, out=self._static_out(t, state), **kw)
+        if kw:
+            rec.h_fin_n = t + 1
         self._mega_last = True                                     # (the reset obs launch may be skipped: step 0 writes the rows)
         next_state = self.env._flatten_obs(raw._obs) if hasattr(self.env, '_flatten_obs') else raw._obs
         if raw.dims.kind == 2:                                     # TJ:244-247

@@ -216,6 +216,13 @@ int64_t ic3_env_encode_backward_window_work(const ic3_env* env, int H);
 int ic3_env_encode_backward_window(ic3_env* env, const int32_t* snaps, int64_t snap_words, int T, const float* grad_out, int ldg,
                                    int64_t step_stride, int H, float* work, int first, ic3_stream stream);
 int ic3_env_encode_backward_window_finish(ic3_env* env, int H, float* dWt, float* dbias /* or NULL */, float* work, ic3_stream stream);
+/* ic3_env_encode_backward_window_finish with every sum in a fixed order and no atomic: dWt / dbias are identical run to run (the
+ * plain finish adds into dWt with float atomics: the last bits move).  The partials are folded in partial order into `scratch`
+ * (ic3_env_encode_backward_window_finish_scratch floats; 0: no window form), then one thread per element of dWt gathers what lands
+ * on it in position order.  `work` is read, not changed: either finish may follow the other.  Used by ic3_mlp_backward's caller. */
+int64_t ic3_env_encode_backward_window_finish_scratch(const ic3_env* env, int H);
+int ic3_env_encode_backward_window_finish_ordered(ic3_env* env, int H, float* dWt, float* dbias /* or NULL */, float* work,
+                                                  float* scratch, ic3_stream stream);
 
 /* Synchronising: returns -EINVAL if any step since the last check saw an out-of-range action. */
 int ic3_env_check(ic3_env* env, ic3_stream stream);
@@ -523,6 +530,55 @@ int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream);
 size_t ic3_rnn_weight_grad_scratch_floats(long long Q, int H);
 int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const float* row_live /* or NULL */, long long Q, int H, float* dA2,
                         int accumulate, float* scratch, ic3_stream stream);
+
+/* The backward through a window of T recorded steps of the IC baseline (models.py:23-34, models.MLP: e = affine1(obs),
+ * x1 = tanh(e), h = tanh(affine2(x1) + x1), heads and value on h) as ONE host call.  No state crosses a step, so the window is
+ * Q = T x R independent rows: T x ic3_env_encode_at (e of every snapshot into the slots of the x1 ring), then ONE launch over all
+ * Q rows:
+ *   x1 = tanh(e) -> over e;  dz = (d . W_heads)(1 - h^2) -> dz;  de = (dz . A2 + dz)(1 - x1^2) -> de;  column sums of dz
+ *   -> dbias_partials
+ * (A2 = affine2.weight, on the fp32 matrix instruction; `+ dz`: the skip), then the encoder's first stage over the de ring — in one
+ * launch (enc_window != 0: ic3_env_encode_backward_window, finish with ic3_env_encode_backward_window_finish or, for gradients
+ * identical run to run, its _ordered form) or per step
+ * (ic3_env_encode_backward_accumulate, finish with ic3_env_encode_backward_finish) — and, with a2_grad,
+ * ic3_rnn_weight_grad(dz, x1, NULL, Q, H, a2_grad, ...).  Nothing runs on the host between the launches.  The caller adds the
+ * partials' sum to affine2.bias, takes affine1.weight / affine1.bias from the encoder's finish call (its dbias is the column sum of
+ * de) and runs ic3_heads_grad.
+ *   h [T][R][H]: the hidden state every step ended with (ic3_commnet_step's h_out);  dhead [T][R][OT] (OT <= 16);  snaps: T
+ *   snapshots, snap_words int32 apart;  enc_wt / enc_bias / loc_table: ic3_env_encode_at's Wt, bias, loc_table (or NULL);
+ *   x1, dz, de [T][R][H]: the rings (written);  dbias_partials [ic3_mlp_backward_partials(T * R, H)][H] (written);  enc_work as the
+ *   encoder form asks, enc_first != 0: this window starts the accumulation;  a2_grad [H][H] ADDED to (or NULL: no weight
+ *   gradient here), wgrad_scratch ic3_rnn_weight_grad_scratch_floats(T * R, H) floats.
+ * No float atomics: the rings, the partials and a2_grad are identical run to run.  hid_size 64 / 128 and OT <= 16, -ENOSYS otherwise.
+ * ic3_mlp_backward_supported(env, H): 1 when the call can run (hid_size 64 / 128, the encoder backward in its partial-sums form).
+ * ic3_mlp_backward_step: the launch alone over Q rows (64-bit row offsets: Q x H x 4 may pass 4 GB) — x1_inout holds e on entry
+ * and x1 on return; returns the number of partials written (accumulate == 0) or added to, ic3_mlp_backward_partials(Q, H). */
+typedef struct ic3_mlp_bptt {
+    uint32_t struct_size;   /* sizeof(ic3_mlp_bptt) of the caller's header (checked first: -EINVAL on mismatch) */
+    int32_t T, E, N, H, OT;
+    int32_t enc_first, enc_window;
+    const float* h;
+    const float* dhead;
+    const int32_t* snaps;
+    int64_t snap_words;
+    const float* enc_wt;
+    const float* enc_bias;
+    const float* loc_table;
+    const float* a2;
+    const float* w_heads;
+    float* x1;
+    float* dz;
+    float* de;
+    float* dbias_partials;
+    float* enc_work;
+    float* a2_grad;
+    float* wgrad_scratch;
+} ic3_mlp_bptt;
+int ic3_mlp_backward_supported(const ic3_env* env, int H);
+int ic3_mlp_backward_partials(long long Q, int H);
+int ic3_mlp_backward_step(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT, const float* a2,
+                          float* dz, float* de, float* dbias_partials, int accumulate, long long Q, int H, ic3_stream stream);
+int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream);
 /* The weight / bias gradient of the heads + value head over a whole episode in one pass (trainer.py:128-225 through
  * comm.py:228,239): dW [OT][H] += sum_m d[m][o] h[m][c], db [OT] += sum_m d[m][o] over the M = steps x rows pairs
  * (d [M][OT], h [M][H]: h_t of every step, i.e. the recorded hidden states shifted by one step).  scratch:
