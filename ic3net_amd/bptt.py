@@ -214,7 +214,8 @@ def loss_gradients(args, batch, records=None):
     episode_masks = torch.stack(batch.episode_mask)
     episode_mini_masks = torch.stack(batch.episode_mini_mask)
     out_rows = _recorded_out(records, T) if (rewards.is_cuda and bool(getattr(args, 'fused_loss', True))) else None
-    if out_rows is not None and len(batch.action_out[0]) <= 4 and rewards.dtype == torch.float32:
+    # (ic3_loss_gradients keeps a transition's [logits | value] row in 16 registers: wider rows take the tensor program)
+    if out_rows is not None and len(batch.action_out[0]) <= 4 and out_rows.shape[-1] <= 16 and rewards.dtype == torch.float32:
         actions = torch.stack(batch.action).reshape(T, -1, E * n)             # (T, heads, R) int32
         alive_masks = torch.stack([m['alive_mask'] for m in batch.misc]).reshape(T, E * n)
         live = torch.stack([m['live'] for m in batch.misc])                   # (T, E)

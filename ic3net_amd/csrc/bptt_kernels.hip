@@ -647,18 +647,20 @@ namespace ic3 {
 struct BpttSide {
     hipStream_t stream = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
+    bool ready = false;
 };
 static BpttSide* bptt_side()
 {
-    static BpttSide side[64];
+    static BpttSide side[65];                                    // (slot 0: device -1, the host build's stand-in runtime)
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    BpttSide& sd = side[dev];
-    if (!sd.stream) {
-        if (hipStreamCreateWithFlags(&sd.stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&sd.join, hipEventDisableTiming) != hipSuccess)
+    if (hipGetDevice(&dev) != hipSuccess || dev < -1 || dev >= 64) return nullptr;
+    BpttSide& sd = side[dev + 1];
+    if (!sd.ready) {
+        if (!sd.stream && hipStreamCreateWithFlags(&sd.stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
+        if ((!sd.fork && hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) != hipSuccess) ||
+            (!sd.join && hipEventCreateWithFlags(&sd.join, hipEventDisableTiming) != hipSuccess))
             return nullptr;
+        sd.ready = true;
     }
     return &sd;
 }
@@ -690,6 +692,10 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
     if (!b->comm_zero && (!b->c_weight || !b->dcw_partials)) return fail(-22, "ic3_bptt_backward: C.weight and its partials");
     if (b->dxh_step && (b->dxh_step < (long long)E * N * 2 * H || ic3_env_encode_backward_window_work(env, H) <= 0))
         return fail(-22, "ic3_bptt_backward: dxh_step >= E * N * 2 * hid_size, on a configuration with ic3_env_encode_backward_window");
+    // (the loop runs in place on the record: what a step's launches would refuse is refused here, before the first one)
+    if (b->detach_gap > 0 && b->row_keep)
+        return fail(-22, "ic3_bptt_backward: detach_gap > 0 with row_keep (a detached step has no dc for row_keep to scale: lock-step "
+                         "windows carry detach_gap, collection-mode windows row_live / row_keep)");
     const long long R = (long long)E * N;
     hipStream_t s = (hipStream_t)stream;
     // Two chains: the steps of envs [0, E1) and [E1, E) are independent until the weight gradients are summed, so with
@@ -698,12 +704,22 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
     // together to be per step or behind the loop: the ring of input gradients (the encoder's stage 1 behind the loop).
     const int E1 = (b->two_chains && b->dxh_step) ? ic3_bptt_first_chain_envs(E, N) : E;
     const int nch = E1 < E ? 2 : 1;
+    if ((long long)std::max(E1, E - E1) * N * 4 * H * 4 >= (1ll << 32))
+        return fail(-22, "ic3_bptt_backward: a chain's rows * 4 * hid_size floats must stay below 4 GB (the gate launch's 32-bit buffer "
+                         "offsets)");
     BpttSide* side = nch == 2 ? bptt_side() : nullptr;
     if (nch == 2 && !side) return fail(-12, "ic3_bptt_backward: no second stream");
     if (nch == 2) {
         IC3_HIP(hipEventRecord(side->fork, s));
         IC3_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
     }
+    // an error behind the fork still joins the second stream: the caller's stream must not run ahead of launches that read its buffers
+    auto join = [&](int rc) {
+        if (nch == 2 && (hipEventRecord(side->join, side->stream) != hipSuccess || hipStreamWaitEvent(s, side->join, 0) != hipSuccess) &&
+            rc >= 0)
+            return fail(-5, "ic3_bptt_backward: joining the second stream failed");
+        return rc;
+    };
     int enc_first = b->enc_first;
     for (int t = T - 1; t >= 0; --t) {
         for (int ch = 0; ch < nch; ++ch) {
@@ -718,33 +734,32 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
             const bool detached = b->detach_gap > 0 && (t + 1) % b->detach_gap == 0;
             float* g = b->gates + ((size_t)t * R + r0) * 4 * H;
             float* dxh = b->dxh + (size_t)t * (size_t)b->dxh_step + r0 * 2 * H;
-            if (b->gate_events && ch == 0) IC3_HIP(hipEventRecord((hipEvent_t)b->gate_events[2 * t], sc));
+            if (b->gate_events && ch == 0 && hipEventRecord((hipEvent_t)b->gate_events[2 * t], sc) != hipSuccess)
+                return join(fail(-5, "ic3_bptt_backward: hipEventRecord of a gate event failed"));
             int rc = ic3_lstm_gates_backward_given(g, nullptr, 0, nullptr, b->lstm_wp3_bwd, b->cs + ((size_t)t * R + r0) * H,
                                                    detached ? nullptr : dh, detached ? nullptr : dc, g,
                                                    dc, b->dbias_partials + (r0 / 64) * 4 * H, 1, dxh,
                                                    b->row_live ? b->row_live + (size_t)t * R + r0 : nullptr,
                                                    b->row_keep ? b->row_keep + (size_t)t * R + r0 : nullptr,
                                                    b->dhead + ((size_t)t * R + r0) * b->OT, b->w_heads, b->OT, (int)Rc, H, scv);
-            if (rc < 0) return rc;
-            if (b->gate_events && ch == 0) IC3_HIP(hipEventRecord((hipEvent_t)b->gate_events[2 * t + 1], sc));
+            if (rc < 0) return join(rc);
+            if (b->gate_events && ch == 0 && hipEventRecord((hipEvent_t)b->gate_events[2 * t + 1], sc) != hipSuccess)
+                return join(fail(-5, "ic3_bptt_backward: hipEventRecord of a gate event failed"));
             const float* out_scale = (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R + r0 : nullptr;
             float* dcw = b->dcw_partials;
             if (dcw && ch) dcw += (size_t)ic3_comm_backward_partials(E1, N) * H * H;
             rc = ic3_comm_backward(dxh, 2 * H, b->hs + ((size_t)t * R + r0) * H, (b->alive && b->alive[t]) ? b->alive[t] + r0 : nullptr,
                                    (b->gate && b->gate[t]) ? b->gate[t] + r0 : nullptr, b->c_weight, out_scale, dh, dcw, 1, Ec, N, H,
                                    b->mode_avg, b->comm_zero, scv);
-            if (rc < 0) return rc;
+            if (rc < 0) return join(rc);
         }
         if (b->dxh_step) continue;                               // (the encoder's first stage: once, behind the loop)
         int rc = ic3_env_encode_backward_accumulate(env, b->snaps + (size_t)t * b->snap_words, b->dxh, 2 * H, H, b->enc_work,
                                                     enc_first, stream);
-        if (rc < 0) return rc;
+        if (rc < 0) return join(rc);
         enc_first = 0;
     }
-    if (nch == 2) {
-        IC3_HIP(hipEventRecord(side->join, side->stream));
-        IC3_HIP(hipStreamWaitEvent(s, side->join, 0));
-    }
+    if (const int rc = join(0); rc < 0) return rc;
     if (b->dxh_step)
         return ic3_env_encode_backward_window(env, b->snaps, b->snap_words, T, b->dxh, 2 * H, b->dxh_step, H, b->enc_work, enc_first,
                                               stream);

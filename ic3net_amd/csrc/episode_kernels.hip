@@ -334,6 +334,8 @@ int ic3_loss_gradients(const float* out, const int32_t* action, const float* ret
         if (sz[k] < 1) return fail(-22, "ic3_loss_gradients: empty action head");
         a.OT += sz[k];
     }
+    // (the kernel keeps a transition's row in registers: float o[16], d[16])
+    if (a.OT > 16) return fail(-22, "ic3_loss_gradients: 1 + sum(head_sizes) = " + std::to_string(a.OT) + " output columns, at most 16");
     a.out = out;
     a.action = action;
     a.returns = returns;

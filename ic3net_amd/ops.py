@@ -250,11 +250,13 @@ def lstm_gates_backward_given(gates, c_prev, dh, dc, dgates, dc_prev, dbias_part
     rollout's launch stored them: envs.set_record_out) — no gate product.  xh + h_prev: h_prev is copied into the h half of xh;
     lstm_wp3_bwd + dxh: [d inp | d h_prev] in the same launch.  row_live / row_keep (R,) float32 (collection mode): c_prev and
     the copied h_prev times row_live, dc times row_keep, per row.  dgates may be `gates` itself (in place).  dhead (R, OT) +
-    w_heads (OT, H): dh + dhead @ w_heads is what the cell sees (the heads' share of dL/dh_t, folded in)."""
+    w_heads (OT, H): dh + dhead @ w_heads is what the cell sees (the heads' share of dL/dh_t, folded in).  dh and / or dc None:
+    zeros (a detach point of the recurrence; no buffer is read) — dh None needs dhead, row_keep needs dc."""
     _need_cuda(gates, "lstm_gates_backward_given")
     R, H = c_prev.shape
-    for t in (gates, c_prev, dh, dgates, dc_prev):
+    for t in (gates, c_prev, dgates, dc_prev) + tuple(v for v in (dh, dc) if v is not None):
         assert t.is_contiguous() and t.dtype == torch.float32
+    assert dh is not None or dhead is not None      # (dh None = zeros: a detach point, the heads' share alone reaches the cell)
     assert tuple(gates.shape) == (R, 4 * H) and tuple(dgates.shape) == (R, 4 * H)
     tiles = (R + 63) // 64
     if dbias_partials is not None:

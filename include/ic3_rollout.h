@@ -308,7 +308,7 @@ int ic3_episode_finalize(const ic3_episode* ep, ic3_stream stream);
  * adv_scale (normalize_rewards: the caller's mean and 1 / std over the live entries; else 0 and 1).  d_out [T][E*N][OT] receives
  * dL/d[logits of every head | value] with the log-softmax folded in (gradients w.r.t. its input), L = action_loss + value_coeff *
  * value_loss - entr * entropy; sums [ic3_loss_gradients_partials(T, E*N)][3] doubles = per-workgroup partial sums of (action_loss,
- * value_loss, entropy): the caller adds them up. */
+ * value_loss, entropy): the caller adds them up.  1..4 heads, OT = 1 + sum(head_sizes) <= 16 (-EINVAL otherwise, nothing launched). */
 int ic3_loss_gradients_partials(long long T, long long R);
 int ic3_loss_gradients(const float* out, const int32_t* action, const float* returns, const float* alive_mask, const float* live,
                        const int32_t* head_sizes, int nheads, float adv_shift, float adv_scale, float entr, float value_coeff,
@@ -437,7 +437,11 @@ int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const f
  *   [ic3_comm_backward_partials][H][H] are ADDED to (zero them before the first window);  enc_work as
  *   ic3_env_encode_backward_accumulate, enc_first != 0: this window starts the accumulation;  gate_events: see the struct.
  * ic3_bptt_backward_supported(env, H): 1 when every step can run (hid_size 64 / 128 / 256, <= 64 agents, the encoder backward in its
- * partial-sums form) — the loop overwrites the record as it goes, so ask first. */
+ * partial-sums form) — the loop overwrites the record as it goes, so ask first.
+ * Refused with -EINVAL BEFORE the first launch (the record is untouched): detach_gap > 0 together with row_keep (a detached step hands
+ * the gate launch no dc for row_keep to scale — lock-step windows carry detach_gap, collection-mode windows the row factors), and a
+ * chain of envs whose rows * 4 * hid_size floats reach 4 GB (the gate launch's 32-bit buffer offsets; with two_chains each chain
+ * counts for itself).  An error of a launch inside the loop still joins the library's second stream before it is returned. */
 typedef struct ic3_bptt {
     uint32_t struct_size;   /* sizeof(ic3_bptt) of the caller's header (checked: -EINVAL on mismatch) */
     int32_t T, E, N, H, OT;

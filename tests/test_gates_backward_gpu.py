@@ -273,3 +273,47 @@ def test_weight_gradient_of_a_window_in_one_launch(H, T, R, live, split):
     tol = 2e-6 * (T * R) ** 0.5 * 16
     assert float((outs[0].double() - want).abs().max()) <= tol
     assert torch.equal(outs[0], outs[1])
+
+
+def _gate_shapes():
+    import bptt_window_ref as ref
+    return ref.GATE_SHAPES
+
+
+@pytest.mark.parametrize("OT", [1, 6, 16])
+@pytest.mark.parametrize("H,R", _gate_shapes())
+def test_gates_backward_given_forms_of_the_window(H, R, OT):
+    """ic3_lstm_gates_backward_given at hid 64 / 128 in every form ic3_bptt_backward issues it (bptt_window_ref.GATE_FORMS): the
+    collection-mode cuts on / off, dh / dc / both None (a detach point; the heads' share alone reaches the cell), in place (dgates over
+    the gates, dc_prev over dc), accumulating onto non-zero partial rows — dgates / dc_prev within 2e-6 and dxh within 6e-6 of the
+    float64 closed form, every partial row's increment; then the copy of h_prev times row_live into the h half of xh.  The host
+    twin is tests/test_host_gates_backward_cpu.py."""
+    import numpy as np
+    import bptt_window_ref as ref
+    from ic3net_amd import ops
+    s = ref.make_gate_step(1000 * H + 10 * R + OT, H, R, OT)
+    d = {k: torch.from_numpy(v).cuda() for k, v in s.items() if isinstance(v, np.ndarray)}
+    wb3 = ops.policy_pack_split_bwd(d['w_ih'], d['w_hh'])
+    tiles = (R + 63) // 64
+    num = lambda v: v.double().cpu().numpy()
+    for form in ref.GATE_FORMS:
+        want_dg, want_dc, want_dx, want_rows = ref.gate_step_reference(s, form)
+        rec = d['gates'].clone()
+        dc_io = d['dc'].clone() if form['dc'] else torch.full((R, H), float('nan'), device='cuda')
+        parts = d['parts0'].clone()
+        dxh = torch.full((R, 2 * H), float('nan'), device='cuda')
+        n = ops.lstm_gates_backward_given(rec, d['c_prev'], d['dh'] if form['dh'] else None, dc_io if form['dc'] else None, rec, dc_io,
+                                          parts, True, lstm_wp3_bwd=wb3, dxh=dxh, row_live=d['live'] if form['cut'] else None,
+                                          row_keep=d['keep'] if (form['cut'] and form['dc']) else None, dhead=d['dhead'],
+                                          w_heads=d['w_heads'])
+        assert n == tiles, form
+        assert np.abs(num(rec) - want_dg).max() <= 2e-6 * max(1.0, np.abs(want_dg).max()), form
+        assert np.abs(num(dc_io) - want_dc).max() <= 2e-6 * max(1.0, np.abs(want_dc).max()), form
+        assert np.abs(num(dxh) - want_dx).max() <= 6e-6 * max(1.0, np.abs(want_dx).max()), form
+        np.testing.assert_allclose(num(parts) - s['parts0'], want_rows, rtol=1e-5, atol=1e-4, err_msg=str(form))
+    wide = torch.full((R, 2 * H + 4), float('nan'), device='cuda')
+    xh = wide[:, :2 * H]
+    dg, dcp = torch.full((R, 4 * H), float('nan'), device='cuda'), torch.full((R, H), float('nan'), device='cuda')
+    ops.lstm_gates_backward_given(d['gates'], d['c_prev'], d['dh'], d['dc'], dg, dcp, xh=xh, h_prev=d['h_prev'], row_live=d['live'])
+    assert torch.equal(wide[:, H:2 * H], d['h_prev'] * d['live'][:, None])
+    assert bool(torch.isnan(wide[:, :H]).all()) and bool(torch.isnan(wide[:, 2 * H:]).all()) and bool(torch.isfinite(dg).all())

@@ -302,6 +302,33 @@ def test_loss_gradients_in_one_launch_on_the_host(T, E, N, heads, entr, norm):
                                   C.c_float(0), C.c_float(vc), p(d_out), p(sums), T, E, N, None) == -22      # at most four heads
 
 
+def test_loss_gradients_refuses_more_than_16_output_columns():
+    """ic3_loss_gradients keeps a transition's row in 16 registers: one head of 16 actions (OT = 17) is -EINVAL with a reason, and
+    nothing is launched (d_out and the sums keep their NaNs); one head of 15 (OT = 16) runs."""
+    from host_abi_util import host_lib, p
+    lib = host_lib()
+    T, E, N = 2, 3, 2
+    R = E * N
+    rng = np.random.default_rng(0)
+    for A, want in ((16, -22), (15, 0)):
+        OT = A + 1
+        z = rng.standard_normal((T, R, OT))
+        z[:, :, :A] -= np.log(np.exp(z[:, :, :A]).sum(2, keepdims=True))
+        out = z.astype(np.float32)
+        action = rng.integers(0, A, size=(T, 1, R)).astype(np.int32)
+        returns, alive, live = rng.standard_normal((T, R)).astype(np.float32), np.ones((T, R), np.float32), np.ones((T, E), np.float32)
+        d_out = np.full((T, R, OT), np.nan, np.float32)
+        sums = np.full((int(lib.ic3_loss_gradients_partials(T, R)), 3), np.nan, np.float64)
+        sizes = np.array([A], np.int32)
+        rc = lib.ic3_loss_gradients(p(out), p(action), p(returns), p(alive), p(live), p(sizes), 1, C.c_float(0), C.c_float(1),
+                                    C.c_float(0.01), C.c_float(0.02), p(d_out), p(sums), T, E, N, None)
+        assert rc == want
+        if want < 0:
+            assert b"at most 16" in lib.ic3_last_error() and np.isnan(d_out).all() and np.isnan(sums).all()
+        else:
+            assert np.isfinite(d_out).all() and np.isfinite(sums).all()
+
+
 @pytest.mark.parametrize("T,E,N,gamma,ratio", [(9, 7, 3, 1.0, 0.0), (12, 30, 10, 0.9, 0.5), (5, 3, 64, 1.0, 1.0)])
 def test_returns_scan_on_the_host(T, E, N, gamma, ratio):
     """ic3_returns_scan == the loop of /root/reference/trainer.py:162-171 (float64)."""

@@ -986,6 +986,50 @@ def test_losses_and_their_gradients_in_one_launch_equal_the_tensor_program(wl, n
     assert float((d1 - d0).abs().max()) <= 1e-6 * max(1.0, float(d0.abs().max()))
 
 
+@pytest.mark.parametrize("A,fused", [(15, True), (16, False)])
+def test_a_policy_output_wider_than_16_columns_takes_the_tensor_program(A, fused):
+    """bptt.loss_gradients on a synthetic batch with one head of A actions: 16 output columns go through ic3_loss_gradients, 17 (more
+    than the launch keeps in registers) through the tensor program — the same losses and d_out as with args.fused_loss = False."""
+    import argparse
+    from types import SimpleNamespace
+    from ic3net_amd import bptt, ops
+    T, E, N = 3, 5, 2
+    R, OT = E * N, A + 1
+    gen = torch.Generator(device='cuda').manual_seed(A)
+    rn = lambda *s: torch.randn(*s, device='cuda', generator=gen)
+    logp = torch.log_softmax(rn(T, E, N, A), 3)
+    value = rn(T, E, N)
+    out = torch.cat([logp, value.unsqueeze(3)], 3).reshape(T, R, OT).contiguous()
+    action = torch.randint(0, A, (T, 1, E, N), device='cuda', generator=gen, dtype=torch.int32)
+    live = torch.ones(T, E, device='cuda')
+    batch = SimpleNamespace(reward=list(rn(T, E, N)), episode_mask=list(torch.ones(T, E, 1, device='cuda')),
+                            episode_mini_mask=list(torch.ones(T, E, N, device='cuda')), action=list(action),
+                            action_out=[[logp[t]] for t in range(T)], value=[value[t].reshape(R, 1) for t in range(T)],
+                            misc=[dict(alive_mask=torch.ones(E, N, device='cuda'), live=live[t]) for t in range(T)])
+    a = argparse.Namespace(nagents=N, gamma=0.9, mean_ratio=0.5, normalize_rewards=False, entr=0.01, value_coeff=0.02,
+                           advantages_per_action=False, naction_heads=[A], fused_loss=True)
+    recs = [SimpleNamespace(out=out, out_n=T, n=T)]
+    calls = []
+    orig = ops.loss_gradients
+
+    def spy(*args, **kw):
+        calls.append(1)
+        return orig(*args, **kw)
+    ops.loss_gradients = spy
+    try:
+        s1, d1 = bptt.loss_gradients(a, batch, recs)
+        assert bool(calls) == fused
+        a.fused_loss = False
+        s0, d0 = bptt.loss_gradients(a, batch, recs)
+        assert len(calls) == int(fused)
+    finally:
+        ops.loss_gradients = orig
+    for k in ("action_loss", "value_loss", "entropy"):
+        assert abs(s1[k] - s0[k]) <= 1e-6 * max(1.0, abs(s0[k])), (k, s1[k], s0[k])
+    assert d1.shape == d0.shape == (T, R, OT)
+    assert float((d1 - d0).abs().max()) <= 1e-6 * max(1.0, float(d0.abs().max()))
+
+
 def test_native_update_is_not_taken_where_it_does_not_apply():
     """Round-3 advisor findings: with args.auto_reset the recorded (h, c) / masks of a restarted env belong to the previous
     episode — since round 5 the explicit backward CUTS there (collection mode, test_collection_mode_grad_matches_reference)
