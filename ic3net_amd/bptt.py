@@ -411,6 +411,17 @@ def backward_episode(args, net, raw, rec, d_out, acc, carry=None):
     return (dh_rec, dc_rec)       # dL/d(h, c) entering the record's first slot (collection mode: the previous window's carry)
 
 
+def _dhead_rows(d_out, T):
+    """d_out's first T steps as one contiguous block: a view where they are one already."""
+    d = d_out[:T]
+    return d if d.is_contiguous() else d.contiguous()
+
+
+def _enc_window(args, raw, H):
+    """The sparse encoder's backward runs in its window form: asked for (args.enc_window, on by default) and there for this env."""
+    return bool(getattr(args, 'enc_window', True)) and raw.encode_window_work(H) is not None
+
+
 def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
     """backward_episode on recorded gates through ic3_bptt_backward (csrc/bptt_kernels.hip).  Per step, last to first:
       ic3_lstm_gates_backward_given   cell derivative from the recorded gates, IN PLACE (dgates over the gates), dL/dh_t taking the
@@ -432,8 +443,7 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
     dh_rec, dc_rec = zeros(R, H), zeros(R, H)
     # the per-step input gradients: a ring of T of them when the encoder's backward has its window form (one launch over all the
     # window's states behind the loop instead of one per step) and the memory is there, else one buffer
-    ring = bool(getattr(args, 'enc_window', True)) and raw.encode_window_work(H) is not None and \
-        _ring_fits(dev, T * R * 2 * H * 4)
+    ring = _enc_window(args, raw, H) and _ring_fits(dev, T * R * 2 * H * 4)
     dxh = torch.empty((T, R, 2 * H) if ring else (R, 2 * H), dtype=torch.float32, device=dev)
     bias_parts = zeros((R + 63) // 64, 4 * H)
     # two chains of launches (envs [0, E1) and [E1, E) on two streams): one fills the ragged last round of the other's launches
@@ -911,10 +921,10 @@ def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
     parts = torch.zeros((ops.rnn_backward_partials(R, H), H), dtype=torch.float32, device=dev)
     cuts = _Cuts(args, rec, T, E, N, dev)
     cuts.carry_in(carry, dh, at_border=True)
-    dhead = d_out[:T] if d_out[:T].is_contiguous() else d_out[:T].contiguous()
+    dhead = _dhead_rows(d_out, T)
     h_last = None if rec.h_last_is_slot(T) else rec.h_last
     w_heads, a2 = _baseline_w_heads(net), net.affine2.weight.detach().contiguous()
-    enc_window = bool(getattr(args, 'enc_window', True)) and raw.encode_window_work(H) is not None
+    enc_window = _enc_window(args, raw, H)
     with _heads_grad_beside(args, rec, d_out, acc, T, R, H):
         ops.rnn_backward(raw, T, E, N, H, rec.hs, dhead, rec.snaps, a2, w_heads, dh, dz, parts, h_last=h_last,
                          detach_gap=cuts.gap, row_live=cuts.live_flat, row_keep=cuts.keep_flat, enc_first=True,
@@ -971,10 +981,10 @@ def _backward_window_mlp(args, net, raw, rec, d_out, acc):
     dev = rec.h_fin.device
     x1, dz, de = (torch.empty((T, R, H), dtype=torch.float32, device=dev) for _ in range(3))
     parts = torch.empty((ops.mlp_backward_partials(T * R, H), H), dtype=torch.float32, device=dev)
-    dhead = d_out[:T] if d_out[:T].is_contiguous() else d_out[:T].contiguous()
+    dhead = _dhead_rows(d_out, T)
     wt = net.affine1.weight.detach().t().contiguous()
     w_heads, a2 = _baseline_w_heads(net), net.affine2.weight.detach().contiguous()
-    enc_window = bool(getattr(args, 'enc_window', True)) and raw.encode_window_work(H) is not None
+    enc_window = _enc_window(args, raw, H)
     with _heads_grad_beside(args, rec, d_out, acc, T, R, H):
         ops.mlp_backward(raw, T, E, N, H, rec.h_fin, dhead, rec.snaps, wt, net.affine1.bias.detach().contiguous(), a2, w_heads,
                          x1, dz, de, parts, enc_first=True, enc_window=enc_window, a2_grad=acc['a2_w'],

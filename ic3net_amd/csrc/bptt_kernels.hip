@@ -14,6 +14,18 @@
 //   ic3_bptt_backward     the loop over a window's steps, last to first, as ONE host call: cell derivative + input gradient
 //                         (ic3_lstm_gates_backward_given, the heads' share of dL/dh folded in) -> ic3_comm_backward -> the sparse
 //                         encoder's backward stage 1 — three launches per step, no host work between them.
+//   ic3_rnn_tanh_backward_step / ic3_rnn_backward   the IC / IRIC baselines' tanh recurrence: one launch per recorded step
+//                         (rnn_tanh_bwd_kernel), and the loop over a window's steps as one host call.
+//   ic3_rnn_weight_grad   ONE launch per window: dA2 += dz^T . (row_live h_prev) over all T x R rows (rnn_wgrad_kernel).
+//   ic3_mlp_backward_step / ic3_mlp_backward   the IC baseline (models.MLP): a window is T x R independent rows, ONE launch over
+//                         all of them (mlp_bwd_kernel), and the window as one host call.
+// and what sizes their buffers / says whether they run: ic3_comm_backward_partials, ic3_lstm_weight_grad_scratch_floats,
+// ic3_bptt_backward_supported, ic3_bptt_first_chain_envs, ic3_rnn_ / ic3_mlp_backward_partials and _supported,
+// ic3_rnn_weight_grad_scratch_floats.
+// What these share exists once.  Device: bp_load1 / bp_load4 / bp_store4 (buffer access, the wave-uniform part in `soff`), bp_zero,
+// bp_kslice (a weight-gradient workgroup's K slice), TanhTile<H> (the tile machine of the two tanh kernels).  Host: launch_kernel
+// (ic3_common.hpp), tanh_partials / tanh_supported, wgrad_plan / wgrad_reduce (the K slices and their fixed-order sum), window_open
+// (a window descriptor's opening checks), encoder_tail (the sparse encoder's stage 1 behind a window's steps).
 //
 // Arithmetic: v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation — the library products these replace ran on
 // the same instruction).  Layouts as gates_bwd.hip: accumulator register `reg` of a 32 x 32 block <-> block row
@@ -48,13 +60,40 @@ __device__ __forceinline__ float bp_load1(__amdgpu_buffer_rsrc_t r, int voff, in
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
-__device__ __forceinline__ bp_f32x4 bp_load4(__amdgpu_buffer_rsrc_t r, int voff)
+__device__ __forceinline__ bp_f32x4 bp_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff = 0)
 {
-    return __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
+    return __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+}
+__device__ __forceinline__ void bp_store4(bp_f32x4 v, __amdgpu_buffer_rsrc_t r, int voff, int soff = 0)   // (past the range: dropped)
+{
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, v), r, voff, soff, 0);
 }
 __device__ __forceinline__ void bp_mfma(bp_f32x16& acc, float x, float y)
 {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x, y, acc, 0, 0, 0);
+}
+template <int N>
+__device__ __forceinline__ void bp_zero(bp_f32x16* acc)        // acc[0 .. N) = 0
+{
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[n][i] = 0.0f;
+}
+
+// The K slice of a weight-gradient workgroup: rows [q0, q0 + nq) of the Q recorded ones (nq clipped to [0, rows_per_wg]: the
+// slices behind the last row are empty), staged KT rows at a time.
+struct KSlice {
+    long long q0, nq;
+    int nstages;
+};
+__device__ __forceinline__ KSlice bp_kslice(long long Q, int rows_per_wg, int KT)
+{
+    const long long q0 = (long long)blockIdx.x * rows_per_wg;
+    long long nq = Q - q0;
+    if (nq > rows_per_wg) nq = rows_per_wg;
+    if (nq < 0) nq = 0;
+    return KSlice{ q0, nq, (int)((nq + KT - 1) / KT) };
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -91,10 +130,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 3 : 1) void comm_bwd_kernel(con
     const int col = 32 * w + li;
     const int N = a.N;
     bp_f32x16 acc2[MB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc2[mb][i] = 0.0f;
+    bp_zero<MB>(acc2);
     const __amdgpu_buffer_rsrc_t rcw = bp_rsrc(a.cw, (long long)H * H * 4);
 
     for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
@@ -249,15 +285,13 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int wm = w & 1, wn = w >> 1;
     const int ny = blockIdx.y;
-    const long long q0 = (long long)blockIdx.x * a.rows_per_wg;
-    long long nq = a.Q - q0;
-    if (nq > a.rows_per_wg) nq = a.rows_per_wg;
-    if (nq < 0) nq = 0;
+    const KSlice sl = bp_kslice(a.Q, a.rows_per_wg, KT);
+    const long long q0 = sl.q0, nq = sl.nq;
+    const int nstages = sl.nstages;
     const __amdgpu_buffer_rsrc_t ri = bp_rsrc(a.inp + q0 * a.ldi, nq > 0 ? ((nq - 1) * a.ldi + H) * 4 : 0);
     const __amdgpu_buffer_rsrc_t rh = bp_rsrc(a.h + q0 * H, nq * H * 4);
     const __amdgpu_buffer_rsrc_t rd = bp_rsrc(a.dg + q0 * 4 * H + ny * DW, nq > 0 ? ((nq - 1) * 4 * H + DW) * 4 : 0);
     const __amdgpu_buffer_rsrc_t rl = bp_rsrc(a.row_live ? a.row_live + q0 : a.h, a.row_live ? nq * 4 : 0);
-    const int nstages = (int)((nq + KT - 1) / KT);
     // a thread stages the same (row-in-stage, column chunk) of every stage: X chunk i at row xrow + i * (NT / X4R)
     const int xrow = tid / X4R, xc4 = tid - xrow * X4R;
     const bool x_is_h = xc4 >= H / 4;
@@ -272,15 +306,14 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
 #pragma unroll
         for (int i = 0; i < XPT; ++i) {
             if (x_is_h) {
-                xr[i] = __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, xvoff + i * xstep, qb * H * 4, 0));
+                xr[i] = bp_load4(rh, xvoff + i * xstep, qb * H * 4);
                 if (a.row_live) xr[i] *= bp_load1(rl, (xrow + i * (NT / X4R)) * 4, qb * 4);
             } else {
-                xr[i] = __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, xvoff + i * xstep, qb * a.ldi * 4, 0));
+                xr[i] = bp_load4(ri, xvoff + i * xstep, qb * a.ldi * 4);
             }
         }
 #pragma unroll
-        for (int i = 0; i < DPT; ++i)
-            dr[i] = __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, dvoff + i * (NT / D4R) * 4 * H * 4, qb * 4 * H * 4, 0));
+        for (int i = 0; i < DPT; ++i) dr[i] = bp_load4(rd, dvoff + i * (NT / D4R) * 4 * H * 4, qb * 4 * H * 4);
     };
     auto stash = [&](int b) {
         bp_f32x4* X4 = reinterpret_cast<bp_f32x4*>(smem + b * SW);
@@ -291,12 +324,7 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
         for (int i = 0; i < DPT; ++i) D4[tid + i * NT] = dr[i];
     };
     bp_f32x16 acc[MB][NB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mb][nb][i] = 0.0f;
+    bp_zero<MB * NB>(&acc[0][0]);
     if (nstages > 0) {
         fetch(0);
         stash(0);
@@ -367,15 +395,13 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_split_kernel(const WGradArg
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int wm = w & 1, wn = w >> 1;
     const int ny = blockIdx.y;
-    const long long q0 = (long long)blockIdx.x * a.rows_per_wg;
-    long long nq = a.Q - q0;
-    if (nq > a.rows_per_wg) nq = a.rows_per_wg;
-    if (nq < 0) nq = 0;
+    const KSlice sl = bp_kslice(a.Q, a.rows_per_wg, KT);
+    const long long q0 = sl.q0, nq = sl.nq;
+    const int nstages = sl.nstages;
     const __amdgpu_buffer_rsrc_t ri = bp_rsrc(a.inp + q0 * a.ldi, nq > 0 ? ((nq - 1) * a.ldi + H) * 4 : 0);
     const __amdgpu_buffer_rsrc_t rh = bp_rsrc(a.h + q0 * H, nq * H * 4);
     const __amdgpu_buffer_rsrc_t rd = bp_rsrc(a.dg + q0 * 4 * H + ny * DW, nq > 0 ? ((nq - 1) * 4 * H + DW) * 4 : 0);
     const __amdgpu_buffer_rsrc_t rl = bp_rsrc(a.row_live ? a.row_live + q0 : a.h, a.row_live ? nq * 4 : 0);
-    const int nstages = (int)((nq + KT - 1) / KT);
     // X group g = tid + i NT: column g % XW, rows 8 (g / XW) .. + 7 of the stage; the D group: column tid % DW, k half tid / DW.
     // Lane part of every address in ONE VGPR (column + the group's k half), the stage / row part on the scalar ALU — an soffset
     // that depends on a VGPR, however uniform, costs a waterfall loop per load.  Which side of [inp | h] a wave stages is
@@ -426,12 +452,7 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_split_kernel(const WGradArg
         for (int p = 0; p < 3; ++p) f[3 * 2 * XW + (p * 2 + dkg) * DW + dcol] = pl[p];
     };
     bp_f32x16 acc[MB][NB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mb][nb][i] = 0.0f;
+    bp_zero<MB * NB>(&acc[0][0]);
     // Pipeline: at the top of iteration s the registers hold stage s + 1 (requested a whole iteration ago) and LDS buffer s & 1
     // holds stage s.  The iteration is ONE basic block — the split + stash of stage s + 1 and the 72 products of stage s
     // (independent work: different LDS buffers; the compiler interleaves them), then the loads of stage s + 2 — so that the vector
@@ -534,9 +555,7 @@ extern "C" int ic3_comm_backward(const float* dxh, int ldd, const float* h_prev,
     if (comm_zero) {                                             // no communication: the gate product's share alone
         const long long R = (long long)E * N, n4 = R * (H / 4);
         const int blocks = (int)std::min<long long>((n4 + 255) / 256, 4096);
-        hipLaunchKernelGGL(dh_copy_kernel, dim3(blocks), dim3(256), 0, s, dxh, ldd, out_scale, dh_out, R, H / 4);
-        IC3_HIP(hipGetLastError());
-        return 0;
+        return launch_kernel(dh_copy_kernel, dim3(blocks), dim3(256), 0, s, dxh, ldd, out_scale, dh_out, R, H / 4);
     }
     if (!h_prev || !c_weight || !dcw_partials) return fail(-22, "ic3_comm_backward: null argument");
     if (H != 64 && H != 128 && H != 256) return fail(-38, "ic3_comm_backward: hid_size 64 / 128 / 256");
@@ -547,36 +566,43 @@ extern "C" int ic3_comm_backward(const float* dxh, int ldd, const float* h_prev,
                          mode_avg, accumulate };
     const int grid = ic3_comm_backward_partials(E, N);
     const size_t lds = ((size_t)64 * (H + 4) + 128) * sizeof(float);
-    if (H == 256) {
-        // (one 512-thread workgroup per CU — dC's 8 accumulator blocks per wave live across the tiles — so the 512 workgroups of
-        //  a large chain run as two rounds)
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(comm_bwd_kernel<256>), lds));
-        hipLaunchKernelGGL((comm_bwd_kernel<256>), dim3(grid), dim3(512), lds, s, a);
-    } else if (H == 128) {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(comm_bwd_kernel<128>), lds));
-        hipLaunchKernelGGL((comm_bwd_kernel<128>), dim3(grid), dim3(256), lds, s, a);
-    } else {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(comm_bwd_kernel<64>), lds));
-        hipLaunchKernelGGL((comm_bwd_kernel<64>), dim3(grid), dim3(128), lds, s, a);
-    }
-    IC3_HIP(hipGetLastError());
-    return grid;     // rows of dcw_partials written
+    // (at 256 one 512-thread workgroup per CU — dC's 8 accumulator blocks per wave live across the tiles — so the 512 workgroups
+    //  of a large chain run as two rounds)
+    const auto kernel = H == 256 ? comm_bwd_kernel<256> : H == 128 ? comm_bwd_kernel<128> : comm_bwd_kernel<64>;
+    const int rc = launch_kernel(kernel, dim3(grid), dim3(2 * H), lds, s, a);
+    return rc < 0 ? rc : grid;     // rows of dcw_partials written
 }
 
 // ---- ic3_lstm_weight_grad ----------------------------------------------------------------------------------------------------
-static int wgrad_slices(long long Q, int H)
+// The K slices of a weight gradient over Q rows, `ny` workgroups per slice: two workgroups per CU, no slice under one 16-row
+// stage, `per` rows per slice (a multiple of 16).  fits: `per` rows of `row_floats` floats stay below 2 GB — the kernels' 32-bit
+// buffer offsets.
+struct WGradPlan {
+    int ks;
+    long long per;
+    bool fits;
+};
+static WGradPlan wgrad_plan(long long Q, int ny, long long row_floats)
 {
-    const int ny = 4 * H / 128;
-    int ks = 2 * ic3::bp_cus() / ny;                             // two workgroups per CU
+    int ks = 2 * ic3::bp_cus() / ny;
     const long long most = (Q + 15) / 16;
     if (ks > most) ks = (int)most;
-    return ks < 1 ? 1 : ks;
+    if (ks < 1) ks = 1;
+    const long long per = ((Q + ks - 1) / ks + 15) / 16 * 16;
+    return WGradPlan{ ks, per, per * row_floats * 4 < (1ll << 31) };
+}
+
+// dW (n floats) += / = the ks partials in `scratch`, summed in slice order; returns ks
+static int wgrad_reduce(const float* scratch, int ks, int n, float* dW, int accumulate, hipStream_t s)
+{
+    const int rc = ic3::launch_kernel(ic3::wgrad_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, scratch, ks, n, dW, accumulate);
+    return rc < 0 ? rc : ks;
 }
 
 extern "C" size_t ic3_lstm_weight_grad_scratch_floats(long long Q, int H)
 {
     if (Q <= 0 || (H != 64 && H != 128)) return 0;
-    return (size_t)wgrad_slices(Q, H) * 2 * H * 4 * H;
+    return (size_t)wgrad_plan(Q, 4 * H / 128, 0).ks * 2 * H * 4 * H;
 }
 
 extern "C" int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const float* dgates, const float* row_live,
@@ -586,41 +612,18 @@ extern "C" int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_pr
     if (!inp || !h_prev || !dgates || !dW || !scratch || Q <= 0) return fail(-22, "ic3_lstm_weight_grad: null argument");
     if (H != 64 && H != 128) return fail(-38, "ic3_lstm_weight_grad: hid_size 64 / 128");
     if (ldi < H || (ldi & 3)) return fail(-22, "ic3_lstm_weight_grad: ldi a multiple of 4, >= hid_size");
-    const int ks = wgrad_slices(Q, H);
-    long long per = (Q + ks - 1) / ks;
-    per = (per + 15) / 16 * 16;
-    if (per * (long long)std::max(ldi, 4 * H) * 4 >= (1ll << 31))
-        return fail(-22, "ic3_lstm_weight_grad: a K slice must stay below 2 GB per operand (32-bit buffer offsets)");
-    const WGradArgs a{ inp, h_prev, dgates, row_live, scratch, Q, ldi, (int)per };
+    const int ny = 4 * H / 128;
+    const WGradPlan pl = wgrad_plan(Q, ny, std::max(ldi, 4 * H));
+    if (!pl.fits) return fail(-22, "ic3_lstm_weight_grad: a K slice must stay below 2 GB per operand (32-bit buffer offsets)");
+    const WGradArgs a{ inp, h_prev, dgates, row_live, scratch, Q, ldi, (int)pl.per };
     hipStream_t s = (hipStream_t)stream;
-    if (split) {                                                 // exact bf16 split products (the rollout's arithmetic)
-        const size_t lds3 = (size_t)2 * 3 * 2 * (2 * H + 128) * 16;
-        if (H == 128) {
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_wgrad_split_kernel<128>), lds3));
-            hipLaunchKernelGGL((lstm_wgrad_split_kernel<128>), dim3(ks, 4), dim3(256), lds3, s, a);
-        } else {
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_wgrad_split_kernel<64>), lds3));
-            hipLaunchKernelGGL((lstm_wgrad_split_kernel<64>), dim3(ks, 2), dim3(256), lds3, s, a);
-        }
-        IC3_HIP(hipGetLastError());
-        const int n3 = 2 * H * 4 * H;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((n3 + 255) / 256), dim3(256), 0, s, scratch, ks, n3, dW, accumulate);
-        IC3_HIP(hipGetLastError());
-        return ks;
-    }
-    const size_t lds = (size_t)2 * 16 * (2 * H + 128) * sizeof(float);
-    if (H == 128) {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_wgrad_kernel<128>), lds));
-        hipLaunchKernelGGL((lstm_wgrad_kernel<128>), dim3(ks, 4), dim3(256), lds, s, a);
-    } else {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_wgrad_kernel<64>), lds));
-        hipLaunchKernelGGL((lstm_wgrad_kernel<64>), dim3(ks, 2), dim3(256), lds, s, a);
-    }
-    IC3_HIP(hipGetLastError());
-    const int n = 2 * H * 4 * H;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, scratch, ks, n, dW, accumulate);
-    IC3_HIP(hipGetLastError());
-    return ks;
+    // split: exact bf16 split products (the rollout's arithmetic), two stages of 3 planes x 2 k halves of 16-byte fragments;
+    // else the fp32 instruction on two stages of 16 rows
+    const auto kernel = split ? (H == 128 ? lstm_wgrad_split_kernel<128> : lstm_wgrad_split_kernel<64>)
+                              : (H == 128 ? lstm_wgrad_kernel<128> : lstm_wgrad_kernel<64>);
+    const size_t lds = split ? (size_t)2 * 3 * 2 * (2 * H + 128) * 16 : (size_t)2 * 16 * (2 * H + 128) * sizeof(float);
+    if (const int rc = launch_kernel(kernel, dim3(pl.ks, ny), dim3(256), lds, s, a); rc < 0) return rc;
+    return wgrad_reduce(scratch, pl.ks, 2 * H * 4 * H, dW, accumulate, s);
 }
 
 // ---- ic3_bptt_backward -------------------------------------------------------------------------------------------------------
@@ -664,6 +667,44 @@ static BpttSide* bptt_side()
     }
     return &sd;
 }
+
+// How a window call (`fn`, descriptor `B` = `sname`) opens: the struct_size handshake, T / E / N against the handle, what the
+// configuration must be (`supported`, else -38 with `needs`), the heads' width.  ot_enosys: more than 16 columns is -38 of its own.
+template <class B>
+static int window_open(const char* fn, const char* sname, const ic3_env* env, const B* b, int (*supported)(const ic3_env*, int),
+                       const char* needs, bool ot_enosys)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!env || !b) return fail(-22, f + "null argument");
+    if (b->struct_size != sizeof(B))
+        return fail(-22, f + sname + " has " + std::to_string(b->struct_size) + " bytes, this library's has " +
+                             std::to_string(sizeof(B)) + " (header / library version mismatch)");
+    if (b->T <= 0 || b->E <= 0 || b->N <= 0 || b->E != env->dims.E || b->N != env->dims.N)
+        return fail(-22, f + "T, E, N must be positive and E, N the handle's");
+    if (!supported(env, b->H)) return fail(-38, f + needs);
+    if (ot_enosys) {
+        if (b->OT < 1) return fail(-22, f + "OT >= 1");
+        if (b->OT > 16) return fail(-38, f + "at most 16 output columns");
+    } else if (b->OT < 1 || b->OT > 16) {
+        return fail(-22, f + "1 <= OT <= 16");
+    }
+    return 0;
+}
+
+// The sparse encoder's backward stage 1 behind a window's steps, over the T input gradients g + t * g_step: its window form (one
+// launch), or its per-step form, last step first (the order of the per-step loops), `enc_first` cleared after the first.
+static int encoder_tail(ic3_env* env, const int32_t* snaps, int64_t snap_words, int T, const float* g, int ldg, int64_t g_step,
+                        int H, float* work, int enc_first, bool window, ic3_stream stream)
+{
+    if (window) return ic3_env_encode_backward_window(env, snaps, snap_words, T, g, ldg, g_step, H, work, enc_first, stream);
+    for (int t = T - 1; t >= 0; --t) {
+        const int rc = ic3_env_encode_backward_accumulate(env, snaps + (size_t)t * snap_words, g + (size_t)t * g_step, ldg, H, work,
+                                                          enc_first, stream);
+        if (rc < 0) return rc;
+        enc_first = 0;
+    }
+    return 0;
+}
 }  // namespace ic3
 
 // envs [0, E1) run on the caller's stream, [E1, E) on the library's second stream (ic3_bptt.two_chains): E1 * N a multiple of 64,
@@ -677,15 +718,12 @@ extern "C" int ic3_bptt_first_chain_envs(int E, int N)
 extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream stream)
 {
     using namespace ic3;
-    if (!env || !b) return fail(-22, "ic3_bptt_backward: null argument");
-    if (b->struct_size != sizeof(ic3_bptt))
-        return fail(-22, "ic3_bptt_backward: ic3_bptt has " + std::to_string(b->struct_size) + " bytes, this library's has " +
-                             std::to_string(sizeof(ic3_bptt)) + " (header / library version mismatch)");
+    if (const int rc = window_open("ic3_bptt_backward", "ic3_bptt", env, b, ic3_bptt_backward_supported,
+                                   "hid_size 64 / 128 / 256, <= 64 agents, a grid whose encoder backward runs in its partial-sums form",
+                                   false);
+        rc < 0)
+        return rc;
     const int T = b->T, E = b->E, N = b->N, H = b->H;
-    if (T <= 0 || E <= 0 || N <= 0 || E != env->dims.E || N != env->dims.N)
-        return fail(-22, "ic3_bptt_backward: T, E, N must be positive and E, N the handle's");
-    if (!ic3_bptt_backward_supported(env, H)) return fail(-38, "ic3_bptt_backward: hid_size 64 / 128 / 256, <= 64 agents, a grid whose encoder backward runs in its partial-sums form");
-    if (b->OT < 1 || b->OT > 16) return fail(-22, "ic3_bptt_backward: 1 <= OT <= 16");
     if (!b->gates || !b->hs || !b->cs || !b->dhead || !b->snaps || !b->lstm_wp3_bwd || !b->w_heads || !b->dh || !b->dc || !b->dxh ||
         !b->dbias_partials || !b->enc_work)
         return fail(-22, "ic3_bptt_backward: null argument");
@@ -787,6 +825,76 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace ic3 {
 
+// The tile machine of rnn_tanh_bwd_kernel and mlp_bwd_kernel: the constants, the LDS layout, a thread's two coordinates and the
+// four pieces both kernels run unchanged.  What differs — the phase-0 arithmetic, what happens to the product, when the next
+// tile's rows are requested — stays in the kernels.
+template <int H>
+struct TanhTile {
+    static constexpr int NT = 4 * H, H4 = H / 4, LDA = H + 4, LDA4 = LDA / 4, CB = H / 32, RPP = NT / H4, PER = 64 / RPP;
+    static_assert(RPP * PER == 64 && NT / 64 == 2 * CB, "tile split");
+    // LDS in floats: A2 in fragment order | the tile's dz | W_heads | the tile's d rows
+    static constexpr int DZ_AT = H * H, WH_AT = DZ_AT + 64 * LDA, SD_AT = WH_AT + 16 * H;
+    static constexpr size_t LDS_BYTES = (size_t)(SD_AT + 64 * 16) * sizeof(float);
+    float* const smem;
+    const bp_f32x4* const Bf4;   // [H / 8][2][H] float4
+    float* const Dz;             // [64][LDA]
+    bp_f32x4* const Dz4;
+    float* const Wh;             // [16][H]
+    float* const Sd;             // [64][OT]
+    const int tid, li, lh;
+    const int cb, rb;            // the product: wave (rb, cb) = tile rows [32 rb, +32) x A2's columns [32 cb, +32)
+    const int c4, rg;            // phase 0, column sums: column chunk c4 of rows rg + RPP i
+
+    __device__ __forceinline__ explicit TanhTile(float* lds)
+        : smem(lds), Bf4(reinterpret_cast<const bp_f32x4*>(lds)), Dz(lds + DZ_AT), Dz4(reinterpret_cast<bp_f32x4*>(lds + DZ_AT)),
+          Wh(lds + WH_AT), Sd(lds + SD_AT), tid(threadIdx.x), li(threadIdx.x & 31), lh((threadIdx.x & 63) >> 5),
+          cb((threadIdx.x >> 6) % CB), rb((threadIdx.x >> 6) / CB), c4(threadIdx.x % H4), rg(threadIdx.x / H4)
+    {
+    }
+    // A2 -> fragment order, W_heads as it is (the caller's barrier behind it)
+    __device__ __forceinline__ void stage_weights(const float* a2, const float* w_heads, int OT) const
+    {
+        for (int i = tid; i < H * H; i += NT) {
+            const int k = i / H, col = i - k * H;
+            smem[(((k >> 3) * 2 + ((k >> 2) & 1)) * H + col) * 4 + (k & 3)] = a2[i];
+        }
+        for (int i = tid; i < OT * H; i += NT) Wh[i] = w_heads[i];
+    }
+    // v + d[row] . W_heads for the thread's 4 columns
+    __device__ __forceinline__ bp_f32x4 heads_share(bp_f32x4 v, int row, int OT) const
+    {
+        const bp_f32x4* const Wh4 = reinterpret_cast<const bp_f32x4*>(Wh);
+        for (int o = 0; o < OT; ++o) v += Sd[row * OT + o] * Wh4[o * H4 + c4];
+        return v;
+    }
+    // the wave's 32 x 32 block of dz . A2 on the fp32 matrix instruction (k = 8 kb + 4 lh + j: A fragment and B slot agree)
+    __device__ __forceinline__ bp_f32x16 product() const
+    {
+        bp_f32x16 acc;
+        bp_zero<1>(&acc);
+#pragma unroll 4
+        for (int kb = 0; kb < H / 8; ++kb) {
+            const bp_f32x4 a4 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
+            const bp_f32x4 b4 = Bf4[(2 * kb + lh) * H + 32 * cb + li];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bp_mfma(acc, a4[j], b4[j]);
+        }
+        return acc;
+    }
+    // column sums of the workgroup: the RPP row groups of a chunk added in group order (reproducible)
+    __device__ __forceinline__ void column_sums(bp_f32x4 bsum, float* db_part, int accumulate) const
+    {
+        Dz4[rg * H4 + c4] = bsum;
+        __syncthreads();
+        if (tid < H4) {
+            bp_f32x4 s = Dz4[tid];
+            for (int g = 1; g < RPP; ++g) s += Dz4[g * H4 + tid];
+            bp_f32x4* dst = reinterpret_cast<bp_f32x4*>(db_part + (size_t)blockIdx.x * H) + tid;
+            *dst = accumulate ? *dst + s : s;
+        }
+    }
+};
+
 struct RnnBwdArgs {
     const float* dh_in;      // [R][H] or null (zeros)
     const float* h;          // [R][H] h_t
@@ -803,24 +911,12 @@ struct RnnBwdArgs {
 template <int H>
 __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void rnn_tanh_bwd_kernel(const RnnBwdArgs a)
 {
-    constexpr int NT = 4 * H, H4 = H / 4, LDA = H + 4, LDA4 = LDA / 4, CB = H / 32, RPP = NT / H4, PER = 64 / RPP;
-    static_assert(RPP * PER == 64 && NT / 64 == 2 * CB, "tile split");
+    using Tile = TanhTile<H>;
+    constexpr int NT = Tile::NT, LDA4 = Tile::LDA4, RPP = Tile::RPP, PER = Tile::PER;
     IC3_DYNAMIC_LDS(float, smem);
-    const bp_f32x4* const Bf4 = reinterpret_cast<const bp_f32x4*>(smem);     // [H / 8][2][H] float4
-    float* const Dz = smem + H * H;                                          // [64][LDA] the tile's dz
-    bp_f32x4* const Dz4 = reinterpret_cast<bp_f32x4*>(Dz);
-    float* const Wh = Dz + 64 * LDA;                                         // [16][H] W_heads
-    const bp_f32x4* const Wh4 = reinterpret_cast<const bp_f32x4*>(Wh);
-    float* const Sd = Wh + 16 * H;                                           // [64][OT] the tile's d rows
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int cb = w % CB, rb = w / CB;
-    const int c4 = tid % H4, rg = tid / H4;                      // phase 0: column chunk c4 of rows rg + RPP i
+    const Tile t(smem);
     const int OT = a.OT;
-    for (int i = tid; i < H * H; i += NT) {
-        const int k = i / H, col = i - k * H;
-        smem[(((k >> 3) * 2 + ((k >> 2) & 1)) * H + col) * 4 + (k & 3)] = a.a2[i];
-    }
-    for (int i = tid; i < OT * H; i += NT) Wh[i] = a.w_heads[i];
+    t.stage_weights(a.a2, a.w_heads, OT);
     bp_f32x4 bsum = { 0.f, 0.f, 0.f, 0.f };
     __syncthreads();
     for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
@@ -834,55 +930,37 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void rnn_tanh_bwd_kernel(
         bp_f32x4 dv[PER], hv[PER];
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            const int off = ((rg + RPP * i) * H + 4 * c4) * 4;
+            const int off = ((t.rg + RPP * i) * H + 4 * t.c4) * 4;
             dv[i] = bp_load4(rdi, off);
             hv[i] = bp_load4(rh, off);
         }
-        for (int i = tid; i < 64 * OT; i += NT) Sd[i] = bp_load1(rd, i * 4);
+        for (int i = t.tid; i < 64 * OT; i += NT) t.Sd[i] = bp_load1(rd, i * 4);
         __syncthreads();
         // ---- phase 0: dz of the tile -> ring, LDS, column sums
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            const int row = rg + RPP * i;
-            bp_f32x4 v = dv[i];
-            for (int o = 0; o < OT; ++o) v += Sd[row * OT + o] * Wh4[o * H4 + c4];
+            const int row = t.rg + RPP * i;
+            const bp_f32x4 v = t.heads_share(dv[i], row, OT);
             const bp_f32x4 z = v * (1.0f - hv[i] * hv[i]);
             bsum += z;
-            Dz4[row * LDA4 + c4] = z;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, z), rz, (row * H + 4 * c4) * 4, 0, 0);
+            t.Dz4[row * LDA4 + t.c4] = z;
+            bp_store4(z, rz, (row * H + 4 * t.c4) * 4);
         }
         __syncthreads();
-        // ---- phase 1: dh_out = dz . A2 on the fp32 matrix instruction (k = 8 kb + 4 lh + j: A fragment and B slot agree)
-        bp_f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-#pragma unroll 4
-        for (int kb = 0; kb < H / 8; ++kb) {
-            const bp_f32x4 a4 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
-            const bp_f32x4 b4 = Bf4[(2 * kb + lh) * H + 32 * cb + li];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bp_mfma(acc, a4[j], b4[j]);
-        }
+        // ---- phase 1: dh_out = (dz . A2) * out_scale, stored from the accumulator layout
+        const bp_f32x16 acc = t.product();
         const __amdgpu_buffer_rsrc_t rout = bp_rsrc(a.dh_out + r0 * H, (long long)rows * H * 4);
         const __amdgpu_buffer_rsrc_t rsc = bp_rsrc(a.out_scale ? a.out_scale + r0 : a.dh_out, a.out_scale ? (long long)rows * 4 : 0);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int lr = 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+            const int lr = 32 * t.rb + (reg & 3) + 8 * (reg >> 2) + 4 * t.lh;
             float o = acc[reg];
             if (a.out_scale) o *= bp_load1(rsc, lr * 4);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o), rout, (lr * H + 32 * cb + li) * 4, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o), rout, (lr * H + 32 * t.cb + t.li) * 4, 0, 0);
         }
         __syncthreads();                                         // every wave is done with the tile's LDS
     }
-    // column sums of the workgroup: the RPP row groups of a chunk added in group order (reproducible)
-    Dz4[rg * H4 + c4] = bsum;
-    __syncthreads();
-    if (tid < H4) {
-        bp_f32x4 s = Dz4[tid];
-        for (int g = 1; g < RPP; ++g) s += Dz4[g * H4 + tid];
-        bp_f32x4* dst = reinterpret_cast<bp_f32x4*>(a.db_part + (size_t)blockIdx.x * H) + tid;
-        *dst = a.accumulate ? *dst + s : s;
-    }
+    t.column_sums(bsum, a.db_part, a.accumulate);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -911,14 +989,12 @@ __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
     IC3_DYNAMIC_LDS(float, smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int wm = w & 1, wn = w >> 1;
-    const long long q0 = (long long)blockIdx.x * a.rows_per_wg;
-    long long nq = a.Q - q0;
-    if (nq > a.rows_per_wg) nq = a.rows_per_wg;
-    if (nq < 0) nq = 0;
+    const KSlice sl = bp_kslice(a.Q, a.rows_per_wg, KT);
+    const long long q0 = sl.q0, nq = sl.nq;
+    const int nstages = sl.nstages;
     const __amdgpu_buffer_rsrc_t rz = bp_rsrc(nq > 0 ? a.dz + q0 * H : a.dz, nq * H * 4);
     const __amdgpu_buffer_rsrc_t rh = bp_rsrc(nq > 0 ? a.h + q0 * H : a.h, nq * H * 4);
     const __amdgpu_buffer_rsrc_t rl = bp_rsrc(a.row_live && nq > 0 ? a.row_live + q0 : a.h, a.row_live ? nq * 4 : 0);
-    const int nstages = (int)((nq + KT - 1) / KT);
     const int srow = tid / H4, sc4 = tid - srow * H4;            // a thread stages rows srow + RPS i, column chunk sc4
     bp_f32x4 zr[PT], hr[PT];
     auto fetch = [&](int s) {
@@ -926,8 +1002,8 @@ __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
 #pragma unroll
         for (int i = 0; i < PT; ++i) {
             const int off = ((srow + RPS * i) * H + 4 * sc4) * 4;
-            zr[i] = __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, off, qb * H * 4, 0));
-            hr[i] = __builtin_bit_cast(bp_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, off, qb * H * 4, 0));
+            zr[i] = bp_load4(rz, off, qb * H * 4);
+            hr[i] = bp_load4(rh, off, qb * H * 4);
             if (a.row_live) hr[i] *= bp_load1(rl, (srow + RPS * i) * 4, qb * 4);
         }
     };
@@ -941,12 +1017,7 @@ __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
         }
     };
     bp_f32x16 acc[MB][MB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < MB; ++nb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mb][nb][i] = 0.0f;
+    bp_zero<MB * MB>(&acc[0][0]);
     if (nstages > 0) {
         fetch(0);
         stash(0);
@@ -990,36 +1061,34 @@ __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
 }  // namespace ic3
 
 // ---- ic3_rnn_backward --------------------------------------------------------------------------------------------------------
-// Tile plan of the per-step launch: tiles of 64 rows, at most one round of workgroup slots (one per CU at hid 128, two at 64), and
-// every workgroup the same number of tiles — the launch lasts as long as the workgroup with the most tiles either way, and every
-// workgroup fewer is one partial less to sum (PP-hard, E = 8192: 1280 tiles on 256 CUs = 256 workgroups x 5, no thin last round).
-extern "C" int ic3_rnn_backward_partials(long long R, int H)
+// Tile plan of a tanh kernel's launch over `rows` rows: tiles of 64 rows, at most one round of workgroup slots (one per CU at hid
+// 128, two at 64), and every workgroup the same number of tiles — the launch lasts as long as the workgroup with the most tiles
+// either way, and every workgroup fewer is one partial less to sum (PP-hard, E = 8192: 1280 tiles on 256 CUs = 256 workgroups x
+// 5, no thin last round).
+static int tanh_partials(long long rows, int H)
 {
-    if (R <= 0 || (H != 64 && H != 128)) return 0;
-    const long long tiles = (R + 63) / 64;
+    if (rows <= 0 || (H != 64 && H != 128)) return 0;
+    const long long tiles = (rows + 63) / 64;
     const long long cap = (long long)ic3::bp_cus() * (H == 64 ? 2 : 1);
     const long long rounds = (tiles + cap - 1) / cap;
     return (int)((tiles + rounds - 1) / rounds);
 }
 
-extern "C" int ic3_rnn_backward_supported(const ic3_env* env, int H)
+// both baselines' windows: the tanh kernels' sizes, and the sparse encoder's backward in its partial-sums form
+static int tanh_supported(const ic3_env* env, int H)
 {
     if (!env || (H != 64 && H != 128)) return 0;
-    return ic3_bptt_backward_supported(env, H);    // (the sparse encoder's backward in its partial-sums form)
+    return ic3_bptt_backward_supported(env, H);
 }
 
-static int rnn_wgrad_slices(long long Q)
-{
-    int ks = 2 * ic3::bp_cus();                                  // two workgroups per CU
-    const long long most = (Q + 15) / 16;
-    if (ks > most) ks = (int)most;
-    return ks < 1 ? 1 : ks;
-}
+extern "C" int ic3_rnn_backward_partials(long long R, int H) { return tanh_partials(R, H); }
+
+extern "C" int ic3_rnn_backward_supported(const ic3_env* env, int H) { return tanh_supported(env, H); }
 
 extern "C" size_t ic3_rnn_weight_grad_scratch_floats(long long Q, int H)
 {
     if (Q <= 0 || (H != 64 && H != 128)) return 0;
-    return (size_t)rnn_wgrad_slices(Q) * H * H;
+    return (size_t)wgrad_plan(Q, 1, 0).ks * H * H;
 }
 
 extern "C" int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const float* row_live, long long Q, int H, float* dA2,
@@ -1028,25 +1097,14 @@ extern "C" int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const f
     using namespace ic3;
     if (!dz || !h_prev || !dA2 || !scratch || Q <= 0) return fail(-22, "ic3_rnn_weight_grad: null argument");
     if (H != 64 && H != 128) return fail(-38, "ic3_rnn_weight_grad: hid_size 64 / 128");
-    const int ks = rnn_wgrad_slices(Q);
-    long long per = (Q + ks - 1) / ks;
-    per = (per + 15) / 16 * 16;
-    if (per * H * 4 >= (1ll << 31)) return fail(-22, "ic3_rnn_weight_grad: a K slice must stay below 2 GB (32-bit buffer offsets)");
-    const RnnWGradArgs a{ dz, h_prev, row_live, scratch, Q, (int)per };
+    const WGradPlan pl = wgrad_plan(Q, 1, H);
+    if (!pl.fits) return fail(-22, "ic3_rnn_weight_grad: a K slice must stay below 2 GB (32-bit buffer offsets)");
+    const RnnWGradArgs a{ dz, h_prev, row_live, scratch, Q, (int)pl.per };
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)2 * 2 * 16 * H * sizeof(float);
-    if (H == 128) {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_wgrad_kernel<128>), lds));
-        hipLaunchKernelGGL((rnn_wgrad_kernel<128>), dim3(ks), dim3(256), lds, s, a);
-    } else {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_wgrad_kernel<64>), lds));
-        hipLaunchKernelGGL((rnn_wgrad_kernel<64>), dim3(ks), dim3(256), lds, s, a);
-    }
-    IC3_HIP(hipGetLastError());
-    const int n = H * H;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, scratch, ks, n, dA2, accumulate);
-    IC3_HIP(hipGetLastError());
-    return ks;
+    if (const int rc = launch_kernel(H == 128 ? rnn_wgrad_kernel<128> : rnn_wgrad_kernel<64>, dim3(pl.ks), dim3(256), lds, s, a); rc < 0)
+        return rc;
+    return wgrad_reduce(scratch, pl.ks, H * H, dA2, accumulate, s);
 }
 
 // one step of the chain (also the unit the tests drive): returns the number of partials written / added to
@@ -1060,34 +1118,23 @@ extern "C" int ic3_rnn_tanh_backward_step(const float* dh_in, const float* h_t, 
     if (H != 64 && H != 128) return fail(-38, "ic3_rnn_tanh_backward_step: hid_size 64 / 128");
     if (OT < 1 || OT > 16) return fail(-22, "ic3_rnn_tanh_backward_step: 1 <= OT <= 16");
     if (R >= (1ll << 31)) return fail(-22, "ic3_rnn_tanh_backward_step: R < 2^31");
-    const int grid = ic3_rnn_backward_partials(R, H);
+    const int grid = tanh_partials(R, H);
     const RnnBwdArgs a{ dh_in, h_t, dhead, w_heads, a2, out_scale, dz, dh_out, dbias_partials, (int)R, OT, (int)((R + 63) / 64),
                         accumulate };
-    const size_t lds = ((size_t)H * H + 64 * (H + 4) + 16 * H + 64 * 16) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    if (H == 128) {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_tanh_bwd_kernel<128>), lds));
-        hipLaunchKernelGGL((rnn_tanh_bwd_kernel<128>), dim3(grid), dim3(512), lds, s, a);
-    } else {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rnn_tanh_bwd_kernel<64>), lds));
-        hipLaunchKernelGGL((rnn_tanh_bwd_kernel<64>), dim3(grid), dim3(256), lds, s, a);
-    }
-    IC3_HIP(hipGetLastError());
-    return grid;
+    const int rc = H == 128 ? launch_kernel(rnn_tanh_bwd_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES, s, a)
+                            : launch_kernel(rnn_tanh_bwd_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES, s, a);
+    return rc < 0 ? rc : grid;
 }
 
 extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream)
 {
     using namespace ic3;
-    if (!env || !b) return fail(-22, "ic3_rnn_backward: null argument");
-    if (b->struct_size != sizeof(ic3_rnn_bptt))
-        return fail(-22, "ic3_rnn_backward: ic3_rnn_bptt has " + std::to_string(b->struct_size) + " bytes, this library's has " +
-                             std::to_string(sizeof(ic3_rnn_bptt)) + " (header / library version mismatch)");
+    if (const int rc = window_open("ic3_rnn_backward", "ic3_rnn_bptt", env, b, tanh_supported,
+                                   "hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form", false);
+        rc < 0)
+        return rc;
     const int T = b->T, E = b->E, N = b->N, H = b->H;
-    if (T <= 0 || E <= 0 || N <= 0 || E != env->dims.E || N != env->dims.N)
-        return fail(-22, "ic3_rnn_backward: T, E, N must be positive and E, N the handle's");
-    if (!ic3_rnn_backward_supported(env, H)) return fail(-38, "ic3_rnn_backward: hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form");
-    if (b->OT < 1 || b->OT > 16) return fail(-22, "ic3_rnn_backward: 1 <= OT <= 16");
     if (!b->hs || !b->dhead || !b->snaps || !b->a2 || !b->w_heads || !b->dh || !b->dz || !b->dbias_partials || !b->enc_work)
         return fail(-22, "ic3_rnn_backward: null argument");
     if (b->a2_grad && !b->wgrad_scratch) return fail(-22, "ic3_rnn_backward: a2_grad needs wgrad_scratch");
@@ -1159,25 +1206,14 @@ struct MlpBwdArgs {
 template <int H>
 __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void mlp_bwd_kernel(const MlpBwdArgs a)
 {
-    constexpr int NT = 4 * H, H4 = H / 4, LDA = H + 4, LDA4 = LDA / 4, CB = H / 32, RPP = NT / H4, PER = 64 / RPP;
+    using Tile = TanhTile<H>;
+    constexpr int NT = Tile::NT, LDA = Tile::LDA, LDA4 = Tile::LDA4, RPP = Tile::RPP, PER = Tile::PER;
     constexpr int DPT = 64 * 16 / NT;                            // d values a thread stages per tile, at most
-    static_assert(RPP * PER == 64 && NT / 64 == 2 * CB && DPT * NT == 64 * 16, "tile split");
+    static_assert(DPT * NT == 64 * 16, "tile split");
     IC3_DYNAMIC_LDS(float, smem);
-    const bp_f32x4* const Bf4 = reinterpret_cast<const bp_f32x4*>(smem);     // [H / 8][2][H] float4
-    float* const Dz = smem + H * H;                                          // [64][LDA] the tile's dz, then its dz . A2
-    bp_f32x4* const Dz4 = reinterpret_cast<bp_f32x4*>(Dz);
-    float* const Wh = Dz + 64 * LDA;                                         // [16][H] W_heads
-    const bp_f32x4* const Wh4 = reinterpret_cast<const bp_f32x4*>(Wh);
-    float* const Sd = Wh + 16 * H;                                           // [64][OT] the tile's d rows
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int cb = w % CB, rb = w / CB;
-    const int c4 = tid % H4, rg = tid / H4;                      // phase 0 / epilogue: column chunk c4 of rows rg + RPP i
+    const Tile t(smem);                                          // (Dz: the tile's dz, then its dz . A2)
     const int OT = a.OT;
-    for (int i = tid; i < H * H; i += NT) {
-        const int k = i / H, col = i - k * H;
-        smem[(((k >> 3) * 2 + ((k >> 2) & 1)) * H + col) * 4 + (k & 3)] = a.a2[i];
-    }
-    for (int i = tid; i < OT * H; i += NT) Wh[i] = a.w_heads[i];
+    t.stage_weights(a.a2, a.w_heads, OT);
     bp_f32x4 bsum = { 0.f, 0.f, 0.f, 0.f };
     bp_f32x4 ev[PER], hv[PER];
     float dp[DPT];
@@ -1190,12 +1226,12 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void mlp_bwd_kernel(const
         const __amdgpu_buffer_rsrc_t rd = bp_rsrc(a.dhead + r0 * OT, (long long)rows * OT * 4);
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            const int off = ((rg + RPP * i) * H + 4 * c4) * 4;
+            const int off = ((t.rg + RPP * i) * H + 4 * t.c4) * 4;
             ev[i] = bp_load4(re, off);
             hv[i] = bp_load4(rh, off);
         }
 #pragma unroll
-        for (int i = 0; i < DPT; ++i) dp[i] = bp_load1(rd, (tid + i * NT) * 4);      // (past 64 OT: past the range, 0)
+        for (int i = 0; i < DPT; ++i) dp[i] = bp_load1(rd, (t.tid + i * NT) * 4);    // (past 64 OT: past the range, 0)
     };
     if ((int)blockIdx.x < a.tiles) fetch(blockIdx.x);
     __syncthreads();
@@ -1206,81 +1242,52 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void mlp_bwd_kernel(const
         const __amdgpu_buffer_rsrc_t rz = bp_rsrc(a.dz + r0 * H, (long long)rows * H * 4);
         const __amdgpu_buffer_rsrc_t rde = bp_rsrc(a.de + r0 * H, (long long)rows * H * 4);
 #pragma unroll
-        for (int i = 0; i < DPT; ++i) Sd[tid + i * NT] = dp[i];
+        for (int i = 0; i < DPT; ++i) t.Sd[t.tid + i * NT] = dp[i];
         __syncthreads();
         // ---- phase 0: x1 over e; dz of the tile -> ring, LDS, column sums
         bp_f32x4 xv[PER], zv[PER];
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            const int row = rg + RPP * i;
+            const int row = t.rg + RPP * i;
             bp_f32x4 x;
 #pragma unroll
             for (int q = 0; q < 4; ++q) x[q] = fast_tanh(ev[i][q]);
-            bp_f32x4 v = { 0.f, 0.f, 0.f, 0.f };
-            for (int o = 0; o < OT; ++o) v += Sd[row * OT + o] * Wh4[o * H4 + c4];
+            const bp_f32x4 v = t.heads_share(bp_f32x4{ 0.f, 0.f, 0.f, 0.f }, row, OT);
             const bp_f32x4 z = v * (1.0f - hv[i] * hv[i]);
             bsum += z;
             xv[i] = x;
             zv[i] = z;
-            Dz4[row * LDA4 + c4] = z;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, x), rx, (row * H + 4 * c4) * 4, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, z), rz, (row * H + 4 * c4) * 4, 0, 0);
+            t.Dz4[row * LDA4 + t.c4] = z;
+            bp_store4(x, rx, (row * H + 4 * t.c4) * 4);
+            bp_store4(z, rz, (row * H + 4 * t.c4) * 4);
         }
         if (tile + (int)gridDim.x < a.tiles) fetch(tile + gridDim.x);       // the next tile's rows, in flight under the product
         __syncthreads();
-        // ---- phase 1: dz . A2 on the fp32 matrix instruction (k = 8 kb + 4 lh + j: A fragment and B slot agree)
-        bp_f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-#pragma unroll 4
-        for (int kb = 0; kb < H / 8; ++kb) {
-            const bp_f32x4 a4 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
-            const bp_f32x4 b4 = Bf4[(2 * kb + lh) * H + 32 * cb + li];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bp_mfma(acc, a4[j], b4[j]);
-        }
+        // ---- phase 1: dz . A2
+        const bp_f32x16 acc = t.product();
         __syncthreads();                                         // every wave has read the tile's dz rows
         // ---- epilogue: the product back through the LDS tile, de = (dz . A2 + dz)(1 - x1^2) in the phase-0 layout
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
-            Dz[(32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh) * LDA + 32 * cb + li] = acc[reg];
+            t.Dz[(32 * t.rb + (reg & 3) + 8 * (reg >> 2) + 4 * t.lh) * LDA + 32 * t.cb + t.li] = acc[reg];
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            const int row = rg + RPP * i;
-            const bp_f32x4 g = (Dz4[row * LDA4 + c4] + zv[i]) * (1.0f - xv[i] * xv[i]);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ps_u32x4, g), rde, (row * H + 4 * c4) * 4, 0, 0);
+            const int row = t.rg + RPP * i;
+            const bp_f32x4 g = (t.Dz4[row * LDA4 + t.c4] + zv[i]) * (1.0f - xv[i] * xv[i]);
+            bp_store4(g, rde, (row * H + 4 * t.c4) * 4);
         }
         __syncthreads();                                         // every thread is done with the tile's LDS
     }
-    // column sums of the workgroup: the RPP row groups of a chunk added in group order (reproducible)
-    Dz4[rg * H4 + c4] = bsum;
-    __syncthreads();
-    if (tid < H4) {
-        bp_f32x4 s = Dz4[tid];
-        for (int g = 1; g < RPP; ++g) s += Dz4[g * H4 + tid];
-        bp_f32x4* dst = reinterpret_cast<bp_f32x4*>(a.db_part + (size_t)blockIdx.x * H) + tid;
-        *dst = a.accumulate ? *dst + s : s;
-    }
+    t.column_sums(bsum, a.db_part, a.accumulate);
 }
 
 }  // namespace ic3
 
 // Tile plan of the launch: as ic3_rnn_backward_partials, over the Q rows of the window (one launch, not one per step).
-extern "C" int ic3_mlp_backward_partials(long long Q, int H)
-{
-    if (Q <= 0 || (H != 64 && H != 128)) return 0;
-    const long long tiles = (Q + 63) / 64;
-    const long long cap = (long long)ic3::bp_cus() * (H == 64 ? 2 : 1);
-    const long long rounds = (tiles + cap - 1) / cap;
-    return (int)((tiles + rounds - 1) / rounds);
-}
+extern "C" int ic3_mlp_backward_partials(long long Q, int H) { return tanh_partials(Q, H); }
 
-extern "C" int ic3_mlp_backward_supported(const ic3_env* env, int H)
-{
-    if (!env || (H != 64 && H != 128)) return 0;
-    return ic3_bptt_backward_supported(env, H);    // (the sparse encoder's backward in its partial-sums form)
-}
+extern "C" int ic3_mlp_backward_supported(const ic3_env* env, int H) { return tanh_supported(env, H); }
 
 // the launch alone (also the unit the tests drive): returns the number of partials written / added to
 extern "C" int ic3_mlp_backward_step(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT, const float* a2,
@@ -1294,34 +1301,22 @@ extern "C" int ic3_mlp_backward_step(float* x1_inout, const float* h, const floa
     if (OT < 1) return fail(-22, "ic3_mlp_backward_step: OT >= 1");
     if (OT > 16) return fail(-38, "ic3_mlp_backward_step: at most 16 output columns");
     if (Q >= (1ll << 36)) return fail(-22, "ic3_mlp_backward_step: Q < 2^36");
-    const int grid = ic3_mlp_backward_partials(Q, H);
+    const int grid = tanh_partials(Q, H);
     const MlpBwdArgs a{ x1_inout, h, dhead, w_heads, a2, dz, de, dbias_partials, Q, OT, (int)((Q + 63) / 64), accumulate };
-    const size_t lds = ((size_t)H * H + 64 * (H + 4) + 16 * H + 64 * 16) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    if (H == 128) {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(mlp_bwd_kernel<128>), lds));
-        hipLaunchKernelGGL((mlp_bwd_kernel<128>), dim3(grid), dim3(512), lds, s, a);
-    } else {
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(mlp_bwd_kernel<64>), lds));
-        hipLaunchKernelGGL((mlp_bwd_kernel<64>), dim3(grid), dim3(256), lds, s, a);
-    }
-    IC3_HIP(hipGetLastError());
-    return grid;
+    const int rc = H == 128 ? launch_kernel(mlp_bwd_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES, s, a)
+                            : launch_kernel(mlp_bwd_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES, s, a);
+    return rc < 0 ? rc : grid;
 }
 
 extern "C" int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream)
 {
     using namespace ic3;
-    if (!env || !b) return fail(-22, "ic3_mlp_backward: null argument");
-    if (b->struct_size != sizeof(ic3_mlp_bptt))
-        return fail(-22, "ic3_mlp_backward: ic3_mlp_bptt has " + std::to_string(b->struct_size) + " bytes, this library's has " +
-                             std::to_string(sizeof(ic3_mlp_bptt)) + " (header / library version mismatch)");
+    if (int rc = window_open("ic3_mlp_backward", "ic3_mlp_bptt", env, b, tanh_supported,
+                             "hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form", true);
+        rc < 0)
+        return rc;
     const int T = b->T, E = b->E, N = b->N, H = b->H;
-    if (T <= 0 || E <= 0 || N <= 0 || E != env->dims.E || N != env->dims.N)
-        return fail(-22, "ic3_mlp_backward: T, E, N must be positive and E, N the handle's");
-    if (!ic3_mlp_backward_supported(env, H)) return fail(-38, "ic3_mlp_backward: hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form");
-    if (b->OT < 1) return fail(-22, "ic3_mlp_backward: OT >= 1");
-    if (b->OT > 16) return fail(-38, "ic3_mlp_backward: at most 16 output columns");
     if (!b->h || !b->dhead || !b->snaps || !b->enc_wt || !b->enc_bias || !b->a2 || !b->w_heads || !b->x1 || !b->dz || !b->de ||
         !b->dbias_partials || !b->enc_work)
         return fail(-22, "ic3_mlp_backward: null argument");
@@ -1337,18 +1332,8 @@ extern "C" int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream 
     }
     int rc = ic3_mlp_backward_step(b->x1, b->h, b->dhead, b->w_heads, b->OT, b->a2, b->dz, b->de, b->dbias_partials, 0, Q, H, stream);
     if (rc < 0) return rc;
-    if (b->enc_window) {
-        rc = ic3_env_encode_backward_window(env, b->snaps, b->snap_words, T, b->de, H, R * H, H, b->enc_work, b->enc_first, stream);
-        if (rc < 0) return rc;
-    } else {
-        int enc_first = b->enc_first;
-        for (int t = T - 1; t >= 0; --t) {                       // (last step first: the order of the per-step loop)
-            rc = ic3_env_encode_backward_accumulate(env, b->snaps + (size_t)t * b->snap_words, b->de + (size_t)t * R * H, H, H,
-                                                    b->enc_work, enc_first, stream);
-            if (rc < 0) return rc;
-            enc_first = 0;
-        }
-    }
+    rc = encoder_tail(env, b->snaps, b->snap_words, T, b->de, H, R * H, H, b->enc_work, b->enc_first, b->enc_window != 0, stream);
+    if (rc < 0) return rc;
     if (b->a2_grad) {
         rc = ic3_rnn_weight_grad(b->dz, b->x1, nullptr, Q, H, b->a2_grad, 1, b->wgrad_scratch, stream);
         if (rc < 0) return rc;

@@ -515,6 +515,13 @@ extern "C" int ic3_lstm_gates_backward_given(const float* gates, float* xh, int 
                                accumulate, lstm_wp3_bwd, dxh, R, H, stream, gates, row_live, row_keep, dhead, w_heads, OT);
 }
 
+// the instantiation for recorded gates (always the split products) / the split or the fp32 gate product
+template <int H>
+static auto gates_bwd_kernel_of(bool given, bool split)
+{
+    return given ? ic3::lstm_gates_bwd_kernel<H, 1, 1> : split ? ic3::lstm_gates_bwd_kernel<H, 1> : ic3::lstm_gates_bwd_kernel<H, 0>;
+}
+
 static int gates_backward_impl(float* xh, int ldx, const float* h_prev, const float* lstm_wp, const void* lstm_wp3, const float* bias,
                                const float* c_prev, const float* dh, const float* dc, float* dgates, float* dc_prev,
                                float* dbias_partials, int accumulate, const void* wb3, float* dxh, int R, int H, ic3_stream stream,
@@ -532,36 +539,10 @@ static int gates_backward_impl(float* xh, int ldx, const float* h_prev, const fl
     const int tiles = (R + 63) / 64;
     const size_t lds = ((size_t)64 * (2 * H + 4) + 4 * H + (gates ? 64 * 16 : 0)) * sizeof(float);   // (+ the dhead tile)
     hipStream_t s = (hipStream_t)stream;
-    if (gates) {                                                 // (H 64 / 128 / 256: checked by the entry point)
-        if (H == 256) {                                          // (512 threads, one workgroup per CU: 140 KB of LDS)
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_gates_bwd_kernel<256, 1, 1>), lds));
-            hipLaunchKernelGGL((lstm_gates_bwd_kernel<256, 1, 1>), dim3(tiles), dim3(512), lds, s, a);
-        } else if (H == 128) {
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_gates_bwd_kernel<128, 1, 1>), lds));
-            hipLaunchKernelGGL((lstm_gates_bwd_kernel<128, 1, 1>), dim3(tiles), dim3(256), lds, s, a);
-        } else {
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_gates_bwd_kernel<64, 1, 1>), lds));
-            hipLaunchKernelGGL((lstm_gates_bwd_kernel<64, 1, 1>), dim3(tiles), dim3(128), lds, s, a);
-        }
-        IC3_HIP(hipGetLastError());
-        return tiles;
-    }
-#define IC3_GB(h)                                                                                                       \
-    case h:                                                                                                             \
-        if (lstm_wp3) {                                                                                                 \
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_gates_bwd_kernel<h, 1>), lds));               \
-            hipLaunchKernelGGL((lstm_gates_bwd_kernel<h, 1>), dim3(tiles), dim3(2 * h), lds, s, a);                     \
-        } else {                                                                                                        \
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lstm_gates_bwd_kernel<h, 0>), lds));               \
-            hipLaunchKernelGGL((lstm_gates_bwd_kernel<h, 0>), dim3(tiles), dim3(2 * h), lds, s, a);                     \
-        }                                                                                                               \
-        break;
-    switch (H) {
-        IC3_GB(64)
-        IC3_GB(128)
-        IC3_GB(256)
-    }
-#undef IC3_GB
-    IC3_HIP(hipGetLastError());
+    // (H 64 / 128 / 256: checked by the entry point; 2 H threads — at 256 one workgroup per CU: 140 KB of LDS)
+    const bool given = gates != nullptr, split = lstm_wp3 != nullptr;
+    const auto kernel = H == 256 ? gates_bwd_kernel_of<256>(given, split)
+                                 : H == 128 ? gates_bwd_kernel_of<128>(given, split) : gates_bwd_kernel_of<64>(given, split);
+    if (const int rc = launch_kernel(kernel, dim3(tiles), dim3(2 * H), lds, s, a); rc < 0) return rc;
     return tiles;   // rows of dbias_partials written
 }

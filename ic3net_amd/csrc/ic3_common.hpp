@@ -140,6 +140,19 @@ struct Range {
         }                                                                                                 \
     } while (0)
 
+// One launch the way every entry point does it: the kernel's dynamic-LDS limit raised (where it asks for any), the launch,
+// the runtime's verdict on it.  0, or IC3_HIP's -5 with ic3_last_error() set (the failed call and the runtime's text; which
+// instantiation it was is not in the message: the entry point that returned -5 tells the kernel family, its H argument the rest).
+// The H dispatch of a call site is the choice of the instantiation it passes.
+template <class... P, class... A>
+inline int launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args)
+{
+    if (lds) IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    IC3_HIP(hipGetLastError());
+    return 0;
+}
+
 // LSTM nonlinearities on the hardware transcendental unit (v_exp_f32 / v_rcp_f32, ~1 ulp each), shared by the
 // pointwise cell kernels and the fused MFMA kernel.  The accurate ocml expf/tanhf made those kernels VALU-bound
 // (~4000 VALU cycles per wave against ~700 cycles of memory time in lstm_cell_heads_kernel).  Absolute error <= ~2e-7

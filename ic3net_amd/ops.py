@@ -311,6 +311,16 @@ def comm_backward(dxh, h_prev, alive, gate, c_weight, dh_out, dcw_partials, E, N
     return n
 
 
+def _scratch(work, key, n, device):
+    """A float32 scratch tensor of at least n elements on `device`, kept in the caller's dict `work` under (key, device) and grown
+    when a call needs more (work None: a fresh one)."""
+    work = work if work is not None else dict()
+    key = (key, str(device))
+    if key not in work or work[key].numel() < n:
+        work[key] = torch.empty((n,), dtype=torch.float32, device=device)
+    return work[key]
+
+
 def lstm_weight_grad(inp, h_prev, dgates, dW, row_live=None, accumulate=True, work=None, split=True):
     """ic3_lstm_weight_grad: dW (2H, 4H) (+)= [inp | h_prev]^T @ dgates over all Q rows of a window of recorded steps in one
     launch.  inp (Q, >= H) rows with unit column stride (the first H floats count: the record's [inp | h] rows), h_prev (Q, H),
@@ -325,15 +335,12 @@ def lstm_weight_grad(inp, h_prev, dgates, dW, row_live=None, accumulate=True, wo
     assert dW.is_contiguous() and tuple(dW.shape) == (2 * H, 4 * H)
     if row_live is not None:
         assert row_live.is_contiguous() and row_live.dtype == torch.float32 and row_live.numel() == Q
-    work = work if work is not None else dict()
     n = int(_lib.lib().ic3_lstm_weight_grad_scratch_floats(Q, H))
     if n == 0:
         raise NotImplementedError("lstm_weight_grad: hid_size 64 / 128")
-    key = ('wgrad', str(dgates.device))
-    if key not in work or work[key].numel() < n:
-        work[key] = torch.empty((n,), dtype=torch.float32, device=dgates.device)
     check(_lib.lib().ic3_lstm_weight_grad(ptr(inp2), inp2.stride(0), ptr(h_prev), ptr(dgates), ptr(row_live), Q, H, ptr(dW),
-                                          int(bool(accumulate)), int(bool(split)), ptr(work[key]), stream()))
+                                          int(bool(accumulate)), int(bool(split)), ptr(_scratch(work, 'wgrad', n, dgates.device)),
+                                          stream()))
 
 
 def first_chain_envs(E, N):
@@ -464,12 +471,8 @@ def rnn_weight_grad(dz, h_prev, dA2, row_live=None, accumulate=True, work=None):
     n = int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(Q, H))
     if n == 0:
         raise NotImplementedError("rnn_weight_grad: hid_size 64 / 128")
-    work = work if work is not None else dict()
-    key = ('rnn_wgrad', str(dz.device))
-    if key not in work or work[key].numel() < n:
-        work[key] = torch.empty((n,), dtype=torch.float32, device=dz.device)
-    check(_lib.lib().ic3_rnn_weight_grad(ptr(dz), ptr(h_prev), ptr(row_live), Q, H, ptr(dA2), int(bool(accumulate)), ptr(work[key]),
-                                         stream()))
+    check(_lib.lib().ic3_rnn_weight_grad(ptr(dz), ptr(h_prev), ptr(row_live), Q, H, ptr(dA2), int(bool(accumulate)),
+                                         ptr(_scratch(work, 'rnn_wgrad', n, dz.device)), stream()))
 
 
 def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_partials, h_last=None, detach_gap=0, row_live=None,
@@ -506,12 +509,8 @@ def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_p
     b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
     if a2_grad is not None:
         assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
-        work = work if work is not None else dict()
-        n = int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H))
-        key = ('rnn_wgrad', str(hs.device))
-        if key not in work or work[key].numel() < n:
-            work[key] = torch.empty((n,), dtype=torch.float32, device=hs.device)
-        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), work[key].data_ptr()
+        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H)), hs.device)
+        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), scratch.data_ptr()       # (`scratch`: alive until the call has returned)
     check(_lib.lib().ic3_rnn_backward(env._h, C.byref(b), stream()))
 
 
@@ -575,12 +574,8 @@ def mlp_backward(env, T, E, N, H, h, dhead, snaps, enc_wt, enc_bias, a2, w_heads
     b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
     if a2_grad is not None:
         assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
-        work = work if work is not None else dict()
-        n = int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H))
-        key = ('rnn_wgrad', str(h.device))
-        if key not in work or work[key].numel() < n:
-            work[key] = torch.empty((n,), dtype=torch.float32, device=h.device)
-        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), work[key].data_ptr()
+        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H)), h.device)
+        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), scratch.data_ptr()       # (`scratch`: alive until the call has returned)
     check(_lib.lib().ic3_mlp_backward(env._h, C.byref(b), stream()))
 
 
