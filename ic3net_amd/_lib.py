@@ -156,6 +156,9 @@ EXPORTS = {
     "ic3_lstm_weight_grad_scratch_floats": (C.c_size_t, [C.c_longlong, C.c_int]),
     "ic3_lstm_weight_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ic3_lstm_weight_grad_wide_scratch_floats": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "ic3_lstm_weight_grad_wide": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ic3_bptt_first_chain_envs": (C.c_int, [C.c_int, C.c_int]),
     "ic3_bptt_backward_supported": (C.c_int, [C.c_void_p, C.c_int]),
     "ic3_bptt_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

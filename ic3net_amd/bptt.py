@@ -460,7 +460,7 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
                           row_keep=cuts.keep_flat, enc_first=True,
                           gate_events=getattr(raw, 'gate_timer', None),     # (bench.py --mode train: HIP events around the gate launches)
                           two_chains=two)
-        if H == 256:
+        if H == 256 and not bool(getattr(args, 'lstm_wgrad_kernel', True)):
             _weight_grad_products(rec, T, R, H, acc['w_cat_t'], cuts.live_flat)
         else:
             work = acc.setdefault('_work', {})
@@ -476,8 +476,8 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
 
 
 def _weight_grad_products(rec, T, R, H, dW, row_live):
-    """The window's [W_ih | W_hh] gradient at hid 256 (ic3_lstm_weight_grad takes 64 / 128): two library products over all T x R
-    rows at once, behind the loop — dW[:H] += inp^T . dgates, dW[H:] += (row_live h)^T . dgates.  Collection mode scales the
+    """The window's [W_ih | W_hh] gradient at hid 256 behind args.lstm_wgrad_kernel=False (the default is the kernel,
+    ops.lstm_weight_grad, as at 64 / 128): two library products over all T x R rows at once, behind the loop — dW[:H] += inp^T . dgates, dW[H:] += (row_live h)^T . dgates.  Collection mode scales the
     dgates rows by row_live in place once the inp product has read them (the record is not read again): no T x R x H copy of h."""
     Q = T * R
     dg = rec.gates[:T].view(Q, 4 * H)

@@ -11,6 +11,7 @@
 //                         two masked-mean launches and two library products per step.
 //   ic3_lstm_weight_grad  ONE launch per window of recorded steps: d[W_ih | W_hh]^T += [inp | h_prev]^T . dgates over all
 //                         T x R rows at once (split-K over the CUs, fixed-order reduction) — replaces a library product per step.
+//                         Hid 64 / 128; ic3_lstm_weight_grad_wide: the same call for 64 / 128 / 256 (what ic3net_amd calls).
 //   ic3_bptt_backward     the loop over a window's steps, last to first, as ONE host call: cell derivative + input gradient
 //                         (ic3_lstm_gates_backward_given, the heads' share of dL/dh folded in) -> ic3_comm_backward -> the sparse
 //                         encoder's backward stage 1 — three launches per step, no host work between them.
@@ -19,7 +20,7 @@
 //   ic3_rnn_weight_grad   ONE launch per window: dA2 += dz^T . (row_live h_prev) over all T x R rows (rnn_wgrad_kernel).
 //   ic3_mlp_backward_step / ic3_mlp_backward   the IC baseline (models.MLP): a window is T x R independent rows, ONE launch over
 //                         all of them (mlp_bwd_kernel), and the window as one host call.
-// and what sizes their buffers / says whether they run: ic3_comm_backward_partials, ic3_lstm_weight_grad_scratch_floats,
+// and what sizes their buffers / says whether they run: ic3_comm_backward_partials, ic3_lstm_weight_grad[_wide]_scratch_floats,
 // ic3_bptt_backward_supported, ic3_bptt_first_chain_envs, ic3_rnn_ / ic3_mlp_backward_partials and _supported,
 // ic3_rnn_weight_grad_scratch_floats.
 // What these share exists once.  Device: bp_load1 / bp_load4 / bp_store4 (buffer access, the wave-uniform part in `soff`), bp_zero,
@@ -262,6 +263,17 @@ __global__ __launch_bounds__(256) void dh_copy_kernel(const float* __restrict__ 
 // Staging: KT = 16 rows per stage, global -> registers -> LDS, double-buffered, one barrier per stage.
 // Bound: MFMA (2 Q 2H 4H flop on the fp32 instruction: 1.72 TFLOP for a PP-hard update); X is read once per column block
 // (4 H / 128 times, from L2 when the blocks of a slice run together: they are gridDim.x apart, i.e. on one XCD), D once.
+// Hid 256 (dW 512 x 1024): all 2H output rows in one workgroup would be 256 accumulator registers per wave, so the <256>
+// instantiations ARE the tile of 128 — XW = 256 staged X columns, a wave holds 128 x 64, the LDS and the registers of <128> (two
+// workgroups per CU) — on a grid (ks, 8, 2): blockIdx.z picks the inp half (output rows 0..255, source rows of stride ldi) or the
+// h half (rows 256..511, times row_live) of [inp | h], so a workgroup stages ONE source and row_live touches the z = 1 workgroups
+// only.  D is fetched and split once per z, X once per ny; the 16 workgroups of a slice are gridDim.x apart with ks a multiple of
+// 8 (one XCD, one L2).  The slices are as many whole rounds of workgroups as keep one below 2 GB (lstm_wgrad_plan): the slices
+// beyond the resident ones simply start later.  WIDE / HT fold away at 64 / 128: those code objects are the earlier ones,
+// instruction for instruction.  Measured (profiles/r11/wgrad_h256.txt): 2.1 M rows 14.3 ms split / 15.8 ms fp32 against 24.6 ms for
+// the two library products they replace; in a config-5 update's kernel trace one launch of 153.0 ms per 80-step window (21 M rows,
+// 64 slices = two rounds; 144 TFLOP/s fp32-equivalent, 0.52 of the bf16 peak as issued — the <128> tile's share), the reduction
+// 0.034 ms.  At most 24 KB per row (no L2 sharing at all) = 3.3 TB/s: matrix-bound either way, as at 128.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct WGradArgs {
     const float* inp;        // [Q][ldi]: the first H floats of a row = inp
@@ -276,7 +288,9 @@ struct WGradArgs {
 template <int H>
 __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
 {
-    constexpr int KT = 16, XW = 2 * H, DW = 128, MB = H / 32, NB = 2, NT = 256;
+    constexpr bool WIDE = H == 256;                              // blockIdx.z: the inp half or the h half of [inp | h]
+    constexpr int HT = WIDE ? 128 : H;                           // output rows per wave
+    constexpr int KT = 16, XW = 2 * HT, DW = 128, MB = HT / 32, NB = 2, NT = 256;
     constexpr int X4R = XW / 4, D4R = DW / 4;                    // float4 per staged row
     constexpr int XPT = KT * X4R / NT, DPT = KT * D4R / NT;      // float4 per thread and stage (4 / 2 at H = 128)
     static_assert(XPT >= 1 && DPT == 2 && (NT % X4R) == 0, "staging split");
@@ -294,8 +308,8 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
     const __amdgpu_buffer_rsrc_t rl = bp_rsrc(a.row_live ? a.row_live + q0 : a.h, a.row_live ? nq * 4 : 0);
     // a thread stages the same (row-in-stage, column chunk) of every stage: X chunk i at row xrow + i * (NT / X4R)
     const int xrow = tid / X4R, xc4 = tid - xrow * X4R;
-    const bool x_is_h = xc4 >= H / 4;
-    const int xvoff = x_is_h ? (xrow * H + 4 * xc4 - H) * 4 : (xrow * a.ldi + 4 * xc4) * 4;
+    const bool x_is_h = WIDE ? blockIdx.z != 0 : xc4 >= H / 4;
+    const int xvoff = x_is_h ? (xrow * H + 4 * xc4 - (WIDE ? 0 : H)) * 4 : (xrow * a.ldi + 4 * xc4) * 4;
     const int xstep = (NT / X4R) * (x_is_h ? H : a.ldi) * 4;    // bytes between two of the thread's chunks
     const int drow = tid / D4R, dc4 = tid - drow * D4R;
     const int dvoff = (drow * 4 * H + 4 * dc4) * 4;
@@ -340,10 +354,10 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
             const int kr = 2 * ks + lh;
             float av[MB];
             if constexpr (MB == 4) {
-                const bp_f32x4 t4 = *reinterpret_cast<const bp_f32x4*>(Xs + kr * XW + wm * H + 4 * li);
+                const bp_f32x4 t4 = *reinterpret_cast<const bp_f32x4*>(Xs + kr * XW + wm * HT + 4 * li);
                 av[0] = t4[0], av[1] = t4[1], av[2] = t4[2], av[3] = t4[3];
             } else {
-                const bp_f32x2 t2 = *reinterpret_cast<const bp_f32x2*>(Xs + kr * XW + wm * H + 2 * li);
+                const bp_f32x2 t2 = *reinterpret_cast<const bp_f32x2*>(Xs + kr * XW + wm * HT + 2 * li);
                 av[0] = t2[0], av[1] = t2[1];
             }
             const bp_f32x2 bv = *reinterpret_cast<const bp_f32x2*>(Ds + kr * DW + wn * 64 + 2 * li);
@@ -356,15 +370,16 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
         if (more) stash((s + 1) & 1);
         __syncthreads();
     }
-    // block (mb, nb), register reg, lane (li, lh): output row m = wm H + MB i + mb with i = (reg & 3) + 8 (reg >> 2) + 4 lh,
-    // output column n = 128 ny + 64 wn + 2 li + nb
-    float* dst = a.part + (size_t)blockIdx.x * XW * 4 * H;
+    // block (mb, nb), register reg, lane (li, lh): output row m = wm HT + MB i + mb with i = (reg & 3) + 8 (reg >> 2) + 4 lh
+    // (hid 256: behind the XW rows of the other half), output column n = 128 ny + 64 wn + 2 li + nb
+    float* dst = a.part + (size_t)blockIdx.x * 2 * H * 4 * H;
+    const int m0 = WIDE ? (int)blockIdx.z * XW : 0;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int i = (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-            const int m = wm * H + MB * i + mb;
+            const int m = m0 + wm * HT + MB * i + mb;
             const int n = DW * ny + 64 * wn + 2 * li;
             *reinterpret_cast<bp_f32x2*>(dst + (size_t)m * 4 * H + n) = bp_f32x2{ acc[mb][0][reg], acc[mb][1][reg] };
         }
@@ -386,7 +401,9 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_kernel(const WGradArgs a)
 template <int H>
 __global__ __launch_bounds__(256, 2) void lstm_wgrad_split_kernel(const WGradArgs a)
 {
-    constexpr int KT = 16, XW = 2 * H, DW = 128, MB = H / 32, NB = 2, NT = 256;
+    constexpr bool WIDE = H == 256;                              // blockIdx.z: the inp half or the h half of [inp | h]
+    constexpr int HT = WIDE ? 128 : H;                           // output rows per wave
+    constexpr int KT = 16, XW = 2 * HT, DW = 128, MB = HT / 32, NB = 2, NT = 256;
     constexpr int NGX = 2 * XW / NT;                             // 8-row groups of X per thread and stage (2 at H = 128, 1 at H = 64)
     constexpr int SQ = 3 * 2 * (XW + DW);                        // 16-byte fragments per stage: [plane][k half][column]
     typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
@@ -412,8 +429,8 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_split_kernel(const WGradArg
 #pragma unroll
     for (int i = 0; i < NGX; ++i) {
         const int g = tid + i * NT, c = g % XW, kg = g / XW;
-        x_is_h[i] = __builtin_amdgcn_readfirstlane((int)(c >= H)) != 0;
-        xoff[i] = x_is_h[i] ? ((c - H) + 8 * kg * H) * 4 : (c + 8 * kg * a.ldi) * 4;
+        x_is_h[i] = WIDE ? blockIdx.z != 0 : __builtin_amdgcn_readfirstlane((int)(c >= H)) != 0;
+        xoff[i] = x_is_h[i] ? ((c - (WIDE ? 0 : H)) + 8 * kg * H) * 4 : (c + 8 * kg * a.ldi) * 4;
         loff[i] = 8 * kg * 4;
     }
     const int doff = (dcol + 8 * dkg * 4 * H) * 4;
@@ -478,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_split_kernel(const WGradArg
         for (int mb = 0; mb < MB; ++mb) {
             ps_u32x4 af[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) af[p] = fx[(p * 2 + lh) * XW + wm * H + 32 * mb + li];
+            for (int p = 0; p < 3; ++p) af[p] = fx[(p * 2 + lh) * XW + wm * HT + 32 * mb + li];
 #pragma unroll
             for (int pb = 0; pb < 3; ++pb)
 #pragma unroll
@@ -491,16 +508,17 @@ __global__ __launch_bounds__(256, 2) void lstm_wgrad_split_kernel(const WGradArg
         fetch(s + 2);
         __syncthreads();
     }
-    // block (mb, nb), register reg, lane (li, lh): output row m = wm H + 32 mb + (reg & 3) + 8 (reg >> 2) + 4 lh, column
-    // n = 128 ny + 64 wn + 32 nb + li
-    float* dst = a.part + (size_t)blockIdx.x * XW * 4 * H;
+    // block (mb, nb), register reg, lane (li, lh): output row m = wm HT + 32 mb + (reg & 3) + 8 (reg >> 2) + 4 lh (hid 256: behind
+    // the XW rows of the other half), column n = 128 ny + 64 wn + 32 nb + li
+    float* dst = a.part + (size_t)blockIdx.x * 2 * H * 4 * H;
+    const int m0 = WIDE ? (int)blockIdx.z * XW : 0;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int m = wm * H + 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                const int m = m0 + wm * HT + 32 * mb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
                 dst[(size_t)m * 4 * H + DW * ny + 64 * wn + 32 * nb + li] = acc[mb][nb][reg];
             }
 }
@@ -599,6 +617,45 @@ static int wgrad_reduce(const float* scratch, int ks, int n, float* dW, int accu
     return rc < 0 ? rc : ks;
 }
 
+// The plan at hid 256 (16 workgroups per slice): config 5's window is 80 x 262 144 rows of 4 KB, and a one-round slice of it lies
+// past the kernels' 32-bit buffer offsets.  ks grows in whole multiples of the one-round count until a slice fits; the slices
+// beyond the workgroup slots run as further rounds (the kernels know nothing of rounds).  64 / 128: wgrad_plan as it is.
+static WGradPlan lstm_wgrad_plan(long long Q, int H, long long row_floats)
+{
+    WGradPlan pl = wgrad_plan(Q, H == 256 ? 16 : 4 * H / 128, row_floats);
+    if (H != 256) return pl;
+    const long long most = (Q + 15) / 16;
+    const int round = pl.ks;
+    for (long long m = 2; !pl.fits && round * m <= most; ++m) {
+        pl.ks = (int)(round * m);
+        pl.per = ((Q + pl.ks - 1) / pl.ks + 15) / 16 * 16;
+        pl.fits = pl.per * row_floats * 4 < (1ll << 31);
+    }
+    return pl;
+}
+
+// ic3_lstm_weight_grad (hid 64 / 128) and ic3_lstm_weight_grad_wide (64 / 128 / 256) behind their hid_size checks
+static int lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const float* dgates, const float* row_live, long long Q,
+                            int H, float* dW, int accumulate, int split, float* scratch, ic3_stream stream)
+{
+    using namespace ic3;
+    if (!inp || !h_prev || !dgates || !dW || !scratch || Q <= 0) return fail(-22, "ic3_lstm_weight_grad: null argument");
+    if (ldi < H || (ldi & 3)) return fail(-22, "ic3_lstm_weight_grad: ldi a multiple of 4, >= hid_size");
+    const WGradPlan pl = lstm_wgrad_plan(Q, H, std::max(ldi, 4 * H));
+    if (!pl.fits) return fail(-22, "ic3_lstm_weight_grad: a K slice must stay below 2 GB per operand (32-bit buffer offsets)");
+    const WGradArgs a{ inp, h_prev, dgates, row_live, scratch, Q, ldi, (int)pl.per };
+    hipStream_t s = (hipStream_t)stream;
+    // split: exact bf16 split products (the rollout's arithmetic), two stages of 3 planes x 2 k halves of 16-byte fragments;
+    // else the fp32 instruction on two stages of 16 rows.  Hid 256: the tile of 128, once per half of [inp | h] (grid z)
+    const auto kernel = split ? (H == 256 ? lstm_wgrad_split_kernel<256> : H == 128 ? lstm_wgrad_split_kernel<128> : lstm_wgrad_split_kernel<64>)
+                              : (H == 256 ? lstm_wgrad_kernel<256> : H == 128 ? lstm_wgrad_kernel<128> : lstm_wgrad_kernel<64>);
+    const int HT = H == 256 ? 128 : H;
+    const size_t lds = split ? (size_t)2 * 3 * 2 * (2 * HT + 128) * 16 : (size_t)2 * 16 * (2 * HT + 128) * sizeof(float);
+    const dim3 grid = H == 256 ? dim3(pl.ks, 8, 2) : dim3(pl.ks, 4 * H / 128);
+    if (const int rc = launch_kernel(kernel, grid, dim3(256), lds, s, a); rc < 0) return rc;
+    return wgrad_reduce(scratch, pl.ks, 2 * H * 4 * H, dW, accumulate, s);
+}
+
 extern "C" size_t ic3_lstm_weight_grad_scratch_floats(long long Q, int H)
 {
     if (Q <= 0 || (H != 64 && H != 128)) return 0;
@@ -608,22 +665,21 @@ extern "C" size_t ic3_lstm_weight_grad_scratch_floats(long long Q, int H)
 extern "C" int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const float* dgates, const float* row_live,
                                     long long Q, int H, float* dW, int accumulate, int split, float* scratch, ic3_stream stream)
 {
-    using namespace ic3;
-    if (!inp || !h_prev || !dgates || !dW || !scratch || Q <= 0) return fail(-22, "ic3_lstm_weight_grad: null argument");
-    if (H != 64 && H != 128) return fail(-38, "ic3_lstm_weight_grad: hid_size 64 / 128");
-    if (ldi < H || (ldi & 3)) return fail(-22, "ic3_lstm_weight_grad: ldi a multiple of 4, >= hid_size");
-    const int ny = 4 * H / 128;
-    const WGradPlan pl = wgrad_plan(Q, ny, std::max(ldi, 4 * H));
-    if (!pl.fits) return fail(-22, "ic3_lstm_weight_grad: a K slice must stay below 2 GB per operand (32-bit buffer offsets)");
-    const WGradArgs a{ inp, h_prev, dgates, row_live, scratch, Q, ldi, (int)pl.per };
-    hipStream_t s = (hipStream_t)stream;
-    // split: exact bf16 split products (the rollout's arithmetic), two stages of 3 planes x 2 k halves of 16-byte fragments;
-    // else the fp32 instruction on two stages of 16 rows
-    const auto kernel = split ? (H == 128 ? lstm_wgrad_split_kernel<128> : lstm_wgrad_split_kernel<64>)
-                              : (H == 128 ? lstm_wgrad_kernel<128> : lstm_wgrad_kernel<64>);
-    const size_t lds = split ? (size_t)2 * 3 * 2 * (2 * H + 128) * 16 : (size_t)2 * 16 * (2 * H + 128) * sizeof(float);
-    if (const int rc = launch_kernel(kernel, dim3(pl.ks, ny), dim3(256), lds, s, a); rc < 0) return rc;
-    return wgrad_reduce(scratch, pl.ks, 2 * H * 4 * H, dW, accumulate, s);
+    if (H != 64 && H != 128) return ic3::fail(-38, "ic3_lstm_weight_grad: hid_size 64 / 128");
+    return lstm_weight_grad(inp, ldi, h_prev, dgates, row_live, Q, H, dW, accumulate, split, scratch, stream);
+}
+
+extern "C" size_t ic3_lstm_weight_grad_wide_scratch_floats(long long Q, int H, int ldi)
+{
+    if (Q <= 0 || (H != 64 && H != 128 && H != 256)) return 0;
+    return (size_t)lstm_wgrad_plan(Q, H, std::max(ldi, 4 * H)).ks * 2 * H * 4 * H;
+}
+
+extern "C" int ic3_lstm_weight_grad_wide(const float* inp, int ldi, const float* h_prev, const float* dgates, const float* row_live,
+                                         long long Q, int H, float* dW, int accumulate, int split, float* scratch, ic3_stream stream)
+{
+    if (H != 64 && H != 128 && H != 256) return ic3::fail(-38, "ic3_lstm_weight_grad_wide: hid_size 64 / 128 / 256");
+    return lstm_weight_grad(inp, ldi, h_prev, dgates, row_live, Q, H, dW, accumulate, split, scratch, stream);
 }
 
 // ---- ic3_bptt_backward -------------------------------------------------------------------------------------------------------

@@ -322,7 +322,7 @@ def _scratch(work, key, n, device):
 
 
 def lstm_weight_grad(inp, h_prev, dgates, dW, row_live=None, accumulate=True, work=None, split=True):
-    """ic3_lstm_weight_grad: dW (2H, 4H) (+)= [inp | h_prev]^T @ dgates over all Q rows of a window of recorded steps in one
+    """ic3_lstm_weight_grad_wide: dW (2H, 4H) (+)= [inp | h_prev]^T @ dgates over all Q rows of a window of recorded steps in one
     launch.  inp (Q, >= H) rows with unit column stride (the first H floats count: the record's [inp | h] rows), h_prev (Q, H),
     dgates (Q, 4H) contiguous; leading dims may be (T, R).  split (default): exact bf16 split products on the bf16 matrix cores
     (the rollout's gate_split arithmetic); False: the fp32 matrix instruction."""
@@ -335,12 +335,12 @@ def lstm_weight_grad(inp, h_prev, dgates, dW, row_live=None, accumulate=True, wo
     assert dW.is_contiguous() and tuple(dW.shape) == (2 * H, 4 * H)
     if row_live is not None:
         assert row_live.is_contiguous() and row_live.dtype == torch.float32 and row_live.numel() == Q
-    n = int(_lib.lib().ic3_lstm_weight_grad_scratch_floats(Q, H))
+    n = int(_lib.lib().ic3_lstm_weight_grad_wide_scratch_floats(Q, H, inp2.stride(0)))
     if n == 0:
-        raise NotImplementedError("lstm_weight_grad: hid_size 64 / 128")
-    check(_lib.lib().ic3_lstm_weight_grad(ptr(inp2), inp2.stride(0), ptr(h_prev), ptr(dgates), ptr(row_live), Q, H, ptr(dW),
-                                          int(bool(accumulate)), int(bool(split)), ptr(_scratch(work, 'wgrad', n, dgates.device)),
-                                          stream()))
+        raise NotImplementedError("lstm_weight_grad: hid_size 64 / 128 / 256")
+    check(_lib.lib().ic3_lstm_weight_grad_wide(ptr(inp2), inp2.stride(0), ptr(h_prev), ptr(dgates), ptr(row_live), Q, H, ptr(dW),
+                                               int(bool(accumulate)), int(bool(split)), ptr(_scratch(work, 'wgrad', n, dgates.device)),
+                                               stream()))
 
 
 def first_chain_envs(E, N):

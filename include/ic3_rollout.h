@@ -417,16 +417,26 @@ int ic3_comm_backward(const float* dxh, int ldd, const float* h_prev, const int3
  * mode: h_prev rows times it).  scratch: ic3_lstm_weight_grad_scratch_floats(Q, H) floats.  split != 0 (what ic3net_amd passes
  * with args.gate_split, the default): every fp32 operand split exactly into three bf16 terms, all nine cross products on the bf16
  * matrix cores, fp32 accumulation — the arithmetic of the rollout's gate product (ic3_policy.gate_split); split == 0: the fp32 matrix
- * instruction.  Exact products either way, split-K over the CUs, slices summed in order (reproducible).  hid_size 64 / 128 (at 256
- * ic3net_amd forms the same two products, inp^T . dgates and (row_live h_prev)^T . dgates, as library GEMMs over the window). */
+ * instruction.  Exact products either way, split-K over the CUs, slices summed in order (reproducible).  hid_size 64 / 128 (256:
+ * the _wide pair below; the query here answers 0 and the call -ENOSYS there). */
 size_t ic3_lstm_weight_grad_scratch_floats(long long Q, int H);
 int ic3_lstm_weight_grad(const float* inp, int ldi, const float* h_prev, const float* dgates, const float* row_live /* or NULL */,
                          long long Q, int H, float* dW, int accumulate, int split, float* scratch, ic3_stream stream);
 
+/* The same call for hid_size 64 / 128 / 256 (added beside the pair above, whose contract stays).  At 64 / 128: the launches of
+ * ic3_lstm_weight_grad, the same bits.  At 256 a workgroup takes one half of [inp | h_prev] (256 output rows) x 128 dgates columns,
+ * and the K slices are as many whole rounds of workgroups as keep a slice's rows x max(ldi, 4H) floats below 2 GB — so the scratch
+ * query takes ldi too: ic3_lstm_weight_grad_wide_scratch_floats(Q, H, ldi) floats (0: hid_size not supported).  row_live scales the
+ * h_prev rows on the way in; dgates is only read.  Returns the number of K slices (scratch floats / (2H x 4H)), negative errno on
+ * error (-ENOSYS: hid_size; -EINVAL: a null argument, ldi < H or not a multiple of 4, a 16-row slice past 2 GB). */
+size_t ic3_lstm_weight_grad_wide_scratch_floats(long long Q, int H, int ldi);
+int ic3_lstm_weight_grad_wide(const float* inp, int ldi, const float* h_prev, const float* dgates, const float* row_live /* or NULL */,
+                              long long Q, int H, float* dW, int accumulate, int split, float* scratch, ic3_stream stream);
+
 /* The backward through a window of T recorded steps (trainer.py:128-225 over comm.py:134-244, one communication pass, recorded
  * gates), last step first, as ONE host call — per step: ic3_lstm_gates_backward_given (in place on the gate record, the heads'
  * share folded in, the input gradient in the same launch) -> ic3_comm_backward -> ic3_env_encode_backward_accumulate on the step's
- * snapshot; nothing runs on the host between the launches.  Afterwards the caller runs ic3_lstm_weight_grad (hid 64 / 128) over the window
+ * snapshot; nothing runs on the host between the launches.  Afterwards the caller runs ic3_lstm_weight_grad (hid 256: ic3_lstm_weight_grad_wide) over the window
  * (gates now holds dgates), ic3_heads_grad, ic3_env_encode_backward_finish and sums the partials.
  *   gates [T][R][4H] in: the recorded activated gates, out: dgates;  hs, cs [>= T][R][H] the state ENTERING every step;
  *   dhead [T][R][OT];  snaps: T snapshots, snap_words int32 apart;  alive / gate: HOST arrays of T device pointers ([E][N] int32,

@@ -1,6 +1,7 @@
 """The update half's hand-written launches alone, at a BASELINE shape (default PP-hard: E = 8192, N = 10, H = 128):
 ic3_comm_backward per step, ic3_lstm_weight_grad per window of T steps, ic3_lstm_gates_backward_given (in place, heads folded in).
-python tools/microbench_bptt.py [E] [N] [H] [T]"""
+python tools/microbench_bptt.py [E] [N] [H] [T]      (H = 256: config 5 is `8192 32 256 8`, about 13 GB of operands; the weight
+gradient's kernels beside the two library products of bptt._weight_grad_products)"""
 import os
 import sys
 
@@ -9,18 +10,27 @@ import torch
 from ic3net_amd import ops
 
 
-def timeit(name, fn, n=20, flop=None, nbytes=None):
+def timeit(name, fn, n=20, flop=None, nbytes=None, each=False):
+    """Mean of n calls between two HIP events behind 3 warm-up calls; each: an event pair per call, the median (min .. max printed)."""
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1 if each else 2)]
+    ev[0].record()
+    for i in range(n):
         fn()
-    e1.record()
+        if each:
+            ev[i + 1].record()
+    if not each:
+        ev[1].record()
     torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / n
     extra = ""
+    if each:
+        reps = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(n))
+        ms = reps[n // 2]
+        extra += "  (%d repetitions: %.3f .. %.3f)" % (n, reps[0], reps[-1])
+    else:
+        ms = ev[0].elapsed_time(ev[1]) / n
     if flop:
         extra += "  %.1f TFLOP/s (%.3f of the fp32 matrix peak 157.3)" % (flop / ms / 1e9, flop / ms / 1e9 / 157.3)
     if nbytes:
@@ -59,13 +69,23 @@ def main():
     timeit("  (rounds 3-5: 2 masked means + 2 library products)", old)
     # weight gradient of a window
     Q = T * R
-    xh, hs, dg = g(T, R, 2 * H), g(T, R, H), g(T, R, 4 * H)
+    # (hid 256: the record keeps inp at row stride H; 64 / 128: the first half of its [inp | h] rows)
+    xh, hs, dg = g(T, R, H if H == 256 else 2 * H), g(T, R, H), g(T, R, 4 * H)
     dW = torch.zeros((2 * H, 4 * H), device=dev)
     work = {}
-    timeit("ic3_lstm_weight_grad, bf16 x 9 (T %d: Q = %d rows)" % (T, Q), lambda: ops.lstm_weight_grad(xh, hs, dg, dW, work=work), n=5,
-           flop=2 * Q * 2 * H * 4 * H, nbytes=Q * (4 * H * 4 + 2 * H * 4))
+    wflop, wbytes = 2 * Q * 2 * H * 4 * H, Q * (4 * H * 4 + 2 * H * 4)
+    ms9 = timeit("ic3_lstm_weight_grad, bf16 x 9 (T %d: Q = %d rows)" % (T, Q), lambda: ops.lstm_weight_grad(xh, hs, dg, dW, work=work),
+                 n=5, flop=wflop, nbytes=wbytes, each=True)
     timeit("ic3_lstm_weight_grad, fp32 instruction", lambda: ops.lstm_weight_grad(xh, hs, dg, dW, work=work, split=False), n=5,
-           flop=2 * Q * 2 * H * 4 * H, nbytes=Q * (4 * H * 4 + 2 * H * 4))
+           flop=wflop, nbytes=wbytes, each=True)
+    if H == 256:
+        # what the kernel replaces at 256 (args.lstm_wgrad_kernel=False): the two library products, on the same tensors
+        from types import SimpleNamespace
+        from ic3net_amd import bptt
+        rec = SimpleNamespace(xh=xh, hs=hs, gates=dg)
+        mslib = timeit("  bptt._weight_grad_products (two library products)", lambda: bptt._weight_grad_products(rec, T, R, H, dW, None),
+                       n=5, flop=wflop, nbytes=wbytes, each=True)
+        print("  bf16 x 9 kernel / library pair: %.3f" % (ms9 / mslib))
     wpart = torch.zeros((8, 2 * H, 4 * H), device=dev)
     xcat = torch.cat([xh[0][:, :H], hs[0]], 1).contiguous()
 
