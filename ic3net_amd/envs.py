@@ -48,7 +48,7 @@ class _BatchedEnv(object):
         self.stat = dict()
         self.episode_over = False
         self.obs_timer = None     # set to a list to collect (start, end) HIP events around every obs launch
-        self.step_timer = None    # likewise around every one-launch policy+step (Trainer._step_body_mega)
+        self.step_timer = None    # likewise around every one-launch policy+step (Trainer._arm_step_timer)
         self.dispatch_events = False   # step_timer pairs stamped by the dispatch (DispatchEvent) instead of records
         self.out = None           # optional {'reward','done','alive','is_completed'} output tensors for step()
         self._last = None

@@ -15,6 +15,7 @@ Differences forced by batching:
 import gc
 from collections import namedtuple
 from collections.abc import Sequence
+from contextlib import contextmanager
 from inspect import signature
 
 import torch
@@ -23,6 +24,7 @@ from torch import optim
 from .action_utils import SampleClock, select_action, translate_action
 from .action_utils import select_action as _select_action_default     # tests monkeypatch `select_action` (action tapes)
 from . import bptt, ops
+from .envs import DispatchEvent
 from .utils import merge_stat
 
 Transition = namedtuple('Transition', ('state', 'action', 'action_out', 'value', 'episode_mask', 'episode_mini_mask',
@@ -134,19 +136,9 @@ class Trainer(object):
         g = self._graphs.get('episode')
         if g is None:
             graph = torch.cuda.CUDAGraph()
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            gc.collect()                                           # (no collection inside a capture: see step_episode)
-            gc_was_on = gc.isenabled()
-            gc.disable()
-            try:
-                with torch.cuda.graph(graph, pool=self._graph_pool, capture_error_mode="thread_local"):
-                    for t in range(T):
-                        self._step_body(t, observe=self._dense_obs())
-            finally:
-                if gc_was_on:
-                    gc.enable()
-            self._graph_gen = getattr(self.policy_net, 'cache_generation', 0)
+            with self._capturing(graph, collect=True):
+                for t in range(T):
+                    self._step_body(t, observe=self._dense_obs())
             g = self._graphs['episode'] = dict(graph=graph, outputs=(self._state, self._info, self._prev_hid, list(self._step_out)),
                                                mega=bool(getattr(self, '_mega_last', False)))
         self.clock.t = T - 1
@@ -155,6 +147,32 @@ class Trainer(object):
         self._step_out = list(step_out)
         self._nsteps = T
         self._mega_last = g['mega']                                # (what the captured steps went through)
+
+    @contextmanager
+    def _capturing(self, graph, collect):
+        """Capture what the body launches into `graph` (the trainer's one memory pool; the graphs are stale once the policy's
+        cache_generation moves on from the one noted here)."""
+        if self._graph_pool is None:
+            self._graph_pool = torch.cuda.graph_pool_handle()
+        # No Python garbage collection INSIDE a capture: a cycle collected there may own device resources of something
+        # long dead (another Trainer's graphs, tensors, events) and releasing them (hipFree, hipGraphDestroy, ...) from
+        # the capturing thread invalidates the capture — "operation failed due to a previous error during capture" at an
+        # arbitrary step of a long-lived process, after which the process is not recoverable (round 4: the GPU suite at
+        # step 53 / 66 of one test, depending on how much the tests before it had allocated).  torch.cuda.graph itself
+        # stopped collecting in its __enter__ (torch 2.10: only under torch.compiler.config.force_cudagraph_gc), so
+        # collect once in front of an episode's first capture (`collect`) and keep the collector off while capturing.
+        if collect:
+            gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            # thread_local: calls made by other threads (e.g. an RCCL watchdog) must not invalidate the capture
+            with torch.cuda.graph(graph, pool=self._graph_pool, capture_error_mode="thread_local"):
+                yield
+        finally:
+            if gc_was_on:
+                gc.enable()
+        self._graph_gen = getattr(self.policy_net, 'cache_generation', 0)
 
     def _auto_reset(self):
         """args.auto_reset: an env that finishes restarts inside the step launch and keeps producing transitions
@@ -322,14 +340,12 @@ class Trainer(object):
             and (ok is None or ok())
 
     def _mega_expected(self, raw):
-        """Will step_episode go through ic3_policy_step?  (no autograd, default sampling, a policy that supports the
-        env: the same conditions _step_body tests, evaluated before the episode starts)"""
+        """Will step_episode go through ic3_policy_step?  (_launch_path_base as _step_body asks it, evaluated before the
+        episode starts, and a policy that supports the env; this launch tolerates args.store_states)"""
         a = self.args
-        if getattr(a, 'rollout_grad', False) or not a.recurrent or self.clock.env is not raw \
-                or select_action is not _select_action_default:
-            return False
         ok = getattr(self.policy_net, 'mega_supported', None)
-        return bool(ok(raw)) if ok is not None else False
+        return self._launch_path_base(raw, getattr(a, 'rollout_grad', False), allow_store=True) and bool(a.recurrent) \
+            and ok is not None and bool(ok(raw))
 
     def _dense_obs(self):
         """args.dense_obs=False skips the obs-assembly launch when nothing consumes the dense observation (sparse
@@ -364,29 +380,12 @@ class Trainer(object):
                                                   (self._mega_now() and self._fused_obs()))
             saved = (self._state, self._info, self._prev_hid)
             graph = torch.cuda.CUDAGraph()
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            # thread_local: calls made by other threads (e.g. an RCCL watchdog) must not invalidate the capture
             timer, raw.obs_timer = raw.obs_timer, None        # no event records inside a capture
-            # No Python garbage collection INSIDE a capture: a cycle collected there may own device resources of something
-            # long dead (another Trainer's graphs, tensors, events) and releasing them (hipFree, hipGraphDestroy, ...) from
-            # the capturing thread invalidates the capture — "operation failed due to a previous error during capture" at an
-            # arbitrary step of a long-lived process, after which the process is not recoverable (round 4: the GPU suite at
-            # step 53 / 66 of one test, depending on how much the tests before it had allocated).  torch.cuda.graph itself
-            # stopped collecting in its __enter__ (torch 2.10: only under torch.compiler.config.force_cudagraph_gc), so
-            # collect once in front of an episode's first capture and keep the collector off while capturing.
-            if not self._graphs:
-                gc.collect()
-            gc_was_on = gc.isenabled()
-            gc.disable()
             try:
-                with torch.cuda.graph(graph, pool=self._graph_pool, capture_error_mode="thread_local"):
+                with self._capturing(graph, collect=not self._graphs):
                     self._step_body(t, observe=in_graph_obs)
             finally:
                 raw.obs_timer = timer
-                if gc_was_on:
-                    gc.enable()
-            self._graph_gen = getattr(self.policy_net, 'cache_generation', 0)
             g = self._graphs[t] = dict(graph=graph, obs_inside=in_graph_obs, inputs=saved,
                                        outputs=(self._state, self._info, self._prev_hid, self._step_out[t]))
             # capture does not execute: fall through to a replay so that step t actually runs
@@ -404,130 +403,151 @@ class Trainer(object):
         self._state, self._info, self._prev_hid, self._step_out[t] = g['outputs']
         self._nsteps = t + 1
 
+    def _launch_path_base(self, raw, grad, allow_store=False):
+        """What every one-launch rollout step asks before its own questions (the policy's, the step's tensors): no autograd
+        (`grad`: args.rollout_grad in front of an episode, torch.is_grad_enabled() inside a step), the env handle the sample
+        clock draws on, the default select_action, and no args.store_states unless the launch tolerates it."""
+        return not grad and raw is not None and self.clock.env is raw and select_action is _select_action_default \
+            and (allow_store or not getattr(self.args, 'store_states', False))
+
+    def _first_hidden(self, state, cont):
+        """(h, c) an LSTM policy enters step 0 with (trainer.py:50-51).  `cont`: the window continues E running streams."""
+        inplace = self._rec is not None and not torch.is_grad_enabled() and self._rec_inplace()
+        if cont:
+            # (h, c) the previous window ended with -> slot 0 of this window's record (fresh rows are zeroed inside the
+            # launch: an env whose t == 0 starts an episode)
+            return self._rec.start_from(*self._prev_hid) if inplace else self._prev_hid
+        if inplace:
+            return self._rec.start()           # native update on the one-launch path: the episode record itself holds the state
+        if getattr(self, '_mega_prev', False) and not torch.is_grad_enabled() and hasattr(self.policy_net, 'zero_hidden'):
+            # the previous step went through the one-launch path: hand it its own buffers, zeroed
+            return self.policy_net.zero_hidden(state.shape[0], state.device)
+        return self.policy_net.init_hidden(batch_size=state.shape[0])
+
     def _step_body(self, t, observe=True):
-        args = self.args
+        args, net = self.args, self.policy_net
         state, info, buf = self._state, self._info, self._buf
-        store = bool(getattr(args, 'store_states', False))
+        raw = self.env.env
         self.clock.t = t
         with torch.set_grad_enabled(bool(getattr(args, 'rollout_grad', False))):
+            grad = torch.is_grad_enabled()
             cont = t == 0 and self._stream_continues()            # collection mode: the window continues E running streams
             if t == 0 and args.hard_attn and args.commnet and not cont:   # trainer.py:45-46 (quirk Q22)
                 info['comm_action'] = self._zeros_comm
-            if torch.is_grad_enabled() and getattr(self.policy_net, 'obs_env', None) is None:
+            if grad and getattr(net, 'obs_env', None) is None:
                 state = state.clone()          # the env reuses its obs buffer; autograd keeps the encoder input
-            if args.recurrent:                                     # trainer.py:49-60
-                if args.rnn_type == 'LSTM' and t == 0 and cont:
-                    if self._rec is not None and self._rec_inplace():
-                        # (h, c) the previous window ended with -> slot 0 of this window's record (fresh rows are zeroed
-                        # inside the launch: an env whose t == 0 starts an episode)
-                        self._prev_hid = self._rec.start_from(*self._prev_hid)
-                elif args.rnn_type == 'LSTM' and t == 0:
-                    if self._rec is not None and not torch.is_grad_enabled() and self._rec_inplace():
-                        # native update on the one-launch path: the episode record itself holds the recurrent state
-                        self._prev_hid = self._rec.start()
-                    elif getattr(self, '_mega_prev', False) and not torch.is_grad_enabled() \
-                            and hasattr(self.policy_net, 'zero_hidden'):
-                        # the previous step went through the one-launch path: hand it its own buffers, zeroed
-                        self._prev_hid = self.policy_net.zero_hidden(state.shape[0], state.device)
-                    else:
-                        self._prev_hid = self.policy_net.init_hidden(batch_size=state.shape[0])
-                fuse_draw = not torch.is_grad_enabled() and self.clock.env is not None \
-                    and hasattr(self.policy_net, 'sample_into') and select_action is _select_action_default
-                raw = self.env.env
-                if self._rec is not None:                          # (h, c) entering step t, env state, masks
-                    self._rec.record(t, self.policy_net, raw, self._prev_hid, info)
-                if fuse_draw and self.clock.env is raw and getattr(self.policy_net, 'mega_ok', None) is not None \
-                        and self.policy_net.mega_ok(raw, [state, self._prev_hid]):
+            if args.recurrent and args.rnn_type == 'LSTM' and t == 0:   # trainer.py:49-51
+                self._prev_hid = self._first_hidden(state, cont)
+            if self._rec is not None:          # native update: (h, c) entering step t, env snapshot, masks
+                self._rec.record(t, net, raw, self._prev_hid if args.recurrent else None, info)
+
+            def asks(name, x):                 # the policy's own answer for this step's tensors
+                return getattr(net, name, None) is not None and getattr(net, name)(raw, x)
+            if args.recurrent:
+                if self._launch_path_base(raw, grad, allow_store=True) and asks('mega_ok', [state, self._prev_hid]):
                     return self._step_body_mega(t, observe)
-                if not torch.is_grad_enabled() and self.clock.env is raw and self.clock.env is not None and not store \
-                        and select_action is _select_action_default and args.rnn_type != 'LSTM' \
-                        and getattr(self.policy_net, 'rnn_step_ok', None) is not None \
-                        and self.policy_net.rnn_step_ok(raw, [state, self._prev_hid]):
+                if self._launch_path_base(raw, grad) and args.rnn_type != 'LSTM' and asks('rnn_step_ok', [state, self._prev_hid]):
                     return self._step_body_rnn(t, observe)         # models.RNN, tanh recurrence: one launch too (round 6)
-                self._refresh_skipped_reset_obs(raw, t)
-                if self._auto_reset():
-                    raise NotImplementedError("args.auto_reset needs the one-launch rollout step (ic3_policy_step: "
-                                              "recurrent CommNet/IC3Net, hid_size 64/128/256, no autograd): per-env "
-                                              "episode starts are handled inside that launch")
+            elif self._launch_path_base(raw, grad) and asks('commnet_step_ok', state):
+                return self._step_body_commnet(t, observe)
+
+            # the launch chain: policy forward, draw, env.step as launches of their own
+            self._refresh_skipped_reset_obs(raw, t)
+            if self._auto_reset():
+                raise NotImplementedError(
+                    "args.auto_reset needs the one-launch rollout step (ic3_policy_step: "
+                    "recurrent CommNet/IC3Net, hid_size 64/128/256, no autograd): per-env "
+                    "episode starts are handled inside that launch" if args.recurrent else
+                    "args.auto_reset needs the one-launch rollout step (ic3_commnet_step: hid_size "
+                    "64/128/256, no autograd): per-env episode starts are handled inside that launch")
+            if args.recurrent:                                     # trainer.py:52-60
+                fuse_draw = not grad and self.clock.env is not None and hasattr(net, 'sample_into') \
+                    and select_action is _select_action_default
                 if fuse_draw:
-                    self.policy_net.sample_into = (self.clock.env, buf['action'][t])
+                    net.sample_into = (self.clock.env, buf['action'][t])
                 try:
-                    action_out, value, prev_hid = self.policy_net([state, self._prev_hid], info)
+                    action_out, value, prev_hid = net([state, self._prev_hid], info)
                 finally:
                     if fuse_draw:
-                        self.policy_net.sample_into = None
+                        net.sample_into = None
                 if (t + 1) % args.detach_gap == 0:                 # trainer.py:56-60
                     prev_hid = (prev_hid[0].detach(), prev_hid[1].detach()) if args.rnn_type == 'LSTM' \
                         else prev_hid.detach()
                 self._prev_hid = prev_hid
             else:
-                raw = self.env.env
-                if self._rec is not None:                          # native update: env snapshot + masks of step t
-                    self._rec.record(t, self.policy_net, raw, None, info)
-                if not torch.is_grad_enabled() and self.clock.env is raw and self.clock.env is not None \
-                        and select_action is _select_action_default and not store \
-                        and getattr(self.policy_net, 'commnet_step_ok', None) is not None \
-                        and self.policy_net.commnet_step_ok(raw, state):
-                    return self._step_body_commnet(t, observe)
-                self._refresh_skipped_reset_obs(raw, t)
-                if self._auto_reset():
-                    raise NotImplementedError("args.auto_reset needs the one-launch rollout step (ic3_commnet_step: hid_size "
-                                              "64/128/256, no autograd): per-env episode starts are handled inside that launch")
-                action_out, value = self.policy_net(state, info)
-            if getattr(self.policy_net, 'sampled', False):                               # drawn by the policy launch
-                self.policy_net.sampled = False
+                action_out, value = net(state, info)
+            if getattr(net, 'sampled', False):                                           # drawn by the policy launch
+                net.sampled = False
                 action = buf['action'][t]
             else:
                 action = select_action(args, action_out, self.clock, out=buf['action'][t])   # trainer.py:65
             action, actual = translate_action(args, self.env, action)                    # trainer.py:66
-            cur_state = state.clone() if store else None
-            raw = self.env.env
+            cur_state = state.clone() if getattr(args, 'store_states', False) else None
             raw.out = dict(reward=buf['reward'][t], done=buf['done'][t], alive=buf['alive'][t],
                            is_completed=buf['is_completed'][t])
-            try:
-                if observe:
-                    next_state, reward, done, info = self.env.step(actual)               # trainer.py:67
-                else:
-                    next_state, reward, done, info = self.env.step(actual, observe=False)
+            try:                                                                         # trainer.py:67
+                next_state, _, _, info = self.env.step(actual) if observe else self.env.step(actual, observe=False)
             finally:
                 raw.out = None
-            info = dict(info)
-            if args.hard_attn and args.commnet:                    # trainer.py:70-71 (gate for the NEXT step)
-                info['comm_action'] = action[-1] if not args.comm_action_one else self._ones_comm
-            if getattr(self, '_should_display', False):            # trainer.py:101-102
-                self.env.display()
-            self._step_out[t] = (cur_state, action_out, value, next_state.clone() if store else None)
-            self._state = next_state
-            self._info = info
-            self._nsteps = t + 1
+            self._commit_step(t, action_out, value, dict(info), next_state, action, cur_state)
 
-    @staticmethod
-    def _step_timer(raw):
-        """The list the one-launch step appends its (start, stop, t) HIP events to, or None: `raw.step_timer` on every
-        `raw.step_timer_every`-th call (bench.py: stamping both events costs ~10 us per launch, so it samples)."""
+    def _commit_step(self, t, action_out, value, info, next_state, action, cur_state=None):
+        """The end of every step body: the gate of the NEXT step, display, and what the step leaves behind."""
+        args = self.args
+        if args.hard_attn and args.commnet:                        # trainer.py:70-71
+            info['comm_action'] = action[-1] if not args.comm_action_one else self._ones_comm
+        if getattr(self, '_should_display', False):                # trainer.py:101-102
+            self.env.display()
+        self._step_out[t] = (cur_state, action_out, value, next_state.clone() if getattr(args, 'store_states', False) else None)
+        self._state = next_state
+        self._info = info
+        self._nsteps = t + 1
+
+    def _after_launch(self, t, action_out, value, cur_state=None):
+        """The end of the three one-launch step bodies: the launch wrote step t's slices of the episode buffers and (with or
+        behind it) the env's observation rows."""
+        buf, raw = self._buf, self.env.env
+        self._mega_last = True                                     # (the reset obs launch may be skipped: step 0 writes the rows)
+        next_state = self.env._flatten_obs(raw._obs) if hasattr(self.env, '_flatten_obs') else raw._obs
+        if raw.dims.kind == 2:                                     # TJ:244-247
+            info = {'alive_mask': buf['alive'][t], 'is_completed': buf['is_completed'][t]}
+        else:
+            info = {'alive_mask_device': buf['alive'][t]}
+        self._commit_step(t, action_out, value, info, next_state, buf['action'][t], cur_state)
+
+    def _arm_step_timer(self, raw, t, around=False):
+        """bench.py's per-launch times: on every `raw.step_timer_every`-th call (stamping both events costs ~10 us per launch,
+        so it samples) the coming one-launch step gets a (start, stop, t) sample in the list `raw.step_timer`, its events
+        stamped by the dispatch of the launch itself.  The LSTM step (`around`) gets back the call that completes the sample
+        BEHIND its launch: where the handle does not ask for `raw.dispatch_events`, torch events are recorded around it."""
         timer = getattr(raw, 'step_timer', None)
         if timer is None:
             return None
         tick = getattr(raw, '_step_timer_tick', 0)
         raw._step_timer_tick = tick + 1
-        return timer if tick % max(1, int(getattr(raw, 'step_timer_every', 1))) == 0 else None
+        if tick % max(1, int(getattr(raw, 'step_timer_every', 1))) != 0:
+            return None
+        stamped = not around or getattr(raw, 'dispatch_events', False)
+        if stamped:
+            e0, e1 = DispatchEvent(), DispatchEvent()
+            raw.set_step_events(e0, e1)
+        else:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(torch.cuda.current_stream())
+
+        def finish():
+            if not stamped:
+                e1.record(torch.cuda.current_stream())
+            timer.append((e0, e1, t))
+        return finish if around else finish()
 
     def _step_body_mega(self, t, observe):
         """The same iteration as _step_body through CommNetMLP.step_env (ic3_policy_step): policy forward, the action
         draws of every head and env.step are ONE launch; the obs-assembly launch follows when `observe`."""
-        args, buf, state, info = self.args, self._buf, self._state, self._info
+        buf, state, info = self._buf, self._state, self._info
         raw = self.env.env
-        store = bool(getattr(args, 'store_states', False))
-        cur_state = state.clone() if store else None
-        timer = self._step_timer(raw)                              # bench: HIP events around the one launch
-        stamped = timer is not None and getattr(raw, 'dispatch_events', False)
-        if stamped:                                                # ... stamped by the dispatch itself
-            from .envs import DispatchEvent
-            e0, e1 = DispatchEvent(), DispatchEvent()
-            raw.set_step_events(e0, e1)
-        elif timer is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream())
+        cur_state = state.clone() if getattr(self.args, 'store_states', False) else None
+        timed = self._arm_step_timer(raw, t, around=True)          # bench: HIP events around the one launch
         # next_state rows are written by the same launch (args.fused_obs, default) unless they are wanted on a second
         # stream (args.overlap_obs) — ic3_policy_step falls back to a separate obs launch by itself when the obs
         # descriptors of a tile do not fit in LDS
@@ -540,57 +560,37 @@ class Trainer(object):
         if rec_out is not None and self._rec.gates is not None:
             extra['record_out'] = (self._rec.gates[t], self._rec.xh[t])   # + the cell's gates, inp rows (bptt: no gate product later)
             self._rec.gates_n += 1
-        action_out, value, prev_hid = self.policy_net.step_env(
+        action_out, value, self._prev_hid = self.policy_net.step_env(      # (no autograd here: detach_gap is moot)
             raw, [state, self._prev_hid], info, action=buf['action'][t], reward=buf['reward'][t], done=buf['done'][t],
             alive=buf['alive'][t], is_completed=buf['is_completed'][t], obs=raw._obs if fused else None,
             hidden_out=rec_out, out=out_buf, **extra)
-        self._mega_last = True
-        if timer is not None:
-            if not stamped:
-                e1.record(torch.cuda.current_stream())
-            timer.append((e0, e1, t))
-        self._prev_hid = prev_hid                                  # no autograd here: detach_gap is moot
+        if timed is not None:
+            timed()
         if observe and not fused:
             if self._overlap_obs() and not torch.cuda.is_current_stream_capturing():
                 self._observe_on_side_stream(raw)                  # obs(t) on a second stream, beside step t+1
             else:
                 raw.observe_timed()
-        next_state = self.env._flatten_obs(raw._obs) if hasattr(self.env, '_flatten_obs') else raw._obs
-        if raw.dims.kind == 2:                                     # TJ:244-247
-            info = {'alive_mask': buf['alive'][t], 'is_completed': buf['is_completed'][t]}
-        else:
-            info = {'alive_mask_device': buf['alive'][t]}
-        if args.hard_attn and args.commnet:                        # trainer.py:70-71 (gate for the NEXT step)
-            info['comm_action'] = buf['action'][t][-1] if not args.comm_action_one else self._ones_comm
-        if getattr(self, '_should_display', False):                # trainer.py:101-102
-            self.env.display()
-        self._step_out[t] = (cur_state, action_out, value, next_state.clone() if store else None)
-        self._state = next_state
-        self._info = info
-        self._nsteps = t + 1
+        self._after_launch(t, action_out, value, cur_state)
 
     def _static_out(self, t, state):
         """hipGraph mode: the launch's [log-probs | value] rows of every step index live in one static buffer, so a captured
         step allocates nothing (allocator traffic inside a capture is avoidable risk — it is what moved the failing step of
-        the garbage-collection problem described in step_episode from 53 to 66).  The buffer is shared by ALL episodes
+        the garbage-collection problem described in _capturing from 53 to 66).  The buffer is shared by ALL episodes
         played in graph mode: action_out / value of a Transition are views of it and are overwritten by the next episode —
         graph-mode rollouts feed statistics, never an update (_use_graph() is False while records are collected, and
         compute_grad refuses a no-grad batch).  Eager mode: None (a fresh tensor per call, a Transition keeps its action_out)."""
-        if self._rec is not None and not self._use_graph():
+        graph, rec, args = self._use_graph(), self._rec, self.args
+        if rec is None and not graph:
+            return None
+        shape = (args.max_steps, state.shape[0] * args.nagents, sum(int(o) for o in args.naction_heads) + 1)
+        if not graph:
             # native update: the rows of every step of the episode in ONE buffer of its record — compute_grad's losses then read
             # them in place (ic3_loss_gradients) instead of stacking T x heads views
-            rec = self._rec
-            OT = sum(int(o) for o in self.args.naction_heads) + 1
             if rec.out is None:
-                rec.out = torch.empty((self.args.max_steps, state.shape[0] * self.args.nagents, OT), dtype=torch.float32,
-                                      device=state.device)
+                rec.out = torch.empty(shape, dtype=torch.float32, device=state.device)
             rec.out_n += 1
             return rec.out[t]
-        if not self._use_graph():
-            return None
-        args = self.args
-        OT = sum(int(o) for o in args.naction_heads) + 1
-        shape = (args.max_steps, state.shape[0] * args.nagents, OT)
         ob = self._static.get('out')
         if ob is None or tuple(ob.shape) != shape:
             ob = self._static['out'] = torch.empty(shape, dtype=torch.float32, device=state.device)
@@ -608,37 +608,19 @@ class Trainer(object):
         """The iteration of _step_body for the NON-recurrent CommNet module through CommNetMLP.step_env_commnet
         (ic3_commnet_step): sparse encoder, communication passes, heads, the draws of every head, env.step and the dense obs
         rows of the state acted on are ONE launch."""
-        args, buf, state, info = self.args, self._buf, self._state, self._info
+        buf, state = self._buf, self._state
         raw = self.env.env
-        timer = self._step_timer(raw)                              # bench: HIP events stamped by the dispatch of the launch
-        if timer is not None:
-            from .envs import DispatchEvent
-            e0, e1 = DispatchEvent(), DispatchEvent()
-            raw.set_step_events(e0, e1)
-            timer.append((e0, e1, t))
+        self._arm_step_timer(raw, t)
         kw = dict()
         rec = self._rec
         if rec is not None and rec.h_fin is not None and rec.h_fin_n == t:   # (models.MLP's record: h of step t -> slot t)
             kw['h_out'] = rec.h_fin[t]
         action_out, value = self.policy_net.step_env_commnet(
-            raw, state, info, action=buf['action'][t], reward=buf['reward'][t], done=buf['done'][t], alive=buf['alive'][t],
+            raw, state, self._info, action=buf['action'][t], reward=buf['reward'][t], done=buf['done'][t], alive=buf['alive'][t],
             is_completed=buf['is_completed'][t], obs=raw._obs if observe else None, out=self._static_out(t, state), **kw)
         if kw:
             rec.h_fin_n = t + 1
-        self._mega_last = True                                     # (the reset obs launch may be skipped: step 0 writes the rows)
-        next_state = self.env._flatten_obs(raw._obs) if hasattr(self.env, '_flatten_obs') else raw._obs
-        if raw.dims.kind == 2:                                     # TJ:244-247
-            info = {'alive_mask': buf['alive'][t], 'is_completed': buf['is_completed'][t]}
-        else:
-            info = {'alive_mask_device': buf['alive'][t]}
-        if args.hard_attn and args.commnet:                        # trainer.py:70-71 (gate for the NEXT step)
-            info['comm_action'] = buf['action'][t][-1] if not args.comm_action_one else self._ones_comm
-        if getattr(self, '_should_display', False):                # trainer.py:101-102
-            self.env.display()
-        self._step_out[t] = (None, action_out, value, None)
-        self._state = next_state
-        self._info = info
-        self._nsteps = t + 1
+        self._after_launch(t, action_out, value)
 
     def _step_body_rnn(self, t, observe):
         """The iteration of _step_body for models.RNN with the tanh recurrence (models.py:68-92, rnn_type 'MLP') through
@@ -646,45 +628,26 @@ class Trainer(object):
         env.step and the dense obs rows of the state acted on are ONE launch.  h_t goes to one of two persistent buffers
         (the one the entering state does not live in: the same sequence of addresses in every episode, so a captured step reads /
         writes the same ones on every replay)."""
-        args, buf, state, info = self.args, self._buf, self._state, self._info
+        args, buf, state = self.args, self._buf, self._state
         raw = self.env.env
-        timer = self._step_timer(raw)
-        if timer is not None:
-            from .envs import DispatchEvent
-            e0, e1 = DispatchEvent(), DispatchEvent()
-            raw.set_step_events(e0, e1)
-            timer.append((e0, e1, t))
+        self._arm_step_timer(raw, t)
         E, N, H = state.shape[0], args.nagents, args.hid_size
         pp = self._static.get('rnn_h')
         if pp is None or tuple(pp.shape) != (2, E, N, H):
             pp = self._static['rnn_h'] = torch.empty((2, E, N, H), dtype=torch.float32, device=state.device)
         h_out = pp[1] if self._prev_hid.data_ptr() == pp[0].data_ptr() else pp[0]
-        action_out, value, h_t = self.policy_net.step_env_rnn(
-            raw, [state, self._prev_hid], info, h_out, action=buf['action'][t], reward=buf['reward'][t], done=buf['done'][t],
+        action_out, value, self._prev_hid = self.policy_net.step_env_rnn(      # (no autograd here: detach_gap is moot)
+            raw, [state, self._prev_hid], self._info, h_out, action=buf['action'][t], reward=buf['reward'][t], done=buf['done'][t],
             alive=buf['alive'][t], is_completed=buf['is_completed'][t], obs=raw._obs if observe else None,
             out=self._static_out(t, state))
-        self._mega_last = True                                     # (the reset obs launch may be skipped: step 0 writes the rows)
-        self._prev_hid = h_t                                       # no autograd here: detach_gap is moot
-        next_state = self.env._flatten_obs(raw._obs) if hasattr(self.env, '_flatten_obs') else raw._obs
-        if raw.dims.kind == 2:                                     # TJ:244-247
-            info = {'alive_mask': buf['alive'][t], 'is_completed': buf['is_completed'][t]}
-        else:
-            info = {'alive_mask_device': buf['alive'][t]}
-        if getattr(self, '_should_display', False):                # trainer.py:101-102
-            self.env.display()
-        self._step_out[t] = (None, action_out, value, None)
-        self._state = next_state
-        self._info = info
-        self._nsteps = t + 1
+        self._after_launch(t, action_out, value)
 
     def _rnn_expected(self, raw):
         """Will step_episode go through ic3_commnet_step with h_in?  (models.RNN, tanh recurrence)"""
         a = self.args
-        if getattr(a, 'rollout_grad', False) or not a.recurrent or a.rnn_type == 'LSTM' or self.clock.env is not raw \
-                or getattr(a, 'store_states', False) or select_action is not _select_action_default:
-            return False
         ok = getattr(self.policy_net, 'rnn_step_supported', None)
-        return bool(ok(raw)) if ok is not None else False
+        return self._launch_path_base(raw, getattr(a, 'rollout_grad', False)) and bool(a.recurrent) and a.rnn_type != 'LSTM' \
+            and ok is not None and bool(ok(raw))
 
     def _mega_now(self):
         """this episode (or, before its first step, the previous one) runs on the one-launch path"""
@@ -713,7 +676,7 @@ class Trainer(object):
         """args.overlap_obs: the dense observation of the new state is assembled on a second stream from a snapshot
         of the integer state (ic3_env_snapshot / ic3_env_observe_at), so this HBM-write-bound launch overlaps the
         MFMA-bound policy kernels of the next step instead of delaying them.  Nothing on the rollout path reads the
-        dense observation (the encoder gathers from the state); consumers join in end_episode()."""
+        dense observation (the encoder gathers from the state); consumers join in _close_window()."""
         main = torch.cuda.current_stream()
         if getattr(self, '_side', None) is None:
             self._side = torch.cuda.Stream(device=main.device)
@@ -732,27 +695,27 @@ class Trainer(object):
             ev.record(self._side)
         self._snap_busy[k] = ev
 
-    def end_episode(self):
-        """Everything get_episode derives per step in the reference (trainer.py:70-105), vectorised over the
-        episode buffers: live / alive / episode masks, per-agent reward and comm-action sums, step counts."""
+    def _close_window(self, copy, finalize, mark_done):
+        """What end_episode and _end_window share — everything get_episode derives per step in the reference
+        (trainer.py:70-105), over the slots just played: joins the side stream, slices the episode buffers (`copy`: clones of
+        what the next episode's replays rewrite), has `finalize(n, done, reward, alive, is_completed, gate, gate_ones)` derive
+        the masks, and hands the native update its record.  Returns (the lazy Transitions, finalize's dict, reward, gate);
+        `mark_done`: misc['done'] = this transition ends its env's episode."""
         args = self.args
         if getattr(self, '_side', None) is not None:
             torch.cuda.current_stream().wait_stream(self._side)    # observations assembled on the side stream
         n, buf = self._nsteps, self._buf
         E, N = buf['reward'].shape[1:]
         has_info = self.env.env.dims.kind == 2                     # TJ reports alive_mask / is_completed in info
-        graph = self._use_graph()
-        # static buffers are rewritten by the next episode's replays: hand out copies (action_out / value of a
-        # Transition stay graph-owned and are valid until the same step of the next episode)
-        reward = buf['reward'][:n].clone() if graph else buf['reward'][:n]
-        action = buf['action'][:n].clone() if graph else buf['action'][:n]
+        reward = buf['reward'][:n].clone() if copy else buf['reward'][:n]
+        action = buf['action'][:n].clone() if copy else buf['action'][:n]
         gated = bool(args.hard_attn and args.commnet)              # trainer.py:73-75
         gate = action[:, -1] if gated and not args.comm_action_one else None
-        m = self._finalize(n, buf['done'][:n], reward, buf['alive'][:n] if has_info else None,
-                           buf['is_completed'][:n] if has_info else None, gate, gated and bool(args.comm_action_one))
+        m = finalize(n, buf['done'][:n], reward, buf['alive'][:n] if has_info else None,
+                     buf['is_completed'][:n] if has_info else None, gate, gated and bool(args.comm_action_one))
         alive_mask, episode_mini_mask, live = m['alive_mask'], m['episode_mini_mask'], m['live']
         episode_mask = m['episode_mask'].unsqueeze(2).expand(n, E, N)                          # trainer.py:92-96
-        done_t = (m['episode_mask'] == 0) if self._auto_reset() else None
+        done_t = (m['episode_mask'] == 0) if mark_done else None
         step_out = self._step_out
 
         def transition(t):
@@ -762,11 +725,37 @@ class Trainer(object):
                 misc['done'] = done_t[t]                           # (E,) this transition ends its env's episode
             return Transition(cur_state, action[t], action_out, value, episode_mask[t], episode_mini_mask[t], next_state,
                               reward[t], misc)
+        self._live = m['live_after']
+        self._episodes_played += 1
+        if self._rec is not None:
+            self._rec.finish(self._prev_hid)
+            self._records.append(self._rec)
+            self._rec = None
         # The n Transition tuples (~10 tensor views each) are built when they are READ: a rollout loop that only wants the
         # statistics (bench.py, soak runs, evaluation) does not pay ~1 ms of host time per episode during which the GPU idles
-        episode = LazyEpisode(n, transition)
+        return LazyEpisode(n, transition), m, reward, gate
+
+    def _agent_stats(self, stat, rsum, csum):
+        """stat['reward'] / ['comm_action'] (+ the enemies' under args.enemy_comm) from the per-agent sums of the live slots
+        (trainer.py:86-88, 73-75); csum: None without the hard-attention gate."""
+        nf, enemy = self.args.nfriendly, bool(getattr(self.args, 'enemy_comm', False))
+        stat['reward'] = rsum[:nf].copy()
+        if enemy:
+            stat['enemy_reward'] = rsum[nf:].copy()
+        if csum is not None:
+            stat['comm_action'] = csum[:nf].copy()
+            if enemy:
+                stat['enemy_comm'] = csum[nf:].copy()
+
+    def end_episode(self):
+        """The episode's Transitions (static graph buffers handed out as copies; action_out / value of a Transition stay
+        graph-owned and are valid until the same step of the next episode) and its statistics: per-agent reward and
+        comm-action sums, step counts, what the env reports."""
+        args = self.args
+        N = self._buf['reward'].shape[2]
+        gated = bool(args.hard_attn and args.commnet)
+        episode, m, _, _ = self._close_window(self._use_graph(), self._finalize, self._auto_reset())
         stat = dict()
-        enemy = bool(getattr(args, 'enemy_comm', False))
         rts = None
         raw = getattr(self.env, 'env', None)
         if hasattr(self.env, 'reward_terminal') and getattr(raw, 'has_terminal_reward', True):
@@ -778,19 +767,7 @@ class Trainer(object):
         num_steps = float(sums[0])
         stat['num_steps'] = num_steps                              # trainer.py:109-110
         stat['steps_taken'] = num_steps
-        rsum = sums[2:2 + N]
-        stat['reward'] = rsum[:args.nfriendly].copy()              # trainer.py:86
-        if enemy:
-            stat['enemy_reward'] = rsum[args.nfriendly:].copy()    # trainer.py:87-88
-        if gated:
-            csum = sums[2 + N:2 + 2 * N]
-            stat['comm_action'] = csum[:args.nfriendly].copy()
-            if enemy:
-                stat['enemy_comm'] = csum[args.nfriendly:].copy()
-        if rts is not None:
-            stat['reward'] = stat['reward'] + rts[:args.nfriendly]
-            if enemy:
-                stat['enemy_reward'] = stat['enemy_reward'] + rts[args.nfriendly:]
+        self._agent_stats(stat, sums[2:2 + N] if rts is None else sums[2:2 + N] + rts, sums[2 + N:2 + 2 * N] if gated else None)
         if env_stat is not None:
             if '_episodes' in env_stat:
                 # auto-reset: an env that restarted on the window's last slot holds a zero-length episode: not counted
@@ -800,12 +777,6 @@ class Trainer(object):
                     env_stat['add_rate'] = env_stat['add_rate'] * (eps - n_zero) / eps
                 env_stat['_episodes'] = eps - n_zero
             merge_stat(env_stat, stat)
-        self._live = m['live_after']
-        self._episodes_played += 1
-        if self._rec is not None:
-            self._rec.finish(self._prev_hid)
-            self._records.append(self._rec)
-            self._rec = None
         return (episode, stat)
 
     def _finalize(self, n, done, reward, alive, is_completed, gate, gate_ones):
@@ -916,16 +887,7 @@ class Trainer(object):
                                   last=(k == len(wins) - 1))
         nsteps = float(complete.sum().item())                     # (synchronises, like the per-episode statistics read)
         st = dict(num_steps=nsteps, steps_taken=nsteps)
-        enemy = bool(getattr(args, 'enemy_comm', False))
-        rs = rsum.cpu().numpy()
-        st['reward'] = rs[:args.nfriendly].copy()
-        if enemy:
-            st['enemy_reward'] = rs[args.nfriendly:].copy()
-        if gated:
-            cs = csum.cpu().numpy()
-            st['comm_action'] = cs[:args.nfriendly].copy()
-            if enemy:
-                st['enemy_comm'] = cs[args.nfriendly:].copy()
+        self._agent_stats(st, rsum.cpu().numpy(), csum.cpu().numpy() if gated else None)
         # env statistics (env_wrappers.get_stat) of the FINISHED episodes only: the device counters of the in-launch restarts
         raw = self.env.env
         ds = raw.device_stats()
@@ -942,34 +904,11 @@ class Trainer(object):
     def _end_window(self):
         """end_episode of a collection window: masks of the max_steps slots just played (no cut at the window's end: the
         streams run on) — statistics and the complete-episode mask are formed over the whole batch by _run_batch_streams."""
-        args = self.args
-        if getattr(self, '_side', None) is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
-        n, buf = self._nsteps, self._buf
-        E, N = buf['reward'].shape[1:]
-        has_info = self.env.env.dims.kind == 2
-        reward, action, done = buf['reward'][:n], buf['action'][:n], buf['done'][:n]
-        gated = bool(args.hard_attn and args.commnet)
-        gate = action[:, -1] if gated and not args.comm_action_one else None
-        m = ops.episode_finalize(done, reward, buf['alive'][:n] if has_info else None,
-                                 buf['is_completed'][:n] if has_info else None, gate, gated and bool(args.comm_action_one),
-                                 True, False, work=self._fin_work)
-        alive_mask, episode_mini_mask, live = m['alive_mask'], m['episode_mini_mask'], m['live']
-        episode_mask = m['episode_mask'].unsqueeze(2).expand(n, E, N)
-        done_t = m['episode_mask'] == 0
-        step_out = self._step_out
-
-        def transition(t):
-            cur_state, action_out, value, next_state = step_out[t]
-            return Transition(cur_state, action[t], action_out, value, episode_mask[t], episode_mini_mask[t], next_state,
-                              reward[t], {'alive_mask': alive_mask[t], 'live': live[t], 'done': done_t[t]})
-        self._live = m['live_after']
-        self._episodes_played += 1
-        if self._rec is not None:
-            self._rec.finish(self._prev_hid)
-            self._records.append(self._rec)
-            self._rec = None
-        return dict(episode=LazyEpisode(n, transition), done=done, reward=reward, gate=gate, live=live, alive_mask=alive_mask)
+        def finalize(n, *slots):                                   # always the launch; auto=True, forced_last=False
+            return ops.episode_finalize(*slots, True, False, work=self._fin_work)
+        episode, m, reward, gate = self._close_window(False, finalize, True)
+        return dict(episode=episode, done=self._buf['done'][:len(episode)], reward=reward, gate=gate, live=m['live'],
+                    alive_mask=m['alive_mask'])
 
     def run_batch(self, epoch):                                    # trainer.py:227-242
         if self._auto_reset():
@@ -1066,8 +1005,7 @@ class Trainer(object):
     def _commnet_expected(self, raw):
         """Will step_episode go through ic3_commnet_step?  (the non-recurrent twin of _mega_expected)"""
         a = self.args
-        if getattr(a, 'rollout_grad', False) or a.recurrent or self.clock.env is not raw or getattr(a, 'store_states', False) \
-                or select_action is not _select_action_default:
+        if not self._launch_path_base(raw, getattr(a, 'rollout_grad', False)) or a.recurrent:
             return False
         net = self.policy_net
         if getattr(net, 'commnet_step_ok', None) is None or not hasattr(raw, '_h'):
