@@ -169,10 +169,22 @@ EXPORTS = {
     "ic3_rnn_weight_grad_scratch_floats": (C.c_size_t, [C.c_longlong, C.c_int]),
     "ic3_rnn_weight_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_void_p]),
+    "ic3_rnn_backward_wide_supported": (C.c_int, [C.c_void_p, C.c_int]),
+    "ic3_rnn_backward_wide_partials": (C.c_int, [C.c_longlong, C.c_int]),
+    "ic3_rnn_tanh_backward_step_wide": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 +
+                                        [C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
+    "ic3_rnn_backward_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ic3_rnn_weight_grad_wide_scratch_floats": (C.c_size_t, [C.c_longlong, C.c_int]),
+    "ic3_rnn_weight_grad_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p]),
     "ic3_mlp_backward_supported": (C.c_int, [C.c_void_p, C.c_int]),
     "ic3_mlp_backward_partials": (C.c_int, [C.c_longlong, C.c_int]),
     "ic3_mlp_backward_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
     "ic3_mlp_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ic3_mlp_backward_wide_supported": (C.c_int, [C.c_void_p, C.c_int]),
+    "ic3_mlp_backward_wide_partials": (C.c_int, [C.c_longlong, C.c_int]),
+    "ic3_mlp_backward_step_wide": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
+    "ic3_mlp_backward_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ic3_env_set_record_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ic3_lstm_gates_backward_dx": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ic3_commnet_forward_supported": (C.c_int, [C.c_int, C.c_int]),

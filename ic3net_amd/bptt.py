@@ -889,11 +889,11 @@ def fold_standin(acc):
     acc['b_heads'].add_(acc2['b_heads'])
 
 
-RNN_WINDOW_SIZES = (64, 128)     # ic3_rnn_backward
+RNN_WINDOW_SIZES = (64, 128, 256)     # ic3_rnn_backward_wide
 
 
 def _rnn_window_ok(args, net, raw, rec, d_out):
-    """models.RNN with the tanh recurrence on a record at its own hid_size (64 / 128), at most 16 output columns, the native loop
+    """models.RNN with the tanh recurrence on a record at its own hid_size (64 / 128 / 256), at most 16 output columns, the native loop
     on (args.bptt_native_loop), the library's answer and the room for the T x R x H ring of dz: _backward_window_rnn."""
     H = args.hid_size
     if not rec.recurrent or getattr(args, 'rnn_type', 'MLP') != 'MLP' or not hasattr(net, 'affine2') or H not in RNN_WINDOW_SIZES:
@@ -906,7 +906,7 @@ def _rnn_window_ok(args, net, raw, rec, d_out):
 
 
 def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
-    """_backward_episode_baseline's tanh branch for a whole window through ic3_rnn_backward (csrc/bptt_kernels.hip).  Per step, last
+    """_backward_episode_baseline's tanh branch for a whole window through ic3_rnn_backward_wide (csrc/bptt_kernels.hip; hid 64 / 128 / 256).  Per step, last
     to first, ONE launch: dh_t = dh + d_t . W_heads, dz_t = dh_t (1 - h_t^2) into a ring of T slots, dh <- (dz_t . A2) * keep_{t-1},
     the column sums of dz_t as per-workgroup partials; then the sparse encoder's first stage over the ring, and affine2's weight
     gradient sum_t dz_t^T (live_t h_{t-1}) over all T x R rows in one launch.  Behind it: the encoder's expansion (affine1.weight),
@@ -937,12 +937,12 @@ def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
     return (dh, dh)
 
 
-MLP_WINDOW_SIZES = (64, 128)     # ic3_mlp_backward
+MLP_WINDOW_SIZES = (64, 128, 256)     # ic3_mlp_backward_wide
 
 
 def mlp_window_wanted(args, net, raw):
     """What a rollout must hold for _backward_window_mlp before it records h_fin: the IC baseline itself (models.MLP, not its
-    recurrent subclass) at hid 64 / 128 — no zero-padded twin —, the native loop on, and the library's answer for this env."""
+    recurrent subclass) at hid 64 / 128 / 256 — no zero-padded twin —, the native loop on, and the library's answer for this env."""
     from . import models
     H = args.hid_size
     if type(net) is not models.MLP or getattr(args, 'recurrent', False) or H not in MLP_WINDOW_SIZES:
@@ -953,7 +953,7 @@ def mlp_window_wanted(args, net, raw):
 
 
 def _mlp_window_ok(args, net, raw, rec, d_out):
-    """models.MLP on a record whose step launches stored h of every step (h_fin), hid_size 64 / 128, at most 16 output columns, the
+    """models.MLP on a record whose step launches stored h of every step (h_fin), hid_size 64 / 128 / 256, at most 16 output columns, the
     native loop on (args.bptt_native_loop), the library's answer and the room for the three T x R x H rings (x1, dz, de):
     _backward_window_mlp."""
     if rec.recurrent or not mlp_window_wanted(args, net, raw):
@@ -968,7 +968,7 @@ def _mlp_window_ok(args, net, raw, rec, d_out):
 
 
 def _backward_window_mlp(args, net, raw, rec, d_out, acc):
-    """_backward_episode_baseline's non-recurrent branch for a whole window through ic3_mlp_backward (csrc/bptt_kernels.hip).  No
+    """_backward_episode_baseline's non-recurrent branch for a whole window through ic3_mlp_backward_wide (csrc/bptt_kernels.hip; hid 64 / 128 / 256).  No
     state crosses a step, so the window is T x R independent rows: e of every snapshot into a ring (T encoder launches), then ONE
     launch — x1 = tanh(e) over e, dz = (d . W_heads)(1 - h^2) with the h the step launches recorded (rec.h_fin), de = (dz . A2 +
     dz)(1 - x1^2), the column sums of dz as per-workgroup partials —, the sparse encoder's first stage over the de ring and affine2's

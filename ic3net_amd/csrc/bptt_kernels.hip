@@ -20,9 +20,11 @@
 //   ic3_rnn_weight_grad   ONE launch per window: dA2 += dz^T . (row_live h_prev) over all T x R rows (rnn_wgrad_kernel).
 //   ic3_mlp_backward_step / ic3_mlp_backward   the IC baseline (models.MLP): a window is T x R independent rows, ONE launch over
 //                         all of them (mlp_bwd_kernel), and the window as one host call.
+//                         The rnn / mlp entries: hid 64 / 128; their _wide twins (ic3_rnn_backward_wide, ...): the same bodies for
+//                         64 / 128 / 256 (what ic3net_amd calls).
 // and what sizes their buffers / says whether they run: ic3_comm_backward_partials, ic3_lstm_weight_grad[_wide]_scratch_floats,
 // ic3_bptt_backward_supported, ic3_bptt_first_chain_envs, ic3_rnn_ / ic3_mlp_backward_partials and _supported,
-// ic3_rnn_weight_grad_scratch_floats.
+// ic3_rnn_weight_grad_scratch_floats, and the _wide twins of the rnn / mlp ones.
 // What these share exists once.  Device: bp_load1 / bp_load4 / bp_store4 (buffer access, the wave-uniform part in `soff`), bp_zero,
 // bp_kslice (a weight-gradient workgroup's K slice), TanhTile<H> (the tile machine of the two tanh kernels).  Host: launch_kernel
 // (ic3_common.hpp), tanh_partials / tanh_supported, wgrad_plan / wgrad_reduce (the K slices and their fixed-order sum), window_open
@@ -617,13 +619,13 @@ static int wgrad_reduce(const float* scratch, int ks, int n, float* dW, int accu
     return rc < 0 ? rc : ks;
 }
 
-// The plan at hid 256 (16 workgroups per slice): config 5's window is 80 x 262 144 rows of 4 KB, and a one-round slice of it lies
+// The plans at hid 256 (`ny` workgroups per slice — the LSTM's: 16): config 5's window is 80 x 262 144 rows of 4 KB, and a one-round slice of it lies
 // past the kernels' 32-bit buffer offsets.  ks grows in whole multiples of the one-round count until a slice fits; the slices
 // beyond the workgroup slots run as further rounds (the kernels know nothing of rounds).  64 / 128: wgrad_plan as it is.
-static WGradPlan lstm_wgrad_plan(long long Q, int H, long long row_floats)
+// (Rounds of at least 8 slices: with fewer than 8 / ny CUs' worth of workgroup slots the plan is wgrad_plan's.)
+static WGradPlan wgrad_plan_rounds(long long Q, int ny, long long row_floats)
 {
-    WGradPlan pl = wgrad_plan(Q, H == 256 ? 16 : 4 * H / 128, row_floats);
-    if (H != 256) return pl;
+    WGradPlan pl = wgrad_plan(Q, ny, row_floats);
     const long long most = (Q + 15) / 16;
     const int round = pl.ks;
     for (long long m = 2; !pl.fits && round * m <= most; ++m) {
@@ -632,6 +634,15 @@ static WGradPlan lstm_wgrad_plan(long long Q, int H, long long row_floats)
         pl.fits = pl.per * row_floats * 4 < (1ll << 31);
     }
     return pl;
+}
+static WGradPlan lstm_wgrad_plan(long long Q, int H, long long row_floats)
+{
+    return H == 256 ? wgrad_plan_rounds(Q, 16, row_floats) : wgrad_plan(Q, 4 * H / 128, row_floats);
+}
+// ic3_rnn_weight_grad: one workgroup per slice at 64 / 128; at 256 the four output quadrants of a slice, and further rounds as above
+static WGradPlan rnn_wgrad_plan(long long Q, int H, long long row_floats)
+{
+    return H == 256 ? wgrad_plan_rounds(Q, 4, row_floats) : wgrad_plan(Q, 1, row_floats);
 }
 
 // ic3_lstm_weight_grad (hid 64 / 128) and ic3_lstm_weight_grad_wide (64 / 128 / 256) behind their hid_size checks
@@ -878,6 +889,18 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
 // of its tile's dh_in rows before the barrier in front of the product, and no other workgroup touches those rows.
 // LDS: H^2 + 64 (H + 4) + 16 H + 1024 floats (110 KB at H = 128: one workgroup of 8 waves per CU; 41 KB at 64: two of 4).
 // HBM per row: dh_in, h_t in, dz, dh_out out (4 H floats) + OT; MFMA 2 H^2 flop per row on the fp32 instruction.
+//
+// H = 256 — the plan: A2 STREAMED FROM L2, rows owned by one workgroup.  A2 is 256 KB, more than a CU's 160 KB of LDS, so
+// rnn_tanh_bwd_kernel<256> / mlp_bwd_kernel<256> keep the same tile machine (1024 threads = 16 waves, a 64-row tile, wave (rb, cb) =
+// 32 rows x 32 of the 256 columns, phase 0 / product / epilogue unchanged) and only TanhTile<256>::product differs: a lane's B values
+// A2[k][col] come from global memory through a buffer descriptor, 8 loads (16 k rows) per stage, the next stage requested in front
+// of this stage's 8 MFMAs.  All workgroups read the same 256 KB, which stays in every XCD's L2.  Staging 64-column chunks of A2
+// through LDS per tile moves the same 256 KB per tile from L2 and adds an LDS round trip and four barriers per tile, so it was not
+// taken.  A workgroup owns ALL 256 columns of its tile's rows (phase 0 reads every dh_in row of the tile in front of the barrier
+// before the product): dh_out == dh_in stays legal.  No atomics; the column sums are the row groups' sums in group order, as at
+// 64 / 128.
+// LDS: 64 (H + 4) + 16 H + 1024 floats = 87 040 bytes: one workgroup of 16 waves per CU (4 per SIMD, <= 128 registers each).
+// Per row: HBM dh_in, h_t in, dz, dh_out out = 4 KB (+ OT floats; mlp: 5 KB); L2 16 waves x 32 KB of A2 per 64-row tile = 8 KB.
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace ic3 {
 
@@ -888,8 +911,10 @@ template <int H>
 struct TanhTile {
     static constexpr int NT = 4 * H, H4 = H / 4, LDA = H + 4, LDA4 = LDA / 4, CB = H / 32, RPP = NT / H4, PER = 64 / RPP;
     static_assert(RPP * PER == 64 && NT / 64 == 2 * CB, "tile split");
-    // LDS in floats: A2 in fragment order | the tile's dz | W_heads | the tile's d rows
-    static constexpr int DZ_AT = H * H, WH_AT = DZ_AT + 64 * LDA, SD_AT = WH_AT + 16 * H;
+    // A2 in LDS for the workgroup's life (64 / 128), or — 256 KB at H = 256, more than a CU's LDS — its B fragments streamed from L2
+    static constexpr bool RESIDENT = H <= 128;
+    // LDS in floats: A2 in fragment order (RESIDENT) | the tile's dz | W_heads | the tile's d rows
+    static constexpr int DZ_AT = RESIDENT ? H * H : 0, WH_AT = DZ_AT + 64 * LDA, SD_AT = WH_AT + 16 * H;
     static constexpr size_t LDS_BYTES = (size_t)(SD_AT + 64 * 16) * sizeof(float);
     float* const smem;
     const bp_f32x4* const Bf4;   // [H / 8][2][H] float4
@@ -907,12 +932,14 @@ struct TanhTile {
           cb((threadIdx.x >> 6) % CB), rb((threadIdx.x >> 6) / CB), c4(threadIdx.x % H4), rg(threadIdx.x / H4)
     {
     }
-    // A2 -> fragment order, W_heads as it is (the caller's barrier behind it)
+    // A2 -> fragment order (RESIDENT), W_heads as it is (the caller's barrier behind it)
     __device__ __forceinline__ void stage_weights(const float* a2, const float* w_heads, int OT) const
     {
-        for (int i = tid; i < H * H; i += NT) {
-            const int k = i / H, col = i - k * H;
-            smem[(((k >> 3) * 2 + ((k >> 2) & 1)) * H + col) * 4 + (k & 3)] = a2[i];
+        if constexpr (RESIDENT) {
+            for (int i = tid; i < H * H; i += NT) {
+                const int k = i / H, col = i - k * H;
+                smem[(((k >> 3) * 2 + ((k >> 2) & 1)) * H + col) * 4 + (k & 3)] = a2[i];
+            }
         }
         for (int i = tid; i < OT * H; i += NT) Wh[i] = w_heads[i];
     }
@@ -924,16 +951,39 @@ struct TanhTile {
         return v;
     }
     // the wave's 32 x 32 block of dz . A2 on the fp32 matrix instruction (k = 8 kb + 4 lh + j: A fragment and B slot agree)
-    __device__ __forceinline__ bp_f32x16 product() const
+    // Streamed (H = 256): the lane's B values A2[8 kb + 4 lh + j][32 cb + li] come from global memory (L2: all workgroups read the
+    // same 256 KB), 16 k rows = 8 loads per stage, the next stage requested in front of this one's 8 MFMAs (past A2's end: 0).
+    __device__ __forceinline__ bp_f32x16 product(const float* a2) const
     {
         bp_f32x16 acc;
         bp_zero<1>(&acc);
+        if constexpr (RESIDENT) {
 #pragma unroll 4
-        for (int kb = 0; kb < H / 8; ++kb) {
-            const bp_f32x4 a4 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
-            const bp_f32x4 b4 = Bf4[(2 * kb + lh) * H + 32 * cb + li];
+            for (int kb = 0; kb < H / 8; ++kb) {
+                const bp_f32x4 a4 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
+                const bp_f32x4 b4 = Bf4[(2 * kb + lh) * H + 32 * cb + li];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bp_mfma(acc, a4[j], b4[j]);
+                for (int j = 0; j < 4; ++j) bp_mfma(acc, a4[j], b4[j]);
+            }
+        } else {
+            const __amdgpu_buffer_rsrc_t ra = bp_rsrc(a2, (long long)H * H * 4);
+            const int voff = (4 * lh * H + 32 * cb + li) * 4;
+            float bv[8], bn[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) bv[j] = bp_load1(ra, voff, (8 * (j >> 2) + (j & 3)) * H * 4);
+#pragma unroll 2
+            for (int kb = 0; kb < H / 8; kb += 2) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) bn[j] = bp_load1(ra, voff, (8 * (kb + 2 + (j >> 2)) + (j & 3)) * H * 4);
+                const bp_f32x4 a0 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + lh];
+                const bp_f32x4 a1 = Dz4[(32 * rb + li) * LDA4 + 2 * kb + 2 + lh];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bp_mfma(acc, a0[j], bv[j]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bp_mfma(acc, a1[j], bv[4 + j]);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) bv[j] = bn[j];
+            }
         }
         return acc;
     }
@@ -1004,7 +1054,7 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void rnn_tanh_bwd_kernel(
         }
         __syncthreads();
         // ---- phase 1: dh_out = (dz . A2) * out_scale, stored from the accumulator layout
-        const bp_f32x16 acc = t.product();
+        const bp_f32x16 acc = t.product(a.a2);
         const __amdgpu_buffer_rsrc_t rout = bp_rsrc(a.dh_out + r0 * H, (long long)rows * H * 4);
         const __amdgpu_buffer_rsrc_t rsc = bp_rsrc(a.out_scale ? a.out_scale + r0 : a.dh_out, a.out_scale ? (long long)rows * 4 : 0);
 #pragma unroll
@@ -1025,6 +1075,10 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void rnn_tanh_bwd_kernel(
 // Both operands row-major with q outermost — the K-major pair v_mfma_f32_32x32x2_f32 wants: lane (i, kk) supplies dz[q0 + kk][m(i)]
 // and h[q0 + kk][n(i)].  Staging: KT = 16 rows of each per stage, global -> registers -> LDS, double-buffered, one barrier per
 // stage (the shape of lstm_wgrad_kernel).  Bound: HBM (2 H floats per row) against MFMA (2 H^2 flop per row) — about even at 128.
+// Hid 256: all H x H outputs in one workgroup would be 256 accumulator registers per wave, so <256> IS the tile of 128 (HT) on the
+// four output quadrants — grid (ks, 2, 2), blockIdx.y picks the 128 dz columns (output rows), blockIdx.z the 128 h columns, both
+// staged with the row stride of 256; row_live scales the h rows on the way in, as at 128.  The partials are [ks][256][256]; the K
+// slices grow by whole rounds of workgroups until one stays below 2 GB (rnn_wgrad_plan).  WIDE / HT fold away at 64 / 128.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct RnnWGradArgs {
     const float* dz;         // [Q][H]
@@ -1038,18 +1092,22 @@ struct RnnWGradArgs {
 template <int H>
 __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
 {
-    constexpr int KT = 16, NT = 256, H4 = H / 4, MB = H / 64, HH = H / 2;
-    constexpr int RPS = NT / H4, PT = KT / RPS;                  // rows staged per pass, passes per stage (2 at H = 128, 1 at 64)
-    constexpr int SW = 2 * KT * H;                               // stage b: dz rows at smem + b * SW, h rows behind them
+    constexpr bool WIDE = H == 256;
+    constexpr int HT = WIDE ? 128 : H;                           // the tile: HT dz columns x HT h columns of a row
+    constexpr int KT = 16, NT = 256, H4 = HT / 4, MB = HT / 64, HH = HT / 2;
+    constexpr int RPS = NT / H4, PT = KT / RPS;                  // rows staged per pass, passes per stage (2 at HT = 128, 1 at 64)
+    constexpr int SW = 2 * KT * HT;                              // stage b: dz rows at smem + b * SW, h rows behind them
     static_assert(PT >= 1 && RPS * PT == KT, "staging split");
     IC3_DYNAMIC_LDS(float, smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int wm = w & 1, wn = w >> 1;
+    const int zc = WIDE ? HT * (int)blockIdx.y : 0, hc = WIDE ? HT * (int)blockIdx.z : 0;   // the quadrant's first dz / h column
     const KSlice sl = bp_kslice(a.Q, a.rows_per_wg, KT);
     const long long q0 = sl.q0, nq = sl.nq;
     const int nstages = sl.nstages;
-    const __amdgpu_buffer_rsrc_t rz = bp_rsrc(nq > 0 ? a.dz + q0 * H : a.dz, nq * H * 4);
-    const __amdgpu_buffer_rsrc_t rh = bp_rsrc(nq > 0 ? a.h + q0 * H : a.h, nq * H * 4);
+    // (WIDE: HT columns of rows H floats apart — the range ends behind the last row's HT columns, so rows past the slice read 0)
+    const __amdgpu_buffer_rsrc_t rz = bp_rsrc(nq > 0 ? a.dz + q0 * H + zc : a.dz, WIDE ? ((nq - 1) * H + HT) * 4 : nq * H * 4);
+    const __amdgpu_buffer_rsrc_t rh = bp_rsrc(nq > 0 ? a.h + q0 * H + hc : a.h, WIDE ? ((nq - 1) * H + HT) * 4 : nq * H * 4);
     const __amdgpu_buffer_rsrc_t rl = bp_rsrc(a.row_live && nq > 0 ? a.row_live + q0 : a.h, a.row_live ? nq * 4 : 0);
     const int srow = tid / H4, sc4 = tid - srow * H4;            // a thread stages rows srow + RPS i, column chunk sc4
     bp_f32x4 zr[PT], hr[PT];
@@ -1083,15 +1141,15 @@ __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
         const bool more = s + 1 < nstages;
         if (more) fetch(s + 1);
         const float* Zs = smem + (s & 1) * SW;
-        const float* Ps = Zs + KT * H;
+        const float* Ps = Zs + KT * HT;
 #pragma unroll
         for (int ks = 0; ks < KT / 2; ++ks) {
             const int kr = 2 * ks + lh;
             float av[MB], bv[MB];
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
-                av[mb] = Zs[kr * H + wm * HH + 32 * mb + li];
-                bv[mb] = Ps[kr * H + wn * HH + 32 * mb + li];
+                av[mb] = Zs[kr * HT + wm * HH + 32 * mb + li];
+                bv[mb] = Ps[kr * HT + wn * HH + 32 * mb + li];
             }
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb)
@@ -1101,8 +1159,8 @@ __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
         if (more) stash((s + 1) & 1);
         __syncthreads();
     }
-    // block (mb, nb), register reg, lane (li, lh): m = wm H / 2 + 32 mb + (reg & 3) + 8 (reg >> 2) + 4 lh, n = wn H / 2 + 32 nb + li
-    float* dst = a.part + (size_t)blockIdx.x * H * H;
+    // block (mb, nb), register reg, lane (li, lh): m = wm HT / 2 + 32 mb + (reg & 3) + 8 (reg >> 2) + 4 lh, n = wn HT / 2 + 32 nb + li
+    float* dst = a.part + (size_t)blockIdx.x * H * H + (size_t)zc * H + hc;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -1121,81 +1179,131 @@ __global__ __launch_bounds__(256, 2) void rnn_wgrad_kernel(const RnnWGradArgs a)
 // 128, two at 64), and every workgroup the same number of tiles — the launch lasts as long as the workgroup with the most tiles
 // either way, and every workgroup fewer is one partial less to sum (PP-hard, E = 8192: 1280 tiles on 256 CUs = 256 workgroups x
 // 5, no thin last round).
-static int tanh_partials(long long rows, int H)
+static int tanh_partials(long long rows, int H, bool wide)
 {
-    if (rows <= 0 || (H != 64 && H != 128)) return 0;
+    if (rows <= 0 || (H != 64 && H != 128 && !(wide && H == 256))) return 0;
     const long long tiles = (rows + 63) / 64;
     const long long cap = (long long)ic3::bp_cus() * (H == 64 ? 2 : 1);
     const long long rounds = (tiles + cap - 1) / cap;
     return (int)((tiles + rounds - 1) / rounds);
 }
 
-// both baselines' windows: the tanh kernels' sizes, and the sparse encoder's backward in its partial-sums form
+// both baselines' windows: the tanh kernels' sizes (64 / 128; the _wide entries: 256 too), and the sparse encoder's backward in
+// its partial-sums form
 static int tanh_supported(const ic3_env* env, int H)
 {
     if (!env || (H != 64 && H != 128)) return 0;
     return ic3_bptt_backward_supported(env, H);
 }
+static int tanh_supported_wide(const ic3_env* env, int H)
+{
+    if (!env || (H != 64 && H != 128 && H != 256)) return 0;
+    return ic3_bptt_backward_supported(env, H);
+}
+static const char* const TANH_SIZES[2] = { "hid_size 64 / 128", "hid_size 64 / 128 / 256" };
+static bool tanh_size_ok(int H, bool wide) { return H == 64 || H == 128 || (wide && H == 256); }
 
-extern "C" int ic3_rnn_backward_partials(long long R, int H) { return tanh_partials(R, H); }
+extern "C" int ic3_rnn_backward_partials(long long R, int H) { return tanh_partials(R, H, false); }
+extern "C" int ic3_rnn_backward_wide_partials(long long R, int H) { return tanh_partials(R, H, true); }
 
 extern "C" int ic3_rnn_backward_supported(const ic3_env* env, int H) { return tanh_supported(env, H); }
+extern "C" int ic3_rnn_backward_wide_supported(const ic3_env* env, int H) { return tanh_supported_wide(env, H); }
 
 extern "C" size_t ic3_rnn_weight_grad_scratch_floats(long long Q, int H)
 {
     if (Q <= 0 || (H != 64 && H != 128)) return 0;
     return (size_t)wgrad_plan(Q, 1, 0).ks * H * H;
 }
+extern "C" size_t ic3_rnn_weight_grad_wide_scratch_floats(long long Q, int H)
+{
+    if (Q <= 0 || !tanh_size_ok(H, true)) return 0;
+    return (size_t)rnn_wgrad_plan(Q, H, H).ks * H * H;
+}
+
+// ic3_rnn_weight_grad (hid 64 / 128) and ic3_rnn_weight_grad_wide (64 / 128 / 256) behind their hid_size checks
+static int rnn_weight_grad(const float* dz, const float* h_prev, const float* row_live, long long Q, int H, float* dA2, int accumulate,
+                           float* scratch, ic3_stream stream, bool wide)
+{
+    using namespace ic3;
+    const char* const fn = wide ? "ic3_rnn_weight_grad_wide: " : "ic3_rnn_weight_grad: ";   // (a std::string only on the way out)
+    if (!dz || !h_prev || !dA2 || !scratch || Q <= 0) return fail(-22, std::string(fn) + "null argument");
+    if (!tanh_size_ok(H, wide)) return fail(-38, std::string(fn) + TANH_SIZES[wide]);
+    const WGradPlan pl = rnn_wgrad_plan(Q, H, H);
+    if (!pl.fits) return fail(-22, std::string(fn) + "a K slice must stay below 2 GB (32-bit buffer offsets)");
+    const RnnWGradArgs a{ dz, h_prev, row_live, scratch, Q, (int)pl.per };
+    hipStream_t s = (hipStream_t)stream;
+    // hid 256: the tile of 128 on the four output quadrants (grid y: the dz columns = output rows, z: the h columns)
+    const int HT = H == 256 ? 128 : H;
+    const size_t lds = (size_t)2 * 2 * 16 * HT * sizeof(float);
+    const auto kernel = H == 256 ? rnn_wgrad_kernel<256> : H == 128 ? rnn_wgrad_kernel<128> : rnn_wgrad_kernel<64>;
+    const dim3 grid = H == 256 ? dim3(pl.ks, 2, 2) : dim3(pl.ks);
+    if (const int rc = launch_kernel(kernel, grid, dim3(256), lds, s, a); rc < 0) return rc;
+    return wgrad_reduce(scratch, pl.ks, H * H, dA2, accumulate, s);
+}
 
 extern "C" int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const float* row_live, long long Q, int H, float* dA2,
                                    int accumulate, float* scratch, ic3_stream stream)
 {
-    using namespace ic3;
-    if (!dz || !h_prev || !dA2 || !scratch || Q <= 0) return fail(-22, "ic3_rnn_weight_grad: null argument");
-    if (H != 64 && H != 128) return fail(-38, "ic3_rnn_weight_grad: hid_size 64 / 128");
-    const WGradPlan pl = wgrad_plan(Q, 1, H);
-    if (!pl.fits) return fail(-22, "ic3_rnn_weight_grad: a K slice must stay below 2 GB (32-bit buffer offsets)");
-    const RnnWGradArgs a{ dz, h_prev, row_live, scratch, Q, (int)pl.per };
-    hipStream_t s = (hipStream_t)stream;
-    const size_t lds = (size_t)2 * 2 * 16 * H * sizeof(float);
-    if (const int rc = launch_kernel(H == 128 ? rnn_wgrad_kernel<128> : rnn_wgrad_kernel<64>, dim3(pl.ks), dim3(256), lds, s, a); rc < 0)
-        return rc;
-    return wgrad_reduce(scratch, pl.ks, H * H, dA2, accumulate, s);
+    return rnn_weight_grad(dz, h_prev, row_live, Q, H, dA2, accumulate, scratch, stream, false);
+}
+extern "C" int ic3_rnn_weight_grad_wide(const float* dz, const float* h_prev, const float* row_live, long long Q, int H, float* dA2,
+                                        int accumulate, float* scratch, ic3_stream stream)
+{
+    return rnn_weight_grad(dz, h_prev, row_live, Q, H, dA2, accumulate, scratch, stream, true);
 }
 
 // one step of the chain (also the unit the tests drive): returns the number of partials written / added to
+static int rnn_tanh_backward_step(const float* dh_in, const float* h_t, const float* dhead, const float* w_heads, int OT, const float* a2,
+                                  const float* out_scale, float* dz, float* dh_out, float* dbias_partials, int accumulate, long long R,
+                                  int H, ic3_stream stream, bool wide)
+{
+    using namespace ic3;
+    const char* const fn = wide ? "ic3_rnn_tanh_backward_step_wide: " : "ic3_rnn_tanh_backward_step: ";   // (a std::string only on the way out)
+    if (!h_t || !dhead || !w_heads || !a2 || !dz || !dh_out || !dbias_partials || R <= 0) return fail(-22, std::string(fn) + "null argument");
+    if (!tanh_size_ok(H, wide)) return fail(-38, std::string(fn) + TANH_SIZES[wide]);
+    if (OT < 1 || OT > 16) return fail(-22, std::string(fn) + "1 <= OT <= 16");
+    if (R >= (1ll << 31)) return fail(-22, std::string(fn) + "R < 2^31");
+    const int grid = tanh_partials(R, H, wide);
+    const RnnBwdArgs a{ dh_in, h_t, dhead, w_heads, a2, out_scale, dz, dh_out, dbias_partials, (int)R, OT, (int)((R + 63) / 64),
+                        accumulate };
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = H == 256   ? launch_kernel(rnn_tanh_bwd_kernel<256>, dim3(grid), dim3(1024), TanhTile<256>::LDS_BYTES, s, a)
+                   : H == 128 ? launch_kernel(rnn_tanh_bwd_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES, s, a)
+                              : launch_kernel(rnn_tanh_bwd_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES, s, a);
+    return rc < 0 ? rc : grid;
+}
+
 extern "C" int ic3_rnn_tanh_backward_step(const float* dh_in, const float* h_t, const float* dhead, const float* w_heads, int OT,
                                           const float* a2, const float* out_scale, float* dz, float* dh_out, float* dbias_partials,
                                           int accumulate, long long R, int H, ic3_stream stream)
 {
-    using namespace ic3;
-    if (!h_t || !dhead || !w_heads || !a2 || !dz || !dh_out || !dbias_partials || R <= 0)
-        return fail(-22, "ic3_rnn_tanh_backward_step: null argument");
-    if (H != 64 && H != 128) return fail(-38, "ic3_rnn_tanh_backward_step: hid_size 64 / 128");
-    if (OT < 1 || OT > 16) return fail(-22, "ic3_rnn_tanh_backward_step: 1 <= OT <= 16");
-    if (R >= (1ll << 31)) return fail(-22, "ic3_rnn_tanh_backward_step: R < 2^31");
-    const int grid = tanh_partials(R, H);
-    const RnnBwdArgs a{ dh_in, h_t, dhead, w_heads, a2, out_scale, dz, dh_out, dbias_partials, (int)R, OT, (int)((R + 63) / 64),
-                        accumulate };
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = H == 128 ? launch_kernel(rnn_tanh_bwd_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES, s, a)
-                            : launch_kernel(rnn_tanh_bwd_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES, s, a);
-    return rc < 0 ? rc : grid;
+    return rnn_tanh_backward_step(dh_in, h_t, dhead, w_heads, OT, a2, out_scale, dz, dh_out, dbias_partials, accumulate, R, H, stream,
+                                  false);
+}
+extern "C" int ic3_rnn_tanh_backward_step_wide(const float* dh_in, const float* h_t, const float* dhead, const float* w_heads, int OT,
+                                               const float* a2, const float* out_scale, float* dz, float* dh_out,
+                                               float* dbias_partials, int accumulate, long long R, int H, ic3_stream stream)
+{
+    return rnn_tanh_backward_step(dh_in, h_t, dhead, w_heads, OT, a2, out_scale, dz, dh_out, dbias_partials, accumulate, R, H, stream,
+                                  true);
 }
 
-extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream)
+static int rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream, bool wide)
 {
     using namespace ic3;
-    if (const int rc = window_open("ic3_rnn_backward", "ic3_rnn_bptt", env, b, tanh_supported,
-                                   "hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form", false);
+    const char* const fn = wide ? "ic3_rnn_backward_wide" : "ic3_rnn_backward";
+    const std::string f = std::string(fn) + ": ";
+    if (const int rc = window_open(fn, "ic3_rnn_bptt", env, b, wide ? tanh_supported_wide : tanh_supported,
+                                   (std::string(TANH_SIZES[wide]) + ", a grid whose encoder backward runs in its partial-sums form").c_str(),
+                                   false);
         rc < 0)
         return rc;
     const int T = b->T, E = b->E, N = b->N, H = b->H;
     if (!b->hs || !b->dhead || !b->snaps || !b->a2 || !b->w_heads || !b->dh || !b->dz || !b->dbias_partials || !b->enc_work)
-        return fail(-22, "ic3_rnn_backward: null argument");
-    if (b->a2_grad && !b->wgrad_scratch) return fail(-22, "ic3_rnn_backward: a2_grad needs wgrad_scratch");
+        return fail(-22, f + "null argument");
+    if (b->a2_grad && !b->wgrad_scratch) return fail(-22, f + "a2_grad needs wgrad_scratch");
     if (b->enc_window && ic3_env_encode_backward_window_work(env, H) <= 0)
-        return fail(-22, "ic3_rnn_backward: enc_window on a configuration without ic3_env_encode_backward_window");
+        return fail(-22, f + "enc_window on a configuration without ic3_env_encode_backward_window");
     const long long R = (long long)E * N;
     int enc_first = b->enc_first;
     for (int t = T - 1; t >= 0; --t) {
@@ -1203,9 +1311,9 @@ extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream 
         const bool detached = b->detach_gap > 0 && (t + 1) % b->detach_gap == 0;
         const float* h_t = (t + 1 < T || !b->h_last) ? b->hs + (size_t)(t + 1) * R * H : b->h_last;
         float* dz = b->dz + (size_t)t * R * H;
-        int rc = ic3_rnn_tanh_backward_step(detached ? nullptr : b->dh, h_t, b->dhead + (size_t)t * R * b->OT, b->w_heads, b->OT, b->a2,
-                                            (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R : nullptr, dz, b->dh,
-                                            b->dbias_partials, 1, R, H, stream);
+        int rc = rnn_tanh_backward_step(detached ? nullptr : b->dh, h_t, b->dhead + (size_t)t * R * b->OT, b->w_heads, b->OT, b->a2,
+                                        (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R : nullptr, dz, b->dh,
+                                        b->dbias_partials, 1, R, H, stream, wide);
         if (rc < 0) return rc;
         if (b->enc_window) continue;                             // (the encoder's first stage: once, behind the loop)
         rc = ic3_env_encode_backward_accumulate(env, b->snaps + (size_t)t * b->snap_words, dz, H, H, b->enc_work, enc_first, stream);
@@ -1217,11 +1325,14 @@ extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream 
         if (rc < 0) return rc;
     }
     if (b->a2_grad) {
-        const int rc = ic3_rnn_weight_grad(b->dz, b->hs, b->row_live, (long long)T * R, H, b->a2_grad, 1, b->wgrad_scratch, stream);
+        const int rc = rnn_weight_grad(b->dz, b->hs, b->row_live, (long long)T * R, H, b->a2_grad, 1, b->wgrad_scratch, stream, wide);
         if (rc < 0) return rc;
     }
     return 0;
 }
+
+extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream) { return rnn_backward(env, b, stream, false); }
+extern "C" int ic3_rnn_backward_wide(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream) { return rnn_backward(env, b, stream, true); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // ic3_mlp_backward: the IC baseline (models.py:23-34, models.MLP), every step on its own:
@@ -1241,7 +1352,8 @@ extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream 
 // and thread (row group, chunk) combines them with the dz / x1 it still holds and stores de 16 bytes per lane (4-byte stores from
 // the accumulator layout cost 1.3 x the write traffic in lstm_gates_bwd_kernel).  The next tile's rows are requested before the
 // product, so the matrix phase of a tile covers the loads of the next.  Row offsets in 64 bits (TJ-hard: 13.1 M rows x 512 B).
-// LDS as rnn_tanh_bwd_kernel (110 KB at H = 128: one workgroup of 8 waves per CU; 41 KB at 64: two of 4).
+// LDS as rnn_tanh_bwd_kernel (110 KB at H = 128: one workgroup of 8 waves per CU; 41 KB at 64: two of 4; 85 KB at 256, where A2's
+// fragments are streamed from L2: the plan in the block above rnn_tanh_bwd_kernel).
 // HBM per row: e, h in, x1, dz, de out (5 H floats) + OT; MFMA 2 H^2 flop per row on the fp32 instruction.
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace ic3 {
@@ -1320,7 +1432,7 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void mlp_bwd_kernel(const
         if (tile + (int)gridDim.x < a.tiles) fetch(tile + gridDim.x);       // the next tile's rows, in flight under the product
         __syncthreads();
         // ---- phase 1: dz . A2
-        const bp_f32x16 acc = t.product();
+        const bp_f32x16 acc = t.product(a.a2);
         __syncthreads();                                         // every wave has read the tile's dz rows
         // ---- epilogue: the product back through the LDS tile, de = (dz . A2 + dz)(1 - x1^2) in the phase-0 layout
 #pragma unroll
@@ -1341,44 +1453,62 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void mlp_bwd_kernel(const
 }  // namespace ic3
 
 // Tile plan of the launch: as ic3_rnn_backward_partials, over the Q rows of the window (one launch, not one per step).
-extern "C" int ic3_mlp_backward_partials(long long Q, int H) { return tanh_partials(Q, H); }
+extern "C" int ic3_mlp_backward_partials(long long Q, int H) { return tanh_partials(Q, H, false); }
+extern "C" int ic3_mlp_backward_wide_partials(long long Q, int H) { return tanh_partials(Q, H, true); }
 
 extern "C" int ic3_mlp_backward_supported(const ic3_env* env, int H) { return tanh_supported(env, H); }
+extern "C" int ic3_mlp_backward_wide_supported(const ic3_env* env, int H) { return tanh_supported_wide(env, H); }
 
 // the launch alone (also the unit the tests drive): returns the number of partials written / added to
+static int mlp_backward_step(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT, const float* a2, float* dz,
+                             float* de, float* dbias_partials, int accumulate, long long Q, int H, ic3_stream stream, bool wide)
+{
+    using namespace ic3;
+    const char* const fn = wide ? "ic3_mlp_backward_step_wide: " : "ic3_mlp_backward_step: ";   // (a std::string only on the way out)
+    if (!x1_inout || !h || !dhead || !w_heads || !a2 || !dz || !de || !dbias_partials || Q <= 0) return fail(-22, std::string(fn) + "null argument");
+    if (!tanh_size_ok(H, wide)) return fail(-38, std::string(fn) + TANH_SIZES[wide]);
+    if (OT < 1) return fail(-22, std::string(fn) + "OT >= 1");
+    if (OT > 16) return fail(-38, std::string(fn) + "at most 16 output columns");
+    if (Q >= (1ll << 36)) return fail(-22, std::string(fn) + "Q < 2^36");
+    const int grid = tanh_partials(Q, H, wide);
+    const MlpBwdArgs a{ x1_inout, h, dhead, w_heads, a2, dz, de, dbias_partials, Q, OT, (int)((Q + 63) / 64), accumulate };
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = H == 256   ? launch_kernel(mlp_bwd_kernel<256>, dim3(grid), dim3(1024), TanhTile<256>::LDS_BYTES, s, a)
+                   : H == 128 ? launch_kernel(mlp_bwd_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES, s, a)
+                              : launch_kernel(mlp_bwd_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES, s, a);
+    return rc < 0 ? rc : grid;
+}
+
 extern "C" int ic3_mlp_backward_step(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT, const float* a2,
                                      float* dz, float* de, float* dbias_partials, int accumulate, long long Q, int H,
                                      ic3_stream stream)
 {
-    using namespace ic3;
-    if (!x1_inout || !h || !dhead || !w_heads || !a2 || !dz || !de || !dbias_partials || Q <= 0)
-        return fail(-22, "ic3_mlp_backward_step: null argument");
-    if (H != 64 && H != 128) return fail(-38, "ic3_mlp_backward_step: hid_size 64 / 128");
-    if (OT < 1) return fail(-22, "ic3_mlp_backward_step: OT >= 1");
-    if (OT > 16) return fail(-38, "ic3_mlp_backward_step: at most 16 output columns");
-    if (Q >= (1ll << 36)) return fail(-22, "ic3_mlp_backward_step: Q < 2^36");
-    const int grid = tanh_partials(Q, H);
-    const MlpBwdArgs a{ x1_inout, h, dhead, w_heads, a2, dz, de, dbias_partials, Q, OT, (int)((Q + 63) / 64), accumulate };
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = H == 128 ? launch_kernel(mlp_bwd_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES, s, a)
-                            : launch_kernel(mlp_bwd_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES, s, a);
-    return rc < 0 ? rc : grid;
+    return mlp_backward_step(x1_inout, h, dhead, w_heads, OT, a2, dz, de, dbias_partials, accumulate, Q, H, stream, false);
+}
+extern "C" int ic3_mlp_backward_step_wide(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT,
+                                          const float* a2, float* dz, float* de, float* dbias_partials, int accumulate, long long Q,
+                                          int H, ic3_stream stream)
+{
+    return mlp_backward_step(x1_inout, h, dhead, w_heads, OT, a2, dz, de, dbias_partials, accumulate, Q, H, stream, true);
 }
 
-extern "C" int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream)
+static int mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream, bool wide)
 {
     using namespace ic3;
-    if (int rc = window_open("ic3_mlp_backward", "ic3_mlp_bptt", env, b, tanh_supported,
-                             "hid_size 64 / 128, a grid whose encoder backward runs in its partial-sums form", true);
+    const char* const fn = wide ? "ic3_mlp_backward_wide" : "ic3_mlp_backward";
+    const std::string f = std::string(fn) + ": ";
+    if (int rc = window_open(fn, "ic3_mlp_bptt", env, b, wide ? tanh_supported_wide : tanh_supported,
+                             (std::string(TANH_SIZES[wide]) + ", a grid whose encoder backward runs in its partial-sums form").c_str(),
+                             true);
         rc < 0)
         return rc;
     const int T = b->T, E = b->E, N = b->N, H = b->H;
     if (!b->h || !b->dhead || !b->snaps || !b->enc_wt || !b->enc_bias || !b->a2 || !b->w_heads || !b->x1 || !b->dz || !b->de ||
         !b->dbias_partials || !b->enc_work)
-        return fail(-22, "ic3_mlp_backward: null argument");
-    if (b->a2_grad && !b->wgrad_scratch) return fail(-22, "ic3_mlp_backward: a2_grad needs wgrad_scratch");
+        return fail(-22, f + "null argument");
+    if (b->a2_grad && !b->wgrad_scratch) return fail(-22, f + "a2_grad needs wgrad_scratch");
     if (b->enc_window && ic3_env_encode_backward_window_work(env, H) <= 0)
-        return fail(-22, "ic3_mlp_backward: enc_window on a configuration without ic3_env_encode_backward_window");
+        return fail(-22, f + "enc_window on a configuration without ic3_env_encode_backward_window");
     const long long R = (long long)E * N, Q = (long long)T * R;
     // e of every recorded step -> the slots of the x1 ring (the step launch does not record its encoder rows)
     for (int t = 0; t < T; ++t) {
@@ -1386,13 +1516,16 @@ extern "C" int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream 
                                          b->x1 + (size_t)t * R * H, H, H, stream);
         if (rc < 0) return rc;
     }
-    int rc = ic3_mlp_backward_step(b->x1, b->h, b->dhead, b->w_heads, b->OT, b->a2, b->dz, b->de, b->dbias_partials, 0, Q, H, stream);
+    int rc = mlp_backward_step(b->x1, b->h, b->dhead, b->w_heads, b->OT, b->a2, b->dz, b->de, b->dbias_partials, 0, Q, H, stream, wide);
     if (rc < 0) return rc;
     rc = encoder_tail(env, b->snaps, b->snap_words, T, b->de, H, R * H, H, b->enc_work, b->enc_first, b->enc_window != 0, stream);
     if (rc < 0) return rc;
     if (b->a2_grad) {
-        rc = ic3_rnn_weight_grad(b->dz, b->x1, nullptr, Q, H, b->a2_grad, 1, b->wgrad_scratch, stream);
+        rc = rnn_weight_grad(b->dz, b->x1, nullptr, Q, H, b->a2_grad, 1, b->wgrad_scratch, stream, wide);
         if (rc < 0) return rc;
     }
     return 0;
 }
+
+extern "C" int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream) { return mlp_backward(env, b, stream, false); }
+extern "C" int ic3_mlp_backward_wide(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream) { return mlp_backward(env, b, stream, true); }

@@ -431,17 +431,17 @@ def bptt_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lst
 
 
 def rnn_backward_supported(env, H):
-    """ic3_rnn_backward_supported: the tanh-recurrence baseline's window backward runs for this env handle at hid_size H."""
-    return bool(_lib.lib().ic3_rnn_backward_supported(env._h, int(H)))
+    """ic3_rnn_backward_wide_supported: the tanh-recurrence baseline's window backward runs for this env handle at hid_size H."""
+    return bool(_lib.lib().ic3_rnn_backward_wide_supported(env._h, int(H)))
 
 
 def rnn_backward_partials(R, H):
-    """Rows of ic3_rnn_bptt.dbias_partials (ic3_rnn_backward_partials)."""
-    return int(_lib.lib().ic3_rnn_backward_partials(int(R), int(H)))
+    """Rows of ic3_rnn_bptt.dbias_partials (ic3_rnn_backward_wide_partials)."""
+    return int(_lib.lib().ic3_rnn_backward_wide_partials(int(R), int(H)))
 
 
 def rnn_tanh_backward_step(dh_in, h_t, dhead, w_heads, a2, dz, dh_out, dbias_partials, out_scale=None, accumulate=False):
-    """ic3_rnn_tanh_backward_step: one step of the tanh recurrence's chain — dz = (dh_in + dhead . w_heads) * (1 - h_t^2),
+    """ic3_rnn_tanh_backward_step_wide: one step of the tanh recurrence's chain — dz = (dh_in + dhead . w_heads) * (1 - h_t^2),
     dh_out = (dz . a2) * out_scale, column sums of dz into dbias_partials (rnn_backward_partials(R, H) rows).  dh_in None: zeros;
     dh_out may be dh_in."""
     _need_cuda(h_t, "rnn_tanh_backward_step")
@@ -452,13 +452,13 @@ def rnn_tanh_backward_step(dh_in, h_t, dhead, w_heads, a2, dz, dh_out, dbias_par
     assert dhead.is_contiguous() and tuple(dhead.shape) == (R, OT) and dhead.dtype == torch.float32
     assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and a2.is_contiguous() and tuple(a2.shape) == (H, H)
     assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (rnn_backward_partials(R, H), H)
-    n = _lib.lib().ic3_rnn_tanh_backward_step(ptr(dh_in), ptr(h_t), ptr(dhead), ptr(w_heads), OT, ptr(a2), _rowvec(out_scale, R),
+    n = _lib.lib().ic3_rnn_tanh_backward_step_wide(ptr(dh_in), ptr(h_t), ptr(dhead), ptr(w_heads), OT, ptr(a2), _rowvec(out_scale, R),
                                               ptr(dz), ptr(dh_out), ptr(dbias_partials), int(bool(accumulate)), R, H, stream())
     return check(n)
 
 
 def rnn_weight_grad(dz, h_prev, dA2, row_live=None, accumulate=True, work=None):
-    """ic3_rnn_weight_grad: dA2 (H, H) (+)= dz^T @ (row_live h_prev) over all Q rows of a window in one launch.  dz, h_prev (Q, H)
+    """ic3_rnn_weight_grad_wide: dA2 (H, H) (+)= dz^T @ (row_live h_prev) over all Q rows of a window in one launch.  dz, h_prev (Q, H)
     contiguous (leading dims may be (T, R)), row_live (Q,) or None."""
     _need_cuda(dz, "rnn_weight_grad")
     H = dz.shape[-1]
@@ -468,16 +468,16 @@ def rnn_weight_grad(dz, h_prev, dA2, row_live=None, accumulate=True, work=None):
     assert dA2.is_contiguous() and tuple(dA2.shape) == (H, H)
     if row_live is not None:
         assert row_live.is_contiguous() and row_live.dtype == torch.float32 and row_live.numel() == Q
-    n = int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(Q, H))
+    n = int(_lib.lib().ic3_rnn_weight_grad_wide_scratch_floats(Q, H))
     if n == 0:
-        raise NotImplementedError("rnn_weight_grad: hid_size 64 / 128")
-    check(_lib.lib().ic3_rnn_weight_grad(ptr(dz), ptr(h_prev), ptr(row_live), Q, H, ptr(dA2), int(bool(accumulate)),
+        raise NotImplementedError("rnn_weight_grad: hid_size 64 / 128 / 256")
+    check(_lib.lib().ic3_rnn_weight_grad_wide(ptr(dz), ptr(h_prev), ptr(row_live), Q, H, ptr(dA2), int(bool(accumulate)),
                                          ptr(_scratch(work, 'rnn_wgrad', n, dz.device)), stream()))
 
 
 def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_partials, h_last=None, detach_gap=0, row_live=None,
                  row_keep=None, enc_first=True, enc_window=True, a2_grad=None, work=None):
-    """ic3_rnn_backward: the backward through a window of T recorded steps of the tanh-recurrence baseline as one host call (one
+    """ic3_rnn_backward_wide: the backward through a window of T recorded steps of the tanh-recurrence baseline as one host call (one
     launch per step, the encoder's first stage over the dz ring — enc_window — or per step, and with a2_grad affine2's weight
     gradient over the window).  hs (>= T, R, H) the states entering the steps (slot T, or h_last, the state leaving the last one),
     dhead (T, R, OT), dz (T, R, H) the ring, dbias_partials (rnn_backward_partials(R, H), H) added to."""
@@ -509,23 +509,23 @@ def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_p
     b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
     if a2_grad is not None:
         assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
-        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H)), hs.device)
+        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_wide_scratch_floats(T * R, H)), hs.device)
         b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), scratch.data_ptr()       # (`scratch`: alive until the call has returned)
-    check(_lib.lib().ic3_rnn_backward(env._h, C.byref(b), stream()))
+    check(_lib.lib().ic3_rnn_backward_wide(env._h, C.byref(b), stream()))
 
 
 def mlp_backward_supported(env, H):
-    """ic3_mlp_backward_supported: the IC baseline's (models.MLP) window backward runs for this env handle at hid_size H."""
-    return bool(_lib.lib().ic3_mlp_backward_supported(env._h, int(H)))
+    """ic3_mlp_backward_wide_supported: the IC baseline's (models.MLP) window backward runs for this env handle at hid_size H."""
+    return bool(_lib.lib().ic3_mlp_backward_wide_supported(env._h, int(H)))
 
 
 def mlp_backward_partials(Q, H):
-    """Rows of ic3_mlp_bptt.dbias_partials for a window of Q = T x R rows (ic3_mlp_backward_partials)."""
-    return int(_lib.lib().ic3_mlp_backward_partials(int(Q), int(H)))
+    """Rows of ic3_mlp_bptt.dbias_partials for a window of Q = T x R rows (ic3_mlp_backward_wide_partials)."""
+    return int(_lib.lib().ic3_mlp_backward_wide_partials(int(Q), int(H)))
 
 
 def mlp_backward_step(x1, h, dhead, w_heads, a2, dz, de, dbias_partials, accumulate=False):
-    """ic3_mlp_backward_step: the IC baseline's backward over Q independent rows in one launch — x1 (Q, H) holds e = affine1(obs)
+    """ic3_mlp_backward_step_wide: the IC baseline's backward over Q independent rows in one launch — x1 (Q, H) holds e = affine1(obs)
     on entry and tanh(e) on return, dz = (dhead . w_heads) * (1 - h^2), de = (dz . a2 + dz) * (1 - x1^2), column sums of dz into
     dbias_partials (mlp_backward_partials(Q, H) rows).  Leading dims may be (T, R)."""
     _need_cuda(h, "mlp_backward_step")
@@ -537,14 +537,14 @@ def mlp_backward_step(x1, h, dhead, w_heads, a2, dz, de, dbias_partials, accumul
     assert dhead.is_contiguous() and dhead.numel() == Q * OT and dhead.dtype == torch.float32
     assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and a2.is_contiguous() and tuple(a2.shape) == (H, H)
     assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (mlp_backward_partials(Q, H), H)
-    n = _lib.lib().ic3_mlp_backward_step(ptr(x1), ptr(h), ptr(dhead), ptr(w_heads), OT, ptr(a2), ptr(dz), ptr(de),
+    n = _lib.lib().ic3_mlp_backward_step_wide(ptr(x1), ptr(h), ptr(dhead), ptr(w_heads), OT, ptr(a2), ptr(dz), ptr(de),
                                          ptr(dbias_partials), int(bool(accumulate)), Q, H, stream())
     return check(n)
 
 
 def mlp_backward(env, T, E, N, H, h, dhead, snaps, enc_wt, enc_bias, a2, w_heads, x1, dz, de, dbias_partials, loc_table=None,
                  enc_first=True, enc_window=True, a2_grad=None, work=None):
-    """ic3_mlp_backward: the backward through a window of T recorded steps of the IC baseline (models.MLP) as one host call —
+    """ic3_mlp_backward_wide: the backward through a window of T recorded steps of the IC baseline (models.MLP) as one host call —
     T encoder launches into the x1 ring, ONE launch over all T x R rows, the encoder's first stage over the de ring (enc_window,
     or per step) and with a2_grad affine2's weight gradient over the window.  h (>= T, R, H) the state every step ended with,
     dhead (T, R, OT), x1 / dz / de (T, R, H) the rings, dbias_partials (mlp_backward_partials(T * R, H), H) written."""
@@ -574,9 +574,9 @@ def mlp_backward(env, T, E, N, H, h, dhead, snaps, enc_wt, enc_bias, a2, w_heads
     b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
     if a2_grad is not None:
         assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
-        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_scratch_floats(T * R, H)), h.device)
+        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_wide_scratch_floats(T * R, H)), h.device)
         b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), scratch.data_ptr()       # (`scratch`: alive until the call has returned)
-    check(_lib.lib().ic3_mlp_backward(env._h, C.byref(b), stream()))
+    check(_lib.lib().ic3_mlp_backward_wide(env._h, C.byref(b), stream()))
 
 
 HEADS_GRAD_MAX_OT = 16      # ic3_heads_grad: at most 16 output columns (the heads' actions in total + the value)

@@ -319,8 +319,9 @@ class Trainer(object):
     def _record_h_fin(self, T, R):
         """Native update of the IC baseline (models.MLP): let every step launch of the recorded rollout store the hidden state it
         ends with in the episode record (ic3_commnet_step's h_out), so the backward runs over the whole window in one launch
-        (bptt._backward_window_mlp) — where that path can run at all (bptt.mlp_window_wanted: hid 64 / 128, no padded twin, the
-        native loop on, the library's answer) and the buffer stays within half of what the device can still give."""
+        (bptt._backward_window_mlp) — where that path can run at all (bptt.mlp_window_wanted: hid 64 / 128 / 256, no padded twin, the
+        native loop on, the library's answer) and the buffer stays within half of what the device can still give (T x R x H floats:
+        at hid 256 twice the bytes of 128, beside the backward's three rings of that size — bptt._mlp_window_ok asks for those)."""
         a = self.args
         raw = getattr(self.env, 'env', None)
         if raw is None or not bptt.mlp_window_wanted(a, self.policy_net, raw):

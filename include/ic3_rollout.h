@@ -507,7 +507,7 @@ int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream stream);
  *   dbias_partials [ic3_rnn_backward_partials(R, H)][H] ADDED to (zero them first);  enc_work as the encoder form asks, enc_first
  *   != 0: this window starts the accumulation;  a2_grad [H][H] ADDED to (or NULL: no weight gradient here), wgrad_scratch
  *   ic3_rnn_weight_grad_scratch_floats(T * R, H) floats.
- * No float atomics: dz, dh, the partials and a2_grad are identical run to run.  hid_size 64 / 128.
+ * No float atomics: dz, dh, the partials and a2_grad are identical run to run.  hid_size 64 / 128 (256: the _wide entries below).
  * ic3_rnn_backward_supported(env, H): 1 when every step can run (hid_size 64 / 128, the encoder backward in its partial-sums form).
  * ic3_rnn_tanh_backward_step: one step of the chain on its own (dh_in NULL: zeros; dh_out may be dh_in; out_scale [R] or NULL);
  * returns the number of partials written (accumulate == 0) or added to. */
@@ -540,10 +540,28 @@ int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream);
 /* affine2's weight gradient over a whole window in one launch (+ a fixed-order reduction): dA2 [H][H] (+)= dz^T . (row_live h_prev)
  * over Q = steps x rows pairs — dz [Q][H] (ic3_rnn_backward's ring), h_prev [Q][H] (slots 0..T-1 of the recorded states), row_live
  * [Q] or NULL.  Exact fp32 products on the fp32 matrix instruction, split-K over the CUs, slices summed in order (reproducible).
- * scratch: ic3_rnn_weight_grad_scratch_floats(Q, H) floats.  hid_size 64 / 128. */
+ * scratch: ic3_rnn_weight_grad_scratch_floats(Q, H) floats.  hid_size 64 / 128 (256: the _wide pair below). */
 size_t ic3_rnn_weight_grad_scratch_floats(long long Q, int H);
 int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const float* row_live /* or NULL */, long long Q, int H, float* dA2,
                         int accumulate, float* scratch, ic3_stream stream);
+
+/* The tanh-recurrence entries above for hid_size 64 / 128 / 256 (added beside them, whose 64 / 128 contract stays: their queries
+ * answer 0 at 256 and their calls -ENOSYS).  Same arguments, the same ic3_rnn_bptt descriptor (struct_size checked first),
+ * wgrad_scratch sized by the _wide query.  At 64 / 128: what the entries above answer and launch — the same partial counts, kernels and bits.
+ * At 256: affine2.weight (256 KB) does not fit a CU's LDS beside the tile, so the step launch streams its matrix fragments from L2;
+ * a workgroup still owns all 256 columns of its 64-row tiles (dh_out may be dh_in), ic3_rnn_backward_wide_partials(R, 256) is the
+ * number of those workgroups and dbias_partials[p] workgroup p's column sums over all 256 columns (one tile per workgroup: the
+ * tile's sums).  The weight gradient runs its tile of 128 on the four output quadrants, K slices in whole rounds of workgroups so
+ * that a slice stays below 2 GB.  No float atomics at any size.  Other sizes: -ENOSYS, the queries answer 0. */
+int ic3_rnn_backward_wide_supported(const ic3_env* env, int H);
+int ic3_rnn_backward_wide_partials(long long R, int H);
+int ic3_rnn_tanh_backward_step_wide(const float* dh_in /* or NULL */, const float* h_t, const float* dhead, const float* w_heads, int OT,
+                                    const float* a2, const float* out_scale /* or NULL */, float* dz, float* dh_out,
+                                    float* dbias_partials, int accumulate, long long R, int H, ic3_stream stream);
+int ic3_rnn_backward_wide(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream);
+size_t ic3_rnn_weight_grad_wide_scratch_floats(long long Q, int H);
+int ic3_rnn_weight_grad_wide(const float* dz, const float* h_prev, const float* row_live /* or NULL */, long long Q, int H, float* dA2,
+                             int accumulate, float* scratch, ic3_stream stream);
 
 /* The backward through a window of T recorded steps of the IC baseline (models.py:23-34, models.MLP: e = affine1(obs),
  * x1 = tanh(e), h = tanh(affine2(x1) + x1), heads and value on h) as ONE host call.  No state crosses a step, so the window is
@@ -563,7 +581,8 @@ int ic3_rnn_weight_grad(const float* dz, const float* h_prev, const float* row_l
  *   x1, dz, de [T][R][H]: the rings (written);  dbias_partials [ic3_mlp_backward_partials(T * R, H)][H] (written);  enc_work as the
  *   encoder form asks, enc_first != 0: this window starts the accumulation;  a2_grad [H][H] ADDED to (or NULL: no weight
  *   gradient here), wgrad_scratch ic3_rnn_weight_grad_scratch_floats(T * R, H) floats.
- * No float atomics: the rings, the partials and a2_grad are identical run to run.  hid_size 64 / 128 and OT <= 16, -ENOSYS otherwise.
+ * No float atomics: the rings, the partials and a2_grad are identical run to run.  hid_size 64 / 128 (256: the _wide entries below)
+ * and OT <= 16, -ENOSYS otherwise.
  * ic3_mlp_backward_supported(env, H): 1 when the call can run (hid_size 64 / 128, the encoder backward in its partial-sums form).
  * ic3_mlp_backward_step: the launch alone over Q rows (64-bit row offsets: Q x H x 4 may pass 4 GB) — x1_inout holds e on entry
  * and x1 on return; returns the number of partials written (accumulate == 0) or added to, ic3_mlp_backward_partials(Q, H). */
@@ -593,6 +612,19 @@ int ic3_mlp_backward_partials(long long Q, int H);
 int ic3_mlp_backward_step(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT, const float* a2,
                           float* dz, float* de, float* dbias_partials, int accumulate, long long Q, int H, ic3_stream stream);
 int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream);
+
+/* The IC baseline's entries above for hid_size 64 / 128 / 256 (added beside them, whose 64 / 128 contract stays).  Same arguments,
+ * the same ic3_mlp_bptt descriptor (struct_size checked first), wgrad_scratch sized by ic3_rnn_weight_grad_wide_scratch_floats.
+ * At 64 / 128:
+ * what the entries above answer and launch, the same bits.  At 256: the launch streams affine2.weight's matrix fragments from L2
+ * (as ic3_rnn_tanh_backward_step_wide), 64-bit row offsets and 16-byte stores as at 128; ic3_mlp_backward_wide_partials(Q, 256) is
+ * the number of row-owning workgroups, dbias_partials[p] workgroup p's column sums over all 256 columns.  Other sizes: -ENOSYS,
+ * the queries answer 0. */
+int ic3_mlp_backward_wide_supported(const ic3_env* env, int H);
+int ic3_mlp_backward_wide_partials(long long Q, int H);
+int ic3_mlp_backward_step_wide(float* x1_inout, const float* h, const float* dhead, const float* w_heads, int OT, const float* a2,
+                               float* dz, float* de, float* dbias_partials, int accumulate, long long Q, int H, ic3_stream stream);
+int ic3_mlp_backward_wide(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream);
 /* The weight / bias gradient of the heads + value head over a whole episode in one pass (trainer.py:128-225 through
  * comm.py:228,239): dW [OT][H] += sum_m d[m][o] h[m][c], db [OT] += sum_m d[m][o] over the M = steps x rows pairs
  * (d [M][OT], h [M][H]: h_t of every step, i.e. the recorded hidden states shifted by one step).  scratch:
