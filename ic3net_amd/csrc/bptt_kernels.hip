@@ -536,18 +536,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     dW[i] = accumulate ? dW[i] + s : s;
 }
 
-static int bp_cus()
-{
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return cus[dev];
-}
-
 }  // namespace ic3
 
 // ---- ic3_comm_backward -------------------------------------------------------------------------------------------------------
@@ -604,7 +592,7 @@ struct WGradPlan {
 };
 static WGradPlan wgrad_plan(long long Q, int ny, long long row_floats)
 {
-    int ks = 2 * ic3::bp_cus() / ny;
+    int ks = 2 * ic3::device_cus() / ny;
     const long long most = (Q + 15) / 16;
     if (ks > most) ks = (int)most;
     if (ks < 1) ks = 1;
@@ -1183,7 +1171,7 @@ static int tanh_partials(long long rows, int H, bool wide)
 {
     if (rows <= 0 || (H != 64 && H != 128 && !(wide && H == 256))) return 0;
     const long long tiles = (rows + 63) / 64;
-    const long long cap = (long long)ic3::bp_cus() * (H == 64 ? 2 : 1);
+    const long long cap = (long long)ic3::device_cus() * (H == 64 ? 2 : 1);
     const long long rounds = (tiles + cap - 1) / cap;
     return (int)((tiles + rounds - 1) / rounds);
 }

@@ -20,11 +20,11 @@
 // draws, step, obs).
 #include <type_traits>
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include "env_device.hpp"
 #include "ic3_common.hpp"
 #include "ps_common.hpp"
+#include "step_launch.hpp"
 
 namespace ic3 {
 
@@ -129,37 +129,10 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
             }
         }
         int2* ptab = reinterpret_cast<int2*>(tile + ((2 * a.EPT * total + 3) & ~3));
-        if constexpr (KIND == IC3_ENV_PP) {
-            int32_t* psr = tile;
-            int32_t* psc = tile + a.EPT * total;
-            for (int i = tid; i < nenv * total; i += NT) {
-                psr[i] = a.pp.loc_r[(size_t)e0 * total + i];
-                psc[i] = a.pp.loc_c[(size_t)e0 * total + i];
-            }
-        } else {
-            for (int i = tid; i < nenv * N; i += NT) {
-                const int el = div_small(i, invN);
-                tj_tile_load_car(tj_tile_at(tile + el * tjw, N), a.tj, e0 + el, i - el * N);
-            }
-        }
+        step_desc_positions<KIND>(tile, e0, nenv, a.pp, a.tj, a.EPT, N, tid, NT);
         __syncthreads();
-        const float inv_nsegE = 1.0f / (float)max(nsegE, 1), inv_WW = 1.0f / (float)max(WW, 1);
-        for (int sg = tid; sg < nenv * nsegE; sg += NT) {
-            const int el = div_small(sg, inv_nsegE), q = sg - el * nsegE;
-            int2 d;
-            if constexpr (KIND == IC3_ENV_PP) {
-                d = pp_tab_entry(tile + el * total, tile + a.EPT * total + el * total, q, a.pp.Np, total, a.pp.dim, a.pp.v);
-                ptab[sg] = d;
-            } else {
-                const TJTile t = tj_tile_at(tile + el * tjw, N);
-                d = tj_tab_entry(t, a.tj, q);
-                t.tab[q] = d;
-            }
-            if (d.y != 0 && WW <= 32) {
-                const int ag = div_small(q, inv_WW);
-                atomicOr(&rmask[el * N + ag], 1u << (q - ag * WW));
-            }
-        }
+        const StepDescGeom dg = { N, WW, total, nsegE, tjw, invN, 1.0f / (float)max(nsegE, 1), 1.0f / (float)max(WW, 1) };
+        step_desc_tab<KIND>(tile, nenv, a.pp, a.tj, a.EPT, dg, rmask, tid, NT);
         __syncthreads();
         // ---- the dense observation rows of the state this step acts on (trainer.py:49), every element stored once ------------
         // Round 6, TJ: the tile's contiguous chunk of the obs tensor (~96-98 % zeros) is ZERO-FILLED here with 16-byte stores — no
@@ -411,26 +384,12 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
             continue;
         }
         const int A = sizes[hd];
-        float mx = -INFINITY;
-        for (int o = 0; o < A; ++o) mx = fmaxf(mx, z[off + o]);
-        float sum = 0.0f;
-        for (int o = 0; o < A; ++o) sum += __builtin_amdgcn_exp2f(1.4426950408889634f * (z[off + o] - mx));
-        const float lse = mx + 0.6931471805599453f * __builtin_amdgcn_logf(sum);
-        for (int o = 0; o < A; ++o) orow[off + o] = z[off + o] - lse;
-        if constexpr (KIND != 0) {          // the draw of this (row, head): same counters and arithmetic as sample_actions_env_kernel
+        const float lse = head_log_softmax(z, orow, off, A);
+        if constexpr (KIND != 0) {          // the draw of this (row, head): the counters of sample_actions_env_kernel
             const int el = div_small(tr, invN), n = tr - el * N;
             const uint32_t x = philox_x24(a.seed, a.gid0 + (uint32_t)(e0 + el), DOMAIN_SAMPLE, (uint32_t)sep[el],
                                           (uint32_t)sts[el], (uint32_t)(hd * N + n));
-            const float u = (float)x * (1.0f / 16777216.0f);
-            float cdf = 0.0f;
-            int act = A - 1;
-            for (int o = 0; o < A - 1; ++o) {
-                cdf += expf(z[off + o] - lse);
-                if (u < cdf) {
-                    act = o;
-                    break;
-                }
-            }
+            const int act = draw_action(x, A, [&](int o) { return z[off + o] - lse; });
             a.action[(size_t)hd * ((size_t)a.E * N) + r0 + tr] = act;
             if (hd == 0) sact[tr] = act;
         }
@@ -537,8 +496,9 @@ extern "C" int ic3_commnet_forward(const float* enc, int E, int N, int H, int co
         return fail(-22, "ic3_commnet_forward: bad arguments");
     if (!ic3_commnet_forward_supported(H, N))
         return fail(-38, "ic3_commnet_forward: needs hid_size 64/128/256 and <= 64 agents per env");
-    if (nheads < 1 || nheads > 4) return fail(-22, "ic3_commnet_forward: 1..4 action heads");
     CommnetArgs a{};
+    int sz[4];
+    if (int rc = parse_heads(head_sizes, nheads, "ic3_commnet_forward", a.OT, sz)) return rc;
     a.enc = enc;
     a.wp = wp;
     a.wp3 = wp3;
@@ -556,14 +516,6 @@ extern "C" int ic3_commnet_forward(const float* enc, int E, int N, int H, int co
     a.mode_avg = mode_avg;
     a.comm_zero = comm_zero;
     a.nheads = nheads;
-    int sz[4] = { 0, 0, 0, 0 };
-    a.OT = 1;
-    for (int i = 0; i < nheads; ++i) {
-        sz[i] = head_sizes[i];
-        if (sz[i] < 1) return fail(-22, "ic3_commnet_forward: empty action head");
-        a.OT += sz[i];
-    }
-    if (a.OT > 16) return fail(-22, "ic3_commnet_forward: more than 15 actions in total");
     a.a0 = sz[0];
     a.a1 = sz[1];
     a.a2 = sz[2];
@@ -573,32 +525,10 @@ extern "C" int ic3_commnet_forward(const float* enc, int E, int N, int H, int co
     a.EPTs = a.EPT;
     const size_t lds = ((size_t)64 * (2 * H + 4) + 3 * 64 + 64 * 16 + 4 * 64) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define IC3_CN(h)                                                                                                 \
-    case h:                                                                                                       \
-        IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(commnet_forward_kernel<h, 0>), lds));               \
-        hipLaunchKernelGGL((commnet_forward_kernel<h, 0>), dim3(tiles), dim3(2 * h), lds, s, a);                       \
-        break;
-    switch (H) {
-        IC3_CN(64)
-        IC3_CN(128)
-        IC3_CN(256)
-    }
-#undef IC3_CN
-    IC3_HIP(hipGetLastError());
-    return 0;
-}
-
-// CUs of the current device (the tile plans below)
-static int commnet_cus()
-{
-    static int cu_count[64] = { 0 };   // per device (a process may drive several GPUs)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cu_count[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cu_count[dev] = prop.multiProcessorCount;
-    }
-    return cu_count[dev] ? cu_count[dev] : 256;
+    return with_hid(H, [&](auto hid) {
+        constexpr int HH = decltype(hid)::value;
+        return launch_kernel(commnet_forward_kernel<HH, 0>, dim3(tiles), dim3(2 * HH), lds, s, a);
+    });
 }
 
 // Envs per tile of the NARROW Predator-Prey launch (the IC baseline's stand-in, the tanh recurrence).  That launch is bound by its
@@ -611,7 +541,7 @@ static int commnet_cus()
 // five tile sizes against this choice.
 static int plan_store_bound_ept(int E, int ept_max)
 {
-    const int cus = commnet_cus();
+    const int cus = ic3::device_cus();
     int best = ept_max;
     double best_cost = 0.0;
     for (int ept = ept_max; ept >= 1 && ept >= ept_max / 3; --ept) {
@@ -638,7 +568,7 @@ static int plan_commnet_tiles(ic3::CommnetArgs& a)
     const int n_all = (a.E + a.EPT - 1) / a.EPT;
     a.n_full = n_all;
     a.EPTs = a.EPT;
-    const int cus = commnet_cus(), epts = 32 / a.N;
+    const int cus = ic3::device_cus(), epts = 32 / a.N;
     if (epts < 1) return n_all;
     const int n_full = (a.E / a.EPT) / cus * cus;
     if (n_full < cus) return n_all;
@@ -651,18 +581,9 @@ static int plan_commnet_tiles(ic3::CommnetArgs& a)
     return n_all;
 }
 
-static size_t commnet_step_tile_words(const ic3_env* env)
-{
-    const int N = env->dims.N, EPT = 64 / N, WW = env->dims.window * env->dims.window;
-    size_t w;
-    if (env->kind == IC3_ENV_PP) w = (size_t)((2 * EPT * (env->pp.N + env->pp.nprey) + 3) & ~3) + (size_t)2 * EPT * N * WW;
-    else w = (size_t)EPT * (((7 * N + 3) & ~3) + 2 * N * WW);
-    return (w + 3) & ~(size_t)3;
-}
-
 static size_t commnet_step_lds(const ic3_env* env, int H, bool narrow = false)
 {
-    return ((size_t)64 * ((narrow ? H : 2 * H) + 4) + 3 * 64 + 64 * 16 + 4 * 64 + commnet_step_tile_words(env) + (narrow ? 16 * H : 0)) *
+    return ((size_t)64 * ((narrow ? H : 2 * H) + 4) + 3 * 64 + 64 * 16 + 4 * 64 + ic3::step_tile_words(env) + (narrow ? 16 * H : 0)) *
            sizeof(float);
 }
 
@@ -687,7 +608,7 @@ extern "C" int ic3_commnet_step(ic3_env* env, const float* enc_wt, const float* 
         comm_passes < 1)
         return fail(-22, "ic3_commnet_step: bad arguments");
     if (env->resets == 0) return fail(-22, "ic3_commnet_step: reset() has not been called");
-    if (nheads < 1 || nheads > 4) return fail(-22, "ic3_commnet_step: 1..4 action heads");
+    if (nheads < 1 || nheads > 4) return fail(-22, "ic3_commnet_step: 1..4 action heads");   // (parse_heads below checks the sizes, behind the shape check)
     const int lds = ic3_commnet_step_supported(env, H);
     if (!lds)
         return fail(-38, "ic3_commnet_step: needs hid_size 64/128/256, <= 64 agents per env and an env tile that fits in LDS (use "
@@ -703,22 +624,12 @@ extern "C" int ic3_commnet_step(ic3_env* env, const float* enc_wt, const float* 
     a.out = out;
     a.h_in = h_in;
     a.h_out = h_out;
-    a.E = env->dims.E;
-    a.N = env->dims.N;
-    a.EPT = 64 / a.N;
     a.passes = comm_passes;
-    a.auto_reset = env->auto_max_steps > 0;
     a.mode_avg = mode_avg;
     a.comm_zero = comm_zero;
     a.nheads = nheads;
-    int sz[4] = { 0, 0, 0, 0 };
-    a.OT = 1;
-    for (int i = 0; i < nheads; ++i) {
-        sz[i] = head_sizes[i];
-        if (sz[i] < 1) return fail(-22, "ic3_commnet_step: empty action head");
-        a.OT += sz[i];
-    }
-    if (a.OT > 16) return fail(-22, "ic3_commnet_step: more than 15 actions in total");
+    int sz[4];
+    if (int rc = parse_heads(head_sizes, nheads, "ic3_commnet_step", a.OT, sz)) return rc;
     a.a0 = sz[0];
     a.a1 = sz[1];
     a.a2 = sz[2];
@@ -727,29 +638,12 @@ extern "C" int ic3_commnet_step(ic3_env* env, const float* enc_wt, const float* 
     a.enc_bias = reinterpret_cast<const cn_f32x4*>(enc_bias);
     a.loc_table = reinterpret_cast<const cn_f32x4*>(loc_table);
     a.obs = obs;
-    a.obs_dim = env->dims.obs_dim;
     a.action = action;
-    a.tile_words = (int)commnet_step_tile_words(env);
-    a.episode = env->f("episode");
-    a.tstep = env->f("t");
-    a.so = StepOut{ reward, done, alive, is_completed, env->d_err };
+    hipEvent_t ev0, ev1;   // one-shot (ic3_env_set_step_events): the dispatch itself stamps the caller's events
+    fill_env_args(a, env, reward, done, alive, is_completed, true, ev0, ev1);
     const bool pp = env->kind == IC3_ENV_PP;
-    if (pp) {
-        a.pp = pp_state_of(env);
-        a.G = group_lanes(a.N);
-        a.seed = env->pp.seed;
-        a.gid0 = env->pp.env_id_offset;
-    } else {
-        a.tj = tj_state_of(env);
-        a.G = tj_group(a.N);
-        a.seed = env->tj.seed;
-        a.gid0 = env->tj.env_id_offset;
-    }
     env->touch_obs(obs);
     hipStream_t s = (hipStream_t)stream;
-    // one-shot (ic3_env_set_step_events): the dispatch itself stamps the caller's events
-    hipEvent_t ev0 = (hipEvent_t)env->ev_start, ev1 = (hipEvent_t)env->ev_stop;
-    env->ev_start = env->ev_stop = nullptr;
     // one pass, communication off, split products: the narrow tile (three workgroups per CU)
     const bool narrow = wp3 && comm_zero && comm_passes == 1;
     const size_t ldsn = commnet_step_lds(env, H, true);
@@ -762,28 +656,12 @@ extern "C" int ic3_commnet_step(ic3_env* env, const float* enc_wt, const float* 
     } else {
         tiles = plan_commnet_tiles(a);
     }
-#define IC3_CS(h)                                                                                                          \
-    case h:                                                                                                                \
-        if (narrow && pp) {                                                                                                \
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(commnet_forward_kernel<h, IC3_ENV_PP, true>), ldsn)); \
-            hipExtLaunchKernelGGL((commnet_forward_kernel<h, IC3_ENV_PP, true>), dim3(tiles), dim3(2 * h), ldsn, s, ev0, ev1, 0, a); \
-        } else if (narrow) {                                                                                               \
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(commnet_forward_kernel<h, IC3_ENV_TJ, true>), ldsn)); \
-            hipExtLaunchKernelGGL((commnet_forward_kernel<h, IC3_ENV_TJ, true>), dim3(tiles), dim3(2 * h), ldsn, s, ev0, ev1, 0, a); \
-        } else if (pp) {                                                                                                   \
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(commnet_forward_kernel<h, IC3_ENV_PP>), lds));        \
-            hipExtLaunchKernelGGL((commnet_forward_kernel<h, IC3_ENV_PP>), dim3(tiles), dim3(2 * h), lds, s, ev0, ev1, 0, a); \
-        } else {                                                                                                           \
-            IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(commnet_forward_kernel<h, IC3_ENV_TJ>), lds));        \
-            hipExtLaunchKernelGGL((commnet_forward_kernel<h, IC3_ENV_TJ>), dim3(tiles), dim3(2 * h), lds, s, ev0, ev1, 0, a); \
-        }                                                                                                                  \
-        break;
-    switch (H) {
-        IC3_CS(64)
-        IC3_CS(128)
-        IC3_CS(256)
-    }
-#undef IC3_CS
-    IC3_HIP(hipGetLastError());
-    return 0;
+    return with_hid(H, [&](auto hid) {
+        constexpr int HH = decltype(hid)::value;
+        const dim3 grid(tiles), block(2 * HH);
+        if (narrow && pp) return launch_kernel_timed(commnet_forward_kernel<HH, IC3_ENV_PP, true>, grid, block, ldsn, s, ev0, ev1, a);
+        if (narrow) return launch_kernel_timed(commnet_forward_kernel<HH, IC3_ENV_TJ, true>, grid, block, ldsn, s, ev0, ev1, a);
+        if (pp) return launch_kernel_timed(commnet_forward_kernel<HH, IC3_ENV_PP>, grid, block, (size_t)lds, s, ev0, ev1, a);
+        return launch_kernel_timed(commnet_forward_kernel<HH, IC3_ENV_TJ>, grid, block, (size_t)lds, s, ev0, ev1, a);
+    });
 }

@@ -705,6 +705,67 @@ __device__ __forceinline__ void tj_obs_store_run(int32_t* tiles, int tile_words,
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Window descriptors of a tile's envs in LDS: the one-launch rollout steps (policy_step_kernel, commnet_forward_kernel)
+// ------------------------------------------------------------------------------------------------
+// Descriptors of `ne` envs starting at env `eb`, built by the NT threads of a workgroup into the LDS block `tl` (its size:
+// step_tile_words, step_launch.hpp):  PP: sr[EPT*total] | sc[EPT*total] | tab[EPT*N*WW] (int2);  TJ: EPT x TJTile.
+// Two phases with a barrier of the caller's between them: the positions, then the per-cell table, which also ORs the cells that
+// carry a count into rmask[row] (WW <= 32: the rows of the encoder only visit the cells flagged there).  The positions derive
+// total / the TJ tile stride from pp / tj / N by the expressions the callers fill StepDescGeom with (tj_tile_words(N, WW));
+// the table takes the geometry its caller holds for the encoder phase behind it.  Handing the positions the struct as well
+// raises commnet_forward_kernel's VGPR count.
+// (The env.step loop over a tile's lanes is kept per kernel: sharing it raised commnet_forward_kernel's SGPR spills.)
+struct StepDescGeom {
+    int N, WW, total, nsegE, tjw;          // agents, window cells, PP entities per env, N * WW, tj_tile_words(N, WW)
+    float invN, inv_nsegE, inv_WW;         // div_small() reciprocals (of max(., 1))
+};
+template <int KIND>
+__device__ __forceinline__ void step_desc_positions(int32_t* tl, int eb, int ne, const PPState& pp, const TJState& tj, int EPT, int N,
+                                                    int tid, int NT)
+{
+    if constexpr (KIND == IC3_ENV_PP) {
+        const int total = pp.Np + pp.nprey;
+        int32_t* psr = tl;
+        int32_t* psc = tl + EPT * total;
+        for (int i = tid; i < ne * total; i += NT) {
+            psr[i] = pp.loc_r[(size_t)eb * total + i];
+            psc[i] = pp.loc_c[(size_t)eb * total + i];
+        }
+    } else if constexpr (KIND == IC3_ENV_TJ) {
+        const int tjw = tj_tile_words(N, (2 * tj.v + 1) * (2 * tj.v + 1));
+        const float invN = 1.0f / (float)N;
+        for (int i = tid; i < ne * N; i += NT) {
+            const int el = div_small(i, invN);
+            tj_tile_load_car(tj_tile_at(tl + el * tjw, N), tj, eb + el, i - el * N);
+        }
+    }
+}
+template <int KIND>
+__device__ __forceinline__ void step_desc_tab(int32_t* tl, int ne, const PPState& pp, const TJState& tj, int EPT, const StepDescGeom& g,
+                                              uint32_t* rmask, int tid, int NT)
+{
+    if constexpr (KIND != 0) {
+        int2* pt = reinterpret_cast<int2*>(tl + ((2 * EPT * g.total + 3) & ~3));
+        for (int s = tid; s < ne * g.nsegE; s += NT) {
+            const int el = div_small(s, g.inv_nsegE), q = s - el * g.nsegE;
+            int2 d;
+            if constexpr (KIND == IC3_ENV_PP) {
+                d = pp_tab_entry(tl + el * g.total, tl + EPT * g.total + el * g.total, q, pp.Np, g.total, pp.dim, pp.v);
+                pt[s] = d;
+            } else {
+                const TJTile t = tj_tile_at(tl + el * g.tjw, g.N);
+                d = tj_tab_entry(t, tj, q);
+                t.tab[q] = d;
+            }
+            if (d.y != 0 && g.WW <= 32) {
+                const int ag = div_small(q, g.inv_WW);
+                atomicOr(&rmask[el * g.N + ag], 1u << (q - ag * g.WW));
+            }
+        }
+    }
+}
+
 // host helpers (pp_kernels.hip / tj_kernels.hip): device views of a handle's state
 PPState pp_state_of(const ic3_env* env);
 TJState tj_state_of(const ic3_env* env);

@@ -77,6 +77,19 @@ hipError_t ensure_dynamic_lds(const void* func, size_t bytes)
     if (e == hipSuccess) cur = bytes;
     return e;
 }
+
+int device_cus()
+{
+    static int cus[64] = { 0 };   // per device (a process may drive several GPUs)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cus[dev]) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus[dev] = prop.multiProcessorCount;
+    }
+    return cus[dev] ? cus[dev] : 256;
+}
+
 int fail(int code, const std::string& msg)
 {
     g_err = msg;

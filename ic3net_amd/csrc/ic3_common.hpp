@@ -118,6 +118,24 @@ int fail(int code, const std::string& msg);
 // hipFuncAttributeMaxDynamicSharedMemorySize of `func` raised to >= `bytes` on the CURRENT device.  The attribute is per
 // device; what has been set is remembered per (function, device), so the driver call happens once per pair, not per launch.
 hipError_t ensure_dynamic_lds(const void* func, size_t bytes);
+// CUs of the CURRENT device (the tile plans of the step launches and of the window backwards), cached per device; 256 where the
+// runtime does not say.
+int device_cus();
+
+// head_sizes[nheads] of an entry point -> OT = 1 + their sum (the log-probs' columns and the value's) and a[0..3] (0 behind the last
+// head), as every kernel with action heads takes them.  0, or -22 with `who` in front of the reason.
+inline int parse_heads(const int32_t* sizes, int nheads, const char* who, int& OT, int (&a)[4])
+{
+    if (nheads < 1 || nheads > 4) return fail(-22, std::string(who) + ": 1..4 action heads");
+    OT = 1;
+    for (int i = 0; i < 4; ++i) {
+        a[i] = i < nheads ? sizes[i] : 0;
+        if (i < nheads && a[i] < 1) return fail(-22, std::string(who) + ": empty action head");
+        OT += a[i];
+    }
+    if (OT > 16) return fail(-22, std::string(who) + ": more than 15 actions in total");
+    return 0;
+}
 
 // roctx ranges around the launches of the hot loop (the reference's unused utils.Timer, utils.py:86-98):
 // `IC3_ROCTX=1 rocprofv3 --marker-trace --kernel-trace ...` shows reset / step / observe / encode / policy_step /
@@ -166,6 +184,40 @@ __device__ __forceinline__ float fast_tanh(float x)
 {
     // (an explicit fma: which of mul + sub / fma the compiler picks must not depend on the code around the call)
     return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x)), 1.0f);
+}
+#endif
+
+// select_action (action_utils.py:32-36: torch.multinomial(exp(logp), 1) per row) as an inverse-CDF draw on the injected uniform
+// u = x24 / 2^24: the first action o with u < sum_{b <= o} exp(logp(b)) (fp32, left to right), the last action as fallback.  ONE
+// copy: the launch-chain equivalence tests rest on every kernel that draws doing exactly this.
+#if defined(__HIPCC__)
+template <class LogP>
+__device__ __forceinline__ int draw_action(uint32_t x24, int A, LogP logp)
+{
+    const float u = (float)x24 * (1.0f / 16777216.0f);
+    float cdf = 0.0f;
+    int act = A - 1;
+    for (int o = 0; o < A - 1; ++o) {
+        cdf += expf(logp(o));
+        if (u < cdf) {
+            act = o;
+            break;
+        }
+    }
+    return act;
+}
+// One action head of one row: log_softmax of its logits z[off, off + A) -> orow[off, off + A) (comm.py:239; hardware exp2 / log2,
+// ~1 ulp: |error| of a log-prob ~1e-7, bar 1e-5).  Returns the log-sum-exp: a kernel that also draws the head's action takes
+// z[off + o] - lse, the value just stored, as draw_action's log-prob.
+__device__ __forceinline__ float head_log_softmax(const float* z, float* orow, int off, int A)
+{
+    float mx = -INFINITY;
+    for (int o = 0; o < A; ++o) mx = fmaxf(mx, z[off + o]);
+    float sum = 0.0f;
+    for (int o = 0; o < A; ++o) sum += __builtin_amdgcn_exp2f(1.4426950408889634f * (z[off + o] - mx));
+    const float lse = mx + 0.6931471805599453f * __builtin_amdgcn_logf(sum);
+    for (int o = 0; o < A; ++o) orow[off + o] = z[off + o] - lse;
+    return lse;
 }
 #endif
 
@@ -231,7 +283,6 @@ int pp_encode_bwd(ic3_env* env, const int32_t* snap, const float* g, int ldg, in
 int tj_encode_bwd(ic3_env* env, const int32_t* snap, const float* g, int ldg, int H, float* dWt, float* dbias, float* work,
                   hipStream_t s, int mode = 0);
 // window form: stage 1 over T recorded states in one launch, and its expand stage
-int enc_bwd_cus();
 int64_t pp_encode_bwd_window_work(const ic3_env* env, int H);
 int64_t tj_encode_bwd_window_work(const ic3_env* env, int H);
 int pp_encode_bwd_window(ic3_env* env, const int32_t* snaps, long long snap_words, int T, const float* g, int ldg, long long g_step,

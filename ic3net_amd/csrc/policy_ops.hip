@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void policy_heads_kernel(const float* __restri
 // lstm_cell_kernel + policy_heads_kernel + sample_actions_env_kernel in one pass: the H/4 lanes that produce a row of
 // h' also hold it in registers, so the head / value dot products are a lane-local FMA block plus a log2(H/4)-step
 // shuffle reduce; lane 0 of the row finishes log_softmax (same arithmetic as policy_heads_kernel) and, when an env
-// handle is given, draws the actions of every head (same arithmetic and Philox counters as sample_actions_env_kernel).
+// handle is given, draws the actions of every head (draw_action, ic3_common.hpp: the draw of sample_actions_env_kernel).
 // Saves re-reading h (R*H*4 bytes) and three launches per step.  H/4 must be a power of two <= 64.
 // (group_sum<G>: env_device.hpp)
 template <int H4, int MAXO>
@@ -339,33 +339,17 @@ __global__ __launch_bounds__(256) void lstm_cell_heads_kernel(const float* __res
             continue;
         }
         const int A = sizes[hd];
-        float mx = -INFINITY;
-        for (int o = 0; o < A; ++o) mx = fmaxf(mx, z[off + o]);
-        float sum = 0.0f;                       // hardware exp2 / log2 (~1 ulp): |error| of a log-prob ~1e-7, bar 1e-5
-        for (int o = 0; o < A; ++o) sum += __builtin_amdgcn_exp2f(1.4426950408889634f * (z[off + o] - mx));
-        const float lse = mx + 0.6931471805599453f * __builtin_amdgcn_logf(sum);
-        for (int o = 0; o < A; ++o) orow[off + o] = z[off + o] - lse;
+        const float lse = head_log_softmax(z, orow, off, A);
         if (action) {
             const int e = grow / N, n = grow - e * N;
             const uint32_t x = philox_x24(seed, gid0 + (uint32_t)e, DOMAIN_SAMPLE, (uint32_t)episode[e], (uint32_t)tstep[e],
                                           (uint32_t)(hd * N + n));
-            const float u = (float)x * (1.0f / 16777216.0f);
-            float cdf = 0.0f;
-            int a = A - 1;
-            for (int o = 0; o < A - 1; ++o) {
-                cdf += expf(z[off + o] - lse);
-                if (u < cdf) {
-                    a = o;
-                    break;
-                }
-            }
-            action[(size_t)hd * R + grow] = a;
+            action[(size_t)hd * R + grow] = draw_action(x, A, [&](int o) { return z[off + o] - lse; });
         }
     }
 }
 
-// action_utils.py:32-36: torch.multinomial(exp(logp), 1) per row.  Inverse-CDF on the injected uniform:
-// first a with u < sum_{b<=a} exp(logp_b), last action as fallback (fp32, left-to-right).
+// action_utils.py:32-36: torch.multinomial(exp(logp), 1) per row (draw_action, ic3_common.hpp).
 __global__ __launch_bounds__(256) void sample_actions_kernel(const float* __restrict__ logp, int ld, int A, int head,
                                                              uint32_t seed, uint32_t gid0, uint32_t episode, uint32_t t,
                                                              int32_t* __restrict__ action,
@@ -375,17 +359,8 @@ __global__ __launch_bounds__(256) void sample_actions_kernel(const float* __rest
     if (row >= E * N) return;
     const int e = row / N, n = row - e * N;
     const uint32_t x = philox_x24(seed, gid0 + (uint32_t)e, DOMAIN_SAMPLE, episode, t, (uint32_t)(head * N + n));
-    const float u = (float)x * (1.0f / 16777216.0f);
     const float* lp = logp + (size_t)row * ld;
-    float cdf = 0.0f;
-    int a = A - 1;
-    for (int b = 0; b < A - 1; ++b) {
-        cdf += expf(lp[b]);
-        if (u < cdf) {
-            a = b;
-            break;
-        }
-    }
+    const int a = draw_action(x, A, [&](int b) { return lp[b]; });
     action[row] = a;
     if (chosen_logp) chosen_logp[row] = lp[a];
 }
@@ -404,17 +379,8 @@ __global__ __launch_bounds__(256) void sample_actions_env_kernel(const float* __
     const int e = row / N, n = row - e * N;
     const uint32_t x = philox_x24(seed, gid0 + (uint32_t)e, DOMAIN_SAMPLE, (uint32_t)episode[e], (uint32_t)tstep[e],
                                   (uint32_t)(head * N + n));
-    const float u = (float)x * (1.0f / 16777216.0f);
     const float* lp = logp + (size_t)row * ld;
-    float cdf = 0.0f;
-    int a = A - 1;
-    for (int b = 0; b < A - 1; ++b) {
-        cdf += expf(lp[b]);
-        if (u < cdf) {
-            a = b;
-            break;
-        }
-    }
+    const int a = draw_action(x, A, [&](int b) { return lp[b]; });
     action[row] = a;
     if (chosen_logp) chosen_logp[row] = lp[a];
 }
@@ -536,9 +502,8 @@ extern "C" int ic3_lstm_cell_heads(const float* gates, float* c, float* h_out, i
         return ic3::fail(-22, "ic3_lstm_cell_heads: bad arguments (1..4 heads, H and ldh multiples of 4)");
     const int H4 = H / 4;
     if (H4 > 64 || (H4 & (H4 - 1))) return ic3::fail(-38, "ic3_lstm_cell_heads: H/4 must be a power of two <= 64");
-    int sz[4] = { 0, 0, 0, 0 }, OT = 1;
-    for (int i = 0; i < nheads; ++i) { sz[i] = head_sizes[i]; OT += head_sizes[i]; }
-    if (OT > IC3_MAX_OT) return ic3::fail(-22, "ic3_lstm_cell_heads: more than 15 actions in total");
+    int sz[4], OT;
+    if (int rc = ic3::parse_heads(head_sizes, nheads, "ic3_lstm_cell_heads", OT, sz)) return rc;
     const int32_t *ep = nullptr, *ts = nullptr;
     uint32_t seed = 0, gid0 = 0;
     int N = 1;
@@ -577,9 +542,8 @@ extern "C" int ic3_policy_heads(const float* h, int ldh, const float* W, const f
 {
     if (!h || !W || !b || !head_sizes || !out || R <= 0 || H <= 0 || (H & 3) || (ldh & 3) || nheads < 1 || nheads > 4)
         return ic3::fail(-22, "ic3_policy_heads: bad arguments (1..4 heads, H % 4 == 0)");
-    int sz[4] = { 0, 0, 0, 0 }, OT = 1;
-    for (int i = 0; i < nheads; ++i) { sz[i] = head_sizes[i]; OT += head_sizes[i]; }
-    if (OT > IC3_MAX_OT) return ic3::fail(-22, "ic3_policy_heads: more than 15 actions in total");
+    int sz[4], OT;
+    if (int rc = ic3::parse_heads(head_sizes, nheads, "ic3_policy_heads", OT, sz)) return rc;
     const size_t lds = (size_t)OT * H * sizeof(float);
     hipLaunchKernelGGL(ic3::policy_heads_kernel, dim3((R + 31) / 32), dim3(256), lds, (hipStream_t)stream, h, ldh, W, b,
                        out, R, H / 4, OT, nheads, sz[0], sz[1], sz[2], sz[3]);

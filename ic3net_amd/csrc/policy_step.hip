@@ -27,11 +27,10 @@
 #include <cstdlib>
 #include <vector>
 
-#include <hip/hip_ext.h>
-
 #include "env_device.hpp"
 #include "ic3_common.hpp"
 #include "ps_common.hpp"
+#include "step_launch.hpp"
 
 namespace ic3 {
 
@@ -182,7 +181,6 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
     float* const shb = reinterpret_cast<float*>(sts + BM);       // [16] head / value biases
     float* const slb = shb + 16;                                 // [4H] b_ih + b_hh
     int32_t* const tile = reinterpret_cast<int32_t*>(slb + 4 * H);   // env descriptors of the tile's envs
-    constexpr int tz = 0;
     constexpr int KB = K / 8;
     constexpr int PER = H / 16;
 
@@ -225,44 +223,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
         const int tjw = tj_tile_words(N, WW);
         const float inv_WW = 1.0f / (float)max(WW, 1);
         const float invN = 1.0f / (float)N, inv_nsegE = 1.0f / (float)max(nsegE, 1);   // div_small(): no integer divisions
-        // env descriptors of `ne` envs starting at env `eb`, into the LDS block `tl` (two phases around a barrier):
-        //   PP: sr[EPT*total] | sc[EPT*total] | tab[EPT*N*WW] (int2);  TJ: EPT x TJTile
-        auto desc_positions = [&](int32_t* tl, int eb, int ne) __attribute__((always_inline)) {
-            if constexpr (KIND == IC3_ENV_PP) {
-                int32_t* psr = tl;
-                int32_t* psc = tl + a.EPT * total;
-                for (int i = tid; i < ne * total; i += NT) {
-                    psr[i] = a.pp.loc_r[(size_t)eb * total + i];
-                    psc[i] = a.pp.loc_c[(size_t)eb * total + i];
-                }
-            } else if constexpr (KIND == IC3_ENV_TJ) {
-                for (int i = tid; i < ne * N; i += NT) {
-                    const int el = div_small(i, invN);
-                    tj_tile_load_car(tj_tile_at(tl + el * tjw, N), a.tj, eb + el, i - el * N);
-                }
-            }
-        };
-        auto desc_tab = [&](int32_t* tl, int ne) __attribute__((always_inline)) {
-            if constexpr (KIND != 0) {
-                int2* pt = reinterpret_cast<int2*>(tl + ((2 * a.EPT * total + 3) & ~3));
-                for (int s = tid; s < ne * nsegE; s += NT) {
-                    const int el = div_small(s, inv_nsegE), q = s - el * nsegE;
-                    int2 d;
-                    if constexpr (KIND == IC3_ENV_PP) {
-                        d = pp_tab_entry(tl + el * total, tl + a.EPT * total + el * total, q, a.pp.Np, total, a.pp.dim, a.pp.v);
-                        pt[s] = d;
-                    } else {
-                        const TJTile t = tj_tile_at(tl + el * tjw, N);
-                        d = tj_tab_entry(t, a.tj, q);
-                        t.tab[q] = d;
-                    }
-                    if (d.y != 0 && WW <= 32) {          // rows of the encoder only visit the cells flagged here
-                        const int ag = div_small(q, inv_WW);
-                        atomicOr(&rmask[el * N + ag], 1u << (q - ag * WW));
-                    }
-                }
-            }
-        };
+        const StepDescGeom dg = { N, WW, total, nsegE, tjw, invN, inv_nsegE, inv_WW };
         // one workgroup per tile: the hardware dispatcher balances the tiles over the CUs (a resident set of workgroups
         // walking a strided tile list was measured slower: 350 vs 327 us, and needed tricks against hoisted loads)
         const TileGeom g = tile_geom<KIND>(a, blockIdx.x);
@@ -329,9 +290,9 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
             v_ep = a.episode[e0 + ecl];
             v_ts = a.tstep[e0 + ecl];
         }
-        const float v_hb = a.head_b[min(tid, a.OT - 1) + tz];
-        const float v_lb0 = a.l_bias[tid + tz], v_lb1 = a.l_bias[tid + NT + tz];   // 4H = 2 NT
-        desc_positions(tile, e0, nenv);                              // (its LDS writes wait for everything above too)
+        const float v_hb = a.head_b[min(tid, a.OT - 1)];
+        const float v_lb0 = a.l_bias[tid], v_lb1 = a.l_bias[tid + NT];   // 4H = 2 NT
+        step_desc_positions<KIND>(tile, e0, nenv, a.pp, a.tj, a.EPT, N, tid, NT);   // (its LDS writes wait for everything above too)
         if (tid < BM) {                                              // wave 0, all lanes
             // auto-reset: an env whose t == 0 is at the start of an episode (see above); `sact` carries the alive flags
             // to the per-env scale below (it is the draws' action buffer much later)
@@ -371,7 +332,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
 
         // ---- S1: window descriptors --------------------------------------------------------------------------------
         if constexpr (KIND != 0) {
-            desc_tab(tile, nenv);
+            step_desc_tab<KIND>(tile, nenv, a.pp, a.tj, a.EPT, dg, rmask, tid, NT);
             __syncthreads();
         }
         }   // first
@@ -393,9 +354,9 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                     v = *reinterpret_cast<const ps_f32x4*>(a.enc_in + (r0 + row) * H + 4 * c4);
                 } else if constexpr (KIND == IC3_ENV_PP) {
                     v = pp_encode_row_t(sr + el * total, sc + el * total, ptab + el * nsegE, aa, c4, H4, WW,
-                                        a.pp.dim * a.pp.dim + 4, a.pp.dim, encW, enc_bias_now + tz, encL, rmask[row]);
+                                        a.pp.dim * a.pp.dim + 4, a.pp.dim, encW, enc_bias_now, encL, rmask[row]);
                 } else {
-                    v = tj_encode_row_t(tj_tile_at(tile + el * tjw, N), a.tj, aa, c4, H4, encW, enc_bias_now + tz, encL,
+                    v = tj_encode_row_t(tj_tile_at(tile + el * tjw, N), a.tj, aa, c4, H4, encW, enc_bias_now, encL,
                                         rmask[row]);
                 }
             }
@@ -978,27 +939,13 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                     continue;
                 }
                 const int A = sizes[hd];
-                float mx = -INFINITY;
-                for (int o = 0; o < A; ++o) mx = fmaxf(mx, z[off + o]);
-                float sum = 0.0f;                       // hardware exp2 / log2 (~1 ulp): |error| of a log-prob ~1e-7, bar 1e-5
-                for (int o = 0; o < A; ++o) sum += __builtin_amdgcn_exp2f(1.4426950408889634f * (z[off + o] - mx));
-                const float lse = mx + 0.6931471805599453f * __builtin_amdgcn_logf(sum);
-                for (int o = 0; o < A; ++o) orow[off + o] = z[off + o] - lse;
+                const float lse = head_log_softmax(z, orow, off, A);
                 if (KIND == 0) continue;                // forward only: the caller draws (ic3_sample_actions)
                 const int el = div_small(tr, invN), n = tr - el * N;
                 const int e = e0 + el;
                 const uint32_t x = philox_x24(a.seed, a.gid0 + (uint32_t)e, DOMAIN_SAMPLE, (uint32_t)sep[el],
                                               (uint32_t)sts[el], (uint32_t)(hd * N + n));
-                const float u = (float)x * (1.0f / 16777216.0f);
-                float cdf = 0.0f;
-                int act = A - 1;
-                for (int o = 0; o < A - 1; ++o) {
-                    cdf += expf(z[off + o] - lse);
-                    if (u < cdf) {
-                        act = o;
-                        break;
-                    }
-                }
+                const int act = draw_action(x, A, [&](int o) { return z[off + o] - lse; });
                 a.action[(size_t)hd * R + grow] = act;
                 if (hd == 0) sact[tr] = act;
             }
@@ -1006,6 +953,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
         __syncthreads();
 
         // ---- S12: env.step for the tile's envs with the env-action head (env_wrappers.py:76-77) ------------------------
+        // (the same loop as commnet_forward_kernel's; env_device.hpp says why the two keep their copies)
         if constexpr (KIND != 0) {
             const int lgG = __builtin_ctz(a.G);
             for (int base = 0; base < a.EPT * a.G; base += NT) {
@@ -1095,19 +1043,6 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
 }
 
 
-static int device_cus()
-{
-    static int cus[64] = { 0 };   // per device (a process may drive several GPUs)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-        cus[dev] = prop.multiProcessorCount;
-    }
-    return cus[dev];
-}
-
 // Tile plan (a.E, a.N, a.EPT set).  Two workgroups share a CU and all tiles cost the same, so a launch whose tile count
 // is not a multiple of the slot count ends with a round in which some CUs still hold two tiles while others hold one
 // or none (PP-hard: 1366 tiles = 2.67 rounds of 512 slots cost 3).  Plan B: as many FULL tiles (EPT envs, two 32-row
@@ -1157,7 +1092,8 @@ static int fill_policy(StepArgs& a, const ic3_policy* p, const char* who)
     if (int rc = check_policy_struct(p, who)) return rc;
     if (!p->c_wp || !p->lstm_wp || !p->lstm_bias || !p->head_w || !p->head_b)
         return fail(-22, std::string(who) + ": incomplete ic3_policy");
-    if (p->nheads < 1 || p->nheads > 4) return fail(-22, std::string(who) + ": 1..4 action heads");
+    int sz[4];
+    if (int rc = parse_heads(p->head_sizes, p->nheads, who, a.OT, sz)) return rc;
     a.Wt = reinterpret_cast<const ps_f32x4*>(p->enc_wt);
     a.enc_bias = reinterpret_cast<const ps_f32x4*>(p->enc_bias);
     a.loc_table = reinterpret_cast<const ps_f32x4*>(p->loc_table);
@@ -1167,14 +1103,6 @@ static int fill_policy(StepArgs& a, const ic3_policy* p, const char* who)
     a.head_w = p->head_w;
     a.head_b = p->head_b;
     a.nheads = p->nheads;
-    int sz[4] = { 0, 0, 0, 0 };
-    a.OT = 1;
-    for (int i = 0; i < p->nheads; ++i) {
-        sz[i] = p->head_sizes[i];
-        if (sz[i] < 1) return fail(-22, std::string(who) + ": empty action head");
-        a.OT += sz[i];
-    }
-    if (a.OT > 16) return fail(-22, std::string(who) + ": more than 15 actions in total");
     a.a0 = sz[0];
     a.a1 = sz[1];
     a.a2 = sz[2];
@@ -1233,7 +1161,7 @@ static double time_tile_mix(const ic3_policy* p, int N, int n_full, int n_half, 
 
 static void calibrate_tile_costs(const ic3_policy* p, int N, int cus, hipStream_t s, TileCosts& tc)
 {
-    const int H = p->H, EPT = 64 / N, EPTh = 32 / N;
+    const int H = p->H, EPT = 64 / N;
     const size_t Rmax = (size_t)2 * cus * EPT * N;
     float* scratch = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1257,7 +1185,6 @@ static void calibrate_tile_costs(const ic3_policy* p, int N, int cus, hipStream_
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(scratch);
-    (void)EPTh;
 }
 
 static const TileCosts& tile_costs(const ic3_policy* p, int N, int H, hipStream_t s)
@@ -1307,17 +1234,17 @@ static int plan_tiles(StepArgs& a, int H, const ic3_policy* p, hipStream_t s)
 template <int H, int KIND, int SPLIT, int MP>
 static int launch_step(const StepArgs& a, int tiles, size_t lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
-    IC3_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(&policy_step_kernel<H, KIND, SPLIT, MP>), lds));   // per (kernel, device)
     // one workgroup per tile, dispatched in tile order (full tiles first, see plan_tiles): the hardware dispatcher
     // balances them over the CUs (a fixed resident set walking a strided tile list was measured slower)
-    const int grid = tiles;
-    if (ev0 || ev1) {   // timed launch: the dispatch itself stamps the events (no separate record packets around it)
-        hipExtLaunchKernelGGL((policy_step_kernel<H, KIND, SPLIT, MP>), dim3(grid), dim3(2 * H), lds, s, ev0, ev1, 0, a);
-    } else {
-        hipLaunchKernelGGL((policy_step_kernel<H, KIND, SPLIT, MP>), dim3(grid), dim3(2 * H), lds, s, a);
-    }
-    IC3_HIP(hipGetLastError());
-    return 0;
+    const dim3 grid(tiles), block(2 * H);
+    if (ev0 || ev1) return launch_kernel_timed(policy_step_kernel<H, KIND, SPLIT, MP>, grid, block, lds, s, ev0, ev1, a);
+    return launch_kernel(policy_step_kernel<H, KIND, SPLIT, MP>, grid, block, lds, s, a);
+}
+// the env instantiation of the handle's kind
+template <int H, int SPLIT, int MP = 0>
+static int launch_step_env(bool pp, const StepArgs& a, int tiles, size_t lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+{
+    return pp ? launch_step<H, IC3_ENV_PP, SPLIT, MP>(a, tiles, lds, s, ev0, ev1) : launch_step<H, IC3_ENV_TJ, SPLIT, MP>(a, tiles, lds, s, ev0, ev1);
 }
 
 }  // namespace ic3
@@ -1325,31 +1252,19 @@ static int launch_step(const StepArgs& a, int tiles, size_t lds, hipStream_t s, 
 using namespace ic3;
 
 
-// LDS bytes of one workgroup (0 = unsupported shape); *tile_words_out = int32 words of one env-descriptor block
-static int policy_step_lds(const ic3_env* env, int H, int with_obs, int* tile_words_out)
+// LDS bytes of one workgroup (0 = unsupported shape)
+static int policy_step_lds(const ic3_env* env, int H)
 {
     if (!env) return 0;
     if (H != 64 && H != 128 && H != 256) return 0;
     const int N = env->dims.N;
     if (N < 1 || N > 64) return 0;
-    const int EPT = 64 / N;
-    const int WW = env->dims.window * env->dims.window;
-    size_t tile_words;
-    if (env->kind == IC3_ENV_PP) {
-        const int total = env->pp.N + env->pp.nprey;
-        tile_words = (size_t)((2 * EPT * total + 3) & ~3) + (size_t)2 * EPT * N * WW;
-    } else {
-        tile_words = (size_t)EPT * (((7 * N + 3) & ~3) + 2 * N * WW);
-    }
-    tile_words = (tile_words + 3) & ~(size_t)3;
-    if (tile_words_out) *tile_words_out = (int)tile_words;
-    (void)with_obs;
-    const size_t lds = ((size_t)64 * (2 * H + 4) + ps_lds_small(H) + tile_words) * sizeof(float);
+    const size_t lds = ((size_t)64 * (2 * H + 4) + ps_lds_small(H) + step_tile_words(env)) * sizeof(float);
     const size_t limit = (H <= 128) ? 80 * 1024 : 160 * 1024;   // two workgroups per CU up to H = 128
     return lds <= limit ? (int)lds : 0;
 }
 
-extern "C" int ic3_policy_step_supported(const ic3_env* env, int H) { return policy_step_lds(env, H, 0, nullptr); }
+extern "C" int ic3_policy_step_supported(const ic3_env* env, int H) { return policy_step_lds(env, H); }
 
 
 extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, int N, float* h, float* c,
@@ -1379,14 +1294,11 @@ extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, 
     hipStream_t s = (hipStream_t)stream;
     const int tiles = plan_tiles(a, H, p, s);
     const size_t lds = ((size_t)64 * (2 * H + 4) + ps_lds_small(H)) * sizeof(float);
-    if (a.l_wp3) {   // the gate product as exact bf16 split products (ic3_policy.gate_split), as in ic3_policy_step
-        if (H == 128) return launch_step<128, 0, 1>(a, tiles, lds, s);
-        if (H == 64) return launch_step<64, 0, 1>(a, tiles, lds, s);
-        return launch_step<256, 0, 1>(a, tiles, lds, s);
-    }
-    if (H == 128) return launch_step<128, 0>(a, tiles, lds, s);
-    if (H == 64) return launch_step<64, 0>(a, tiles, lds, s);
-    return launch_step<256, 0>(a, tiles, lds, s);
+    return with_hid(H, [&](auto hid) {
+        constexpr int HH = decltype(hid)::value;
+        // the gate product as exact bf16 split products (ic3_policy.gate_split), as in ic3_policy_step
+        return a.l_wp3 ? launch_step<HH, 0, 1>(a, tiles, lds, s) : launch_step<HH, 0>(a, tiles, lds, s);
+    });
 }
 
 extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, float* c, const int32_t* alive_in,
@@ -1408,12 +1320,7 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
     if (env->resets == 0) return fail(-22, "ic3_policy_step: reset() has not been called");
     if (!p->enc_wt || !p->enc_bias) return fail(-22, "ic3_policy_step: incomplete ic3_policy (encoder)");
     const int H = p->H;
-    // next_state rows are stored from inside the kernel when their descriptors fit in LDS next to the tile's own (otherwise
-    // ic3_env_observe runs as a launch of its own in front of the kernel: same rows)
-    int tile_words = 0;
-    int lds = obs ? policy_step_lds(env, H, 1, &tile_words) : 0;
-    const bool fused_obs = lds != 0;
-    if (!lds) lds = policy_step_lds(env, H, 0, &tile_words);
+    const int lds = policy_step_lds(env, H);
     if (!lds)
         return fail(-38, "ic3_policy_step: needs hid_size 64/128/256, <= 64 agents per env and an env tile that fits "
                          "in LDS (use ic3_env_encode + ic3_comm_masked_mean + GEMMs + ic3_lstm_cell_heads + ic3_env_step)");
@@ -1436,26 +1343,12 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
     a.comm_in = comm_in;
     a.out = out;
     a.action = action;
-    a.E = env->dims.E;
-    a.N = env->dims.N;
-    a.EPT = 64 / a.N;
-    a.episode = env->f("episode");
-    a.tstep = env->f("t");
-    a.so = StepOut{ reward, done, alive, is_completed, env->d_err };
+    hipEvent_t ev0, ev1;                                         // one-shot (ic3_env_set_step_events): the step's LAST launch
+    fill_env_args(a, env, reward, done, alive, is_completed, !inner, ev0, ev1);
     const bool pp = env->kind == IC3_ENV_PP;
-    if (pp) {
-        a.pp = pp_state_of(env);
-        a.G = group_lanes(a.N);
-        a.seed = env->pp.seed;
-        a.gid0 = env->pp.env_id_offset;
-    } else {
-        a.tj = tj_state_of(env);
-        a.G = tj_group(a.N);
-        a.seed = env->tj.seed;
-        a.gid0 = env->tj.env_id_offset;
-    }
     const int tiles = plan_tiles(a, H, p, (hipStream_t)stream);
     // incremental obs rows (opt-in): the buffer must be the one the previous call painted, untouched since
+    const bool fused_obs = obs != nullptr;                       // next_state rows are stored from inside the kernel
     const bool incr = fused_obs && env->obs_rec != nullptr;
     const bool incr_valid = incr && env->painted_valid && env->painted_obs == obs;   // (no zero fill in the launch)
     a.obs_rec = incr ? env->obs_rec : nullptr;
@@ -1464,10 +1357,7 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
         env->painted_obs = obs;
         env->painted_valid = true;
     }
-    a.tile_words = tile_words;
-    a.obs = fused_obs ? obs : nullptr;
-    a.obs_dim = env->dims.obs_dim;
-    a.auto_reset = env->auto_max_steps > 0;
+    a.obs = obs;
     {   // pacing of the obs zero fill (speed only: a slot past a wave's last chunk is dropped by the hardware).
         // A wave of a full tile owns `per_wave` 1 KiB chunks.  Stores issued back to back are exposed at the HBM write
         // rate; stores between MFMAs ride in their shadows until the rate all CUs ask for exceeds what HBM takes.
@@ -1516,38 +1406,16 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
         a.zrest = (fused_obs && !incr_valid) ? (int)(left > 0 ? left + 1 : 0) : 0;
     }
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (obs && !fused_obs) {   // same contents, as a launch of its own in front (the step below changes the state)
-        rc = ic3_env_observe(env, obs, stream);
-        if (rc) return rc;
-    }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (!inner) {                                                // one-shot (ic3_env_set_step_events): the step's LAST launch
-        ev0 = (hipEvent_t)env->ev_start;
-        ev1 = (hipEvent_t)env->ev_stop;
-        env->ev_start = env->ev_stop = nullptr;
-    }
     if (a.npass > 1) {   // comm_passes > 1 as a loop inside the launch (MP instantiations: split gate product, hid 64 / 128)
         if (!a.l_wp3 || (H != 128 && H != 64))
             return fail(-38, "ic3_policy_step: npasses >= 2 needs gate_split and hid_size 64 / 128 (use one call per pass)");
-        if (H == 128)
-            return pp ? launch_step<128, IC3_ENV_PP, 1, 1>(a, tiles, lds, s, ev0, ev1) : launch_step<128, IC3_ENV_TJ, 1, 1>(a, tiles, lds, s, ev0, ev1);
-        return pp ? launch_step<64, IC3_ENV_PP, 1, 1>(a, tiles, lds, s, ev0, ev1) : launch_step<64, IC3_ENV_TJ, 1, 1>(a, tiles, lds, s, ev0, ev1);
+        return H == 128 ? launch_step_env<128, 1, 1>(pp, a, tiles, lds, s, ev0, ev1) : launch_step_env<64, 1, 1>(pp, a, tiles, lds, s, ev0, ev1);
     }
-    if (a.l_wp3) {   // gate_split: the gate product on the bf16 matrix cores with exact split products
-        if (H == 128)
-            rc = pp ? launch_step<128, IC3_ENV_PP, 1>(a, tiles, lds, s, ev0, ev1) : launch_step<128, IC3_ENV_TJ, 1>(a, tiles, lds, s, ev0, ev1);
-        else if (H == 64)
-            rc = pp ? launch_step<64, IC3_ENV_PP, 1>(a, tiles, lds, s, ev0, ev1) : launch_step<64, IC3_ENV_TJ, 1>(a, tiles, lds, s, ev0, ev1);
-        else
-            rc = pp ? launch_step<256, IC3_ENV_PP, 1>(a, tiles, lds, s, ev0, ev1) : launch_step<256, IC3_ENV_TJ, 1>(a, tiles, lds, s, ev0, ev1);
-    } else if (H == 128)
-        rc = pp ? launch_step<128, IC3_ENV_PP>(a, tiles, lds, s, ev0, ev1) : launch_step<128, IC3_ENV_TJ>(a, tiles, lds, s, ev0, ev1);
-    else if (H == 64)
-        rc = pp ? launch_step<64, IC3_ENV_PP>(a, tiles, lds, s, ev0, ev1) : launch_step<64, IC3_ENV_TJ>(a, tiles, lds, s, ev0, ev1);
-    else
-        rc = pp ? launch_step<256, IC3_ENV_PP>(a, tiles, lds, s, ev0, ev1) : launch_step<256, IC3_ENV_TJ>(a, tiles, lds, s, ev0, ev1);
-    return rc;
+    return with_hid(H, [&](auto hid) {
+        constexpr int HH = decltype(hid)::value;
+        // gate_split: the gate product on the bf16 matrix cores with exact split products
+        return a.l_wp3 ? launch_step_env<HH, 1>(pp, a, tiles, lds, s, ev0, ev1) : launch_step_env<HH, 0>(pp, a, tiles, lds, s, ev0, ev1);
+    });
 }
 
 

@@ -420,22 +420,11 @@ int pp_encode_bwd(ic3_env* env, const int32_t* snap, const float* g, int ldg, in
     return 0;
 }
 
-int enc_bwd_cus()
-{
-    static int cus[64] = {};      // per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return cus[dev];
-}
 static EncWinPlan pp_win_plan(const ic3_env* env, int H)
 {
     const ic3_pp_cfg& c = env->pp;
     const int W = 2 * c.vision + 1;
-    return enc_win_plan((long long)c.E * env->dims.N, env->dims.N, c.N + c.nprey, H, c.dim * c.dim, 2 * W * W, enc_bwd_cus());
+    return enc_win_plan((long long)c.E * env->dims.N, env->dims.N, c.N + c.nprey, H, c.dim * c.dim, 2 * W * W, device_cus());
 }
 int64_t pp_encode_bwd_window_work(const ic3_env* env, int H)
 {

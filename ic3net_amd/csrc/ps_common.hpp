@@ -1,6 +1,8 @@
-// ps_common.hpp — what policy_step.hip (the one-launch rollout step) and policy_pack.hip (its weight packing and the
-// gate-product probe) share: vector types, the compiler-visible buffer loads, the fp32 matrix instruction, and the EXACT split
-// of an fp32 value into three bf16 terms (ic3_policy.gate_split).
+// ps_common.hpp — what policy_step.hip (the one-launch rollout step), policy_pack.hip (its weight packing and the
+// gate-product probe), commnet_fwd.hip (the CommNet step's split products) and bptt_kernels.hip (the window backwards)
+// share on the device: vector types, the compiler-visible buffer loads, the fp32 matrix instruction, and the EXACT split
+// of an fp32 value into three bf16 terms (ic3_policy.gate_split).  The host-side helpers of the
+// step launches are in step_launch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

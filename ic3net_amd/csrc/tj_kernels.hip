@@ -583,7 +583,7 @@ static EncWinPlan tj_win_plan(const ic3_env* env, int H)
 {
     const ic3_dims& d = env->dims;
     const int hdr = env->tj.vocab_type ? 4 : 2;
-    return enc_win_plan((long long)env->tj.E * env->tj.N, env->tj.N, env->tj.N, H, d.grid_h * d.grid_w, hdr + d.window * d.window, enc_bwd_cus());
+    return enc_win_plan((long long)env->tj.E * env->tj.N, env->tj.N, env->tj.N, H, d.grid_h * d.grid_w, hdr + d.window * d.window, device_cus());
 }
 int64_t tj_encode_bwd_window_work(const ic3_env* env, int H)
 {

@@ -978,6 +978,88 @@ def test_step_events_are_stamped_by_the_launch():
     env.close()
 
 
+def test_bad_action_head_sizes_are_refused_by_every_entry_point():
+    """Every entry point with action heads reads head_sizes[nheads] through one parser: no heads or five of them, an empty head
+    and sizes that sum to 16 (17 output columns with the value's) come back as -22 with the entry point's name in
+    ic3_last_error() and nothing written; the valid [5, 2] call right behind runs.  pp_easy's shape."""
+    lib = host_lib()
+    w = WORKLOADS['pp_easy']
+    E, N, H = 2, w['N'], w['H']
+    R = E * N
+    env = make_env(w, E, 3, 40)
+    env.reset()
+    P = make_params(env.obs_dim, H, [5, 2], seed=4)
+    P['f_modules.0.weight'], P['f_modules.0.bias'] = P['C_modules.0.weight'] * 0.5, P['C_modules.0.bias'] * 0.5
+    pol = HostPolicy(env, P, H, [5, 2])
+    cw = commnet_weights(lib, P, H, [5, 2], 1)
+    pad = lambda a: np.ascontiguousarray(np.concatenate([a, np.zeros((17 - len(a),) + a.shape[1:], np.float32)]))   # room for 17 columns
+    pol.w_heads, pol.b_heads = pad(pol.w_heads), pad(pol.b_heads)
+    pol.struct.head_w, pol.struct.head_b = pol.w_heads.ctypes.data, pol.b_heads.ctypes.data
+    head_w, head_b = pol.w_heads, pol.b_heads
+    rng = np.random.default_rng(9)
+    enc = (rng.standard_normal((R, H)) * 0.3).astype(np.float32)
+    gates = (rng.standard_normal((R, 4 * H)) * 0.5).astype(np.float32)
+    nan = lambda *s: np.full(s, np.nan, np.float32)
+    neg = lambda *s: np.full(s, -1, np.int32)
+
+    def policy_struct(sizes, nheads):
+        pol.struct.nheads = nheads
+        for i in range(4):
+            pol.struct.head_sizes[i] = int(sizes[i]) if i < len(sizes) else 0
+        return C.byref(pol.struct)
+
+    def policy_step(sizes, nheads, hc):
+        o = [hc(R, H), hc(R, H), nan(R, 17), neg(4, R), env._obs_buf(), nan(E, N), neg(E), neg(E, N), neg(E, N)]
+        return lib.ic3_policy_step(env._h, policy_struct(sizes, nheads), p(o[0]), p(o[1]), None, None, *[p(x) for x in o[2:]], None), o
+
+    def policy_forward(sizes, nheads, hc):
+        o = [hc(R, H), hc(R, H), nan(R, 17)]
+        return lib.ic3_policy_forward(policy_struct(sizes, nheads), p(enc), E, N, p(o[0]), p(o[1]), None, None, p(o[2]), None), o
+
+    def commnet_forward(sizes, nheads, hc):
+        o = [nan(R, 17), nan(R, H)]
+        return lib.ic3_commnet_forward(p(enc), E, N, H, 1, p(cw['wp']), None, p(cw['bias']), p(head_w), p(head_b), p(sizes), nheads, 1, 0,
+                                       None, None, p(o[0]), p(o[1]), None), o
+
+    def commnet_step(sizes, nheads, hc):
+        o = [nan(R, 17), neg(4, R), env._obs_buf(), nan(E, N), neg(E), neg(E, N), neg(E, N)]
+        return lib.ic3_commnet_step(env._h, p(cw['wt']), p(cw['enc_bias']), None, H, 1, p(cw['wp']), None, p(cw['bias']), p(head_w),
+                                    p(head_b), p(sizes), nheads, 1, 0, None, None, None, None, *[p(x) for x in o], None), o
+
+    def lstm_cell_heads(sizes, nheads, hc):
+        o = [hc(R, H), nan(R, H), nan(R, 17), neg(4, R)]
+        return lib.ic3_lstm_cell_heads(p(gates), p(o[0]), p(o[1]), H, R, H, p(head_w), p(head_b), p(sizes), nheads, p(o[2]), env._h,
+                                       p(o[3]), None), o
+
+    def policy_heads(sizes, nheads, hc):
+        o = [nan(R, 17)]
+        return lib.ic3_policy_heads(p(enc), H, p(head_w), p(head_b), p(sizes), nheads, p(o[0]), R, H, None), o
+
+    bad = [([1, 1, 1, 1, 1], 0), ([1, 1, 1, 1, 1], 5), ([5, 0], 2), ([0], 1), ([8, 8], 2), ([4, 4, 4, 4], 4)]
+    zeros = lambda *s: np.zeros(s, np.float32)
+    for call in (policy_step, policy_forward, commnet_forward, commnet_step, lstm_cell_heads, policy_heads):
+        name = "ic3_" + call.__name__
+        for sizes, nheads in bad:
+            rc, outs = call(np.array(sizes, np.int32), nheads, nan)
+            assert rc == -22, (name, sizes, nheads, rc)
+            msg = lib.ic3_last_error().decode()
+            assert msg.startswith(name + ":"), (name, sizes, nheads, msg)
+            for o in outs:
+                assert (np.isnan(o) if o.dtype == np.float32 else o == -1).all(), (name, sizes, nheads)
+        rc, outs = call(np.array([5, 10], np.int32), 2, zeros)          # 15 actions, 16 columns: the most that is taken
+        assert rc == 0, (name, rc, lib.ic3_last_error().decode())
+        out = [o for o in outs if o.shape == (R, 17)][0].reshape(-1)[:R * 16].reshape(R, 16)
+        assert np.isfinite(out).all(), name
+        np.testing.assert_allclose(np.exp(out[:, 5:15]).sum(1), 1.0, atol=1e-5)
+        rc, outs = call(np.array([5, 2], np.int32), 2, zeros)
+        assert rc == 0, (name, rc, lib.ic3_last_error().decode())
+        out = [o for o in outs if o.shape == (R, 17)][0].reshape(-1)[:R * 8].reshape(R, 8)   # the call's own [R][8] layout
+        assert np.isfinite(out).all(), name
+        np.testing.assert_allclose(np.exp(out[:, :5]).sum(1), 1.0, atol=1e-5)
+        np.testing.assert_allclose(np.exp(out[:, 5:7]).sum(1), 1.0, atol=1e-5)
+    env.close()
+
+
 def test_results_do_not_depend_on_the_lane_schedule():
     """The stand-in runtime schedules the lanes of a workgroup round-robin from lane 0 up; IC3_HOST_SCHED=reverse walks them
     from the top down, =shuffle in a new pseudo-random order every round.  Device code whose result depends on which lane runs first between two cross-lane operations — a
