@@ -98,6 +98,19 @@ class MlpBptt(C.Structure):
                 ("a2_grad", C.c_void_p), ("wgrad_scratch", C.c_void_p)]
 
 
+class CommnetBptt(C.Structure):
+    """ic3_commnet_bptt (include/ic3_rollout.h): one window of the non-recurrent CommNet module's backward."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "passes", "mode_avg", "comm_zero",
+                                                                        "enc_first", "enc_window", "max_chunk_steps")] + \
+               [("dhead", C.c_void_p), ("snaps", C.c_void_p), ("snap_words", C.c_int64), ("alive", C.c_void_p), ("gate", C.c_void_p),
+                ("enc_wt", C.c_void_p), ("enc_bias", C.c_void_p), ("loc_table", C.c_void_p), ("wp", C.c_void_p), ("wp3", C.c_void_p),
+                ("bias", C.c_void_p), ("w_heads", C.c_void_p), ("f_weight", C.POINTER(C.c_void_p)), ("c_weight", C.POINTER(C.c_void_p)),
+                ("f_grad", C.POINTER(C.c_void_p)), ("c_grad", C.POINTER(C.c_void_p)), ("bias_grad", C.POINTER(C.c_void_p)),
+                ("heads_w_grad", C.c_void_p), ("heads_b_grad", C.c_void_p), ("h_pass", C.c_void_p), ("dxh", C.c_void_p),
+                ("dz", C.c_void_p), ("dx", C.c_void_p), ("de", C.c_void_p), ("dh", C.c_void_p), ("scratch", C.c_void_p),
+                ("enc_work", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "ic3_version": (C.c_int, []),
@@ -192,6 +205,15 @@ EXPORTS = {
     "ic3_commnet_pack_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ic3_commnet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 +
                             [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "ic3_commnet_forward_record": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 +
+                                   [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "ic3_commnet_backward_supported": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ic3_commnet_backward_chunk_steps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "ic3_commnet_backward_scratch_floats": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "ic3_commnet_pass_backward_partials": (C.c_int, [C.c_longlong, C.c_int]),
+    "ic3_commnet_pass_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int,
+                                                                                             C.c_longlong, C.c_int, C.c_void_p]),
+    "ic3_commnet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ic3_commnet_step_supported": (C.c_int, [C.c_void_p, C.c_int]),
     "ic3_commnet_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int] +
                          [C.c_void_p] * 12),

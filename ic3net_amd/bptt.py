@@ -775,7 +775,11 @@ def _backward_episode_commnet(args, net, raw, rec, d_out, acc):
     mean, library GEMMs for the H x H layers), then
         dz_i = dh_{i+1} (1 - h_{i+1}^2);   dx += dz_i;   dF_i += dz_i^T h_i;   dC_i += dz_i^T comm_i;
         dh_i = dz_i F_i + mix(dz_i C_i)            (the mixing matrix of the communication block is symmetric)
-    and finally d enc = (dx + dh_0)(1 - x^2) through ic3_env_encode_backward on the snapshot."""
+    and finally d enc = (dx + dh_0)(1 - x^2) through ic3_env_encode_backward on the snapshot.  A record that qualifies
+    (_commnet_window_ok) goes to _backward_window_commnet — the same arithmetic as window-wide launches — instead of the loop below,
+    as _backward_episode_baseline hands its own over to _backward_window_mlp."""
+    if _commnet_window_ok(args, net, raw, rec, d_out):
+        return _backward_window_commnet(args, net, raw, rec, d_out, acc)
     cn = net._commnet_cache()
     P = net.comm_passes
     T, R, H = rec.n, rec.rows, net.hid_size
@@ -842,6 +846,68 @@ def _backward_episode_commnet(args, net, raw, rec, d_out, acc):
         fgrad[i].finish()
         if cgrad[i] is not None:
             cgrad[i].finish()
+
+
+COMMNET_WINDOW_SIZES = (64, 128, 256)     # ic3_commnet_backward
+
+
+def _commnet_window_ok(args, net, raw, rec, d_out):
+    """The non-recurrent CommNet module (`supported` has tied it to its own env) at hid_size 64 / 128 / 256 — a zero-padded twin at
+    the twin's size —, at most 16 output columns, the native loop (args.bptt_native_loop) and args.commnet_window_backward on, the
+    library's answer for this env and the room for what ops.commnet_backward allocates: with Q = T x R rows (a chunk's, when the
+    library splits the window) the enc / h_pass ring of (P + 1) Q H floats, dxh Q 2H, dz, dx, de and dh Q H each — (P + 7) Q H
+    floats — plus the partials' scratch (ops.commnet_backward_ring_floats): _backward_window_commnet."""
+    H, T = net.hid_size, rec.n
+    if rec.recurrent or H not in COMMNET_WINDOW_SIZES or T < 1 or d_out.shape[-1] > 16 or not d_out.is_cuda:
+        return False
+    if not bool(getattr(args, 'bptt_native_loop', True)) or not bool(getattr(args, 'commnet_window_backward', True)):
+        return False
+    N = net.nagents
+    if not hasattr(raw, '_h') or not ops.commnet_backward_supported(raw, H, N):
+        return False
+    chunk = int(getattr(args, 'commnet_window_chunk_steps', 0))
+    return _ring_fits(rec.device, 4 * ops.commnet_backward_ring_floats(raw, T, rec.rows // N, N, H, net.comm_passes, chunk))
+
+
+def _backward_window_commnet(args, net, raw, rec, d_out, acc):
+    """_backward_episode_commnet for a whole window through ic3_commnet_backward (csrc/bptt_kernels.hip).  No state crosses a step,
+    so the window is T x R independent rows in T x E independent envs: enc of every snapshot into a ring (T encoder launches), the
+    forward again over all T x E envs in one launch with h_0 .. h_P kept, then per pass, last to first, three window-wide launches
+    — dz_i = dh_{i+1} (1 - h_{i+1}^2) with dz_i F_i beside it, the communication backward (dh_i = dz_i F_i + mix(dz_i) C_i and
+    dC_i = mix(dz_i)^T h_i: the mixing matrix is symmetric), dF_i = dz_i^T h_i — and fixed-order sums of the partials; de = (sum_i
+    dz_i + dh_0)(1 - h_0^2), the sparse encoder's first stage over the de ring, the heads' gradient on the recomputed h_P.  All on
+    the current stream, inside the one host call (the heads' pass reads a ring that exists only there: no second stream, nothing to
+    join).  Collection mode needs only the masks of the envs that start an episode (cuts.masks_window); the record is read, never
+    written.  args.commnet_window_chunk_steps > 0 bounds the steps per chunk (tests)."""
+    cn = net._commnet_cache()
+    T, R, H, N = rec.n, rec.rows, net.hid_size, net.nagents
+    E = R // N
+    dev = rec.device
+    mask_zero = bool(args.comm_mask_zero)
+    cuts = _Cuts(args, rec, T, E, N, dev)
+    alive, gate = cuts.masks_window(rec.alive[:T], rec.gate[:T])
+    if all(m is None for m in rec.gate[:T]):                      # no gate head: an env that starts an episode talks, as in the
+        gate = [None] * T                                         # step launch and in the loop (cuts.masks without fill_gate)
+
+    def stacked(ms):                                           # T entries (E, N) or None -> (T, E, N), None: everyone
+        if all(m is None for m in ms):
+            return None
+        ones = next(m for m in ms if m is not None).new_ones((E, N))
+        return torch.stack([m if m is not None else ones for m in ms]).contiguous()
+    enc_window = _enc_window(args, raw, H)
+    ops.commnet_backward(raw, T, E, N, H, _dhead_rows(d_out, T), rec.snaps, stacked(alive), stacked(gate), cn['wt'], cn['enc_bias'],
+                         cn['wp'], cn['bias'], cn['w_heads'], [m.weight.detach() for m in net.f_modules],
+                         [m.weight.detach() for m in net.C_modules], acc['f_w'], acc['c_w_p'], acc['cf_b'],
+                         heads_w_grad=acc['w_heads'], heads_b_grad=acc['b_heads'], wp3=cn.get('wp3'), loc_table=cn['loc_table'],
+                         mode_avg=getattr(args, 'comm_mode', 'avg') == 'avg', comm_zero=mask_zero, enc_first=True,
+                         enc_window=enc_window, max_chunk_steps=int(getattr(args, 'commnet_window_chunk_steps', 0)),
+                         work=acc.setdefault('_work', {}))
+    # (the ordered finish where the env has the window form: the encoder's gradient identical run to run, like the rest of the path)
+    dwt, db = raw.encode_backward_window_finish_ordered(H, want_bias=True) if enc_window \
+        else raw.encode_backward_finish(H, want_bias=True)
+    acc['wt'].add_(dwt)
+    acc['enc_bias'].add_(db)
+    net.commnet_window_backwards = getattr(net, 'commnet_window_backwards', 0) + 1
 
 
 def standin_for_backward(args, net, rec=None):

@@ -22,6 +22,9 @@
 //                         all of them (mlp_bwd_kernel), and the window as one host call.
 //                         The rnn / mlp entries: hid 64 / 128; their _wide twins (ic3_rnn_backward_wide, ...): the same bodies for
 //                         64 / 128 / 256 (what ic3net_amd calls).
+//   ic3_commnet_pass_backward / ic3_commnet_backward   the NON-recurrent CommNet module: a window is T x R independent rows in T x E
+//                         independent envs — per communication pass one launch of commnet_pass_bwd_kernel, ic3_comm_backward and
+//                         ic3_rnn_weight_grad over all of them, and the window (in chunks of whole steps) as one host call; hid 64 / 128 / 256.
 // and what sizes their buffers / says whether they run: ic3_comm_backward_partials, ic3_lstm_weight_grad[_wide]_scratch_floats,
 // ic3_bptt_backward_supported, ic3_bptt_first_chain_envs, ic3_rnn_ / ic3_mlp_backward_partials and _supported,
 // ic3_rnn_weight_grad_scratch_floats, and the _wide twins of the rnn / mlp ones.
@@ -1517,3 +1520,285 @@ static int mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream, 
 
 extern "C" int ic3_mlp_backward(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream) { return mlp_backward(env, b, stream, false); }
 extern "C" int ic3_mlp_backward_wide(ic3_env* env, const ic3_mlp_bptt* b, ic3_stream stream) { return mlp_backward(env, b, stream, true); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// ic3_commnet_backward: the NON-recurrent CommNet module (comm.py:127-129, 179-224; the forward of commnet_fwd.hip),
+//     x = h_0 = tanh(enc),   h_{i+1} = tanh(x + F_i h_i + C_i mix(h_i) + b_i)   i = 0 .. P - 1,   [logits | value] = W_heads h_P + b
+// differentiated over a window of recorded steps.  No state crosses a step: the window is Q = T x R independent rows in T x E
+// independent envs, and the backward is a chain of window-wide launches — every one of them a launch the library already had,
+// but for the two small kernels below:
+//     T x ic3_env_encode_at                       enc of every snapshot -> slot 0 of the h_pass ring
+//     ic3_commnet_forward_record over T x E envs  h_0 .. h_P of every row -> the ring (slot 0 over enc: a workgroup owns its rows)
+//     per pass i = P - 1 .. 0:
+//       commnet_pass_bwd_kernel                   dz_i = (dh_{i+1} [+ d . W_heads: last pass]) (1 - h_{i+1}^2) -> [dz_i | dz_i F_i] rows,
+//                                                 the dz slot, dx (+)= dz_i, column sums of dz_i (d b_i) as per-workgroup partials
+//       ic3_comm_backward on [dz_i | dz_i F_i]    dh_i = dz_i F_i + mix(dz_i) C_i,  dC_i partials = mix(dz_i)^T h_i   (the mixing matrix
+//                                                 is symmetric: mix(dz C) = mix(dz) C and dz^T mix(h) = mix(dz)^T h)
+//       ic3_rnn_weight_grad_wide                  dF_i += dz_i^T h_i over all rows
+//       wgrad_reduce x 2                          dC_i += its partials, d b_i += its partials, in partial order
+//     commnet_de_kernel                           de = (dx + dh_0)(1 - h_0^2)
+//     encoder_tail                                the sparse encoder's stage 1 over the de ring
+//     ic3_heads_grad                              (with heads_w_grad) the heads' gradient on slot P of the ring
+// all on the caller's stream.
+//
+// commnet_pass_bwd_kernel<H>: the tile machine of rnn_tanh_bwd_kernel (TanhTile<H>: 4H threads, persistent over 64-row tiles, F_i in
+// LDS in fragment order at 64 / 128, its fragments streamed from L2 at 256, buffer descriptors whose ranges drop the rows past the
+// window) with mlp_bwd_kernel's epilogue (the product back through the LDS tile, 16-byte stores) and 64-bit row offsets.  dz is
+// stored TWICE — columns [0, H) of the [Q][2H] rows ic3_comm_backward reads and the contiguous [Q][H] slot the weight gradient
+// reads (rnn_wgrad_kernel has no leading dimension) — H floats = 4 H bytes per row and pass more than a fused chain would move
+// (512 B at H = 128): accepted here, the stages are launches the library already tests.
+// HBM per row and pass: dh_in, h_{i+1}, dx in, dz twice, dz F_i, dx out = 7 H floats (+ OT on the last pass); MFMA 2 H^2 flop.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace ic3 {
+
+struct CommnetPassArgs {
+    const float* dh_in;      // [Q][H] or null (zeros)
+    const float* h_next;     // [Q][H] h_{i+1}
+    const float* dhead;      // [Q][OT] or null (OT == 0 then)
+    const float* w_heads;    // [OT][H]
+    const float* fw;         // [H][H] f_modules[i].weight (out, in): dz . F_i
+    float* dxh;              // [Q][2H]: [dz | dz . F_i]
+    float* dz;               // [Q][H]
+    float* dx;               // [Q][H]: = dz (dx_add == 0) or += dz
+    float* db_part;          // [gridDim.x][H]
+    long long Q;
+    int OT, tiles, dx_add, accumulate;
+};
+
+template <int H>
+__global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void commnet_pass_bwd_kernel(const CommnetPassArgs a)
+{
+    using Tile = TanhTile<H>;
+    constexpr int NT = Tile::NT, LDA = Tile::LDA, LDA4 = Tile::LDA4, RPP = Tile::RPP, PER = Tile::PER;
+    IC3_DYNAMIC_LDS(float, smem);
+    const Tile t(smem);                                          // (Dz: the tile's dz, then its dz . F_i)
+    const int OT = a.OT;
+    t.stage_weights(a.fw, a.w_heads, OT);
+    bp_f32x4 bsum = { 0.f, 0.f, 0.f, 0.f };
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        const long long r0 = (long long)tile * 64;
+        const int rows = (a.Q - r0) < 64 ? (int)(a.Q - r0) : 64;
+        // (rows past the window read 0 and their stores are dropped: the ranges of the buffer descriptors)
+        const __amdgpu_buffer_rsrc_t rdi = bp_rsrc(a.dh_in ? a.dh_in + r0 * H : a.h_next, a.dh_in ? (long long)rows * H * 4 : 0);
+        const __amdgpu_buffer_rsrc_t rh = bp_rsrc(a.h_next + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rd = bp_rsrc(a.dhead ? a.dhead + r0 * OT : a.h_next, a.dhead ? (long long)rows * OT * 4 : 0);
+        const __amdgpu_buffer_rsrc_t rz = bp_rsrc(a.dz + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rx = bp_rsrc(a.dx + r0 * H, (long long)rows * H * 4);
+        const __amdgpu_buffer_rsrc_t rxh = bp_rsrc(a.dxh + r0 * 2 * H, (long long)rows * 2 * H * 4);
+        bp_f32x4 dv[PER], hv[PER], xv[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int off = ((t.rg + RPP * i) * H + 4 * t.c4) * 4;
+            dv[i] = bp_load4(rdi, off);
+            hv[i] = bp_load4(rh, off);
+            xv[i] = a.dx_add ? bp_load4(rx, off) : bp_f32x4{ 0.f, 0.f, 0.f, 0.f };
+        }
+        for (int i = t.tid; i < 64 * OT; i += NT) t.Sd[i] = bp_load1(rd, i * 4);
+        __syncthreads();
+        // ---- phase 0: dz of the tile -> the [dz | .] rows, the dz slot, dx, LDS, column sums
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int row = t.rg + RPP * i;
+            const bp_f32x4 v = t.heads_share(dv[i], row, OT);
+            const bp_f32x4 z = v * (1.0f - hv[i] * hv[i]);
+            bsum += z;
+            t.Dz4[row * LDA4 + t.c4] = z;
+            bp_store4(z, rz, (row * H + 4 * t.c4) * 4);
+            bp_store4(z, rxh, (row * 2 * H + 4 * t.c4) * 4);
+            bp_store4(xv[i] + z, rx, (row * H + 4 * t.c4) * 4);
+        }
+        __syncthreads();
+        // ---- phase 1: dz . F_i
+        const bp_f32x16 acc = t.product(a.fw);
+        __syncthreads();                                         // every wave has read the tile's dz rows
+        // ---- epilogue: the product back through the LDS tile, stored 16 bytes per lane into columns [H, 2H)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg)
+            t.Dz[(32 * t.rb + (reg & 3) + 8 * (reg >> 2) + 4 * t.lh) * LDA + 32 * t.cb + t.li] = acc[reg];
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int row = t.rg + RPP * i;
+            bp_store4(t.Dz4[row * LDA4 + t.c4], rxh, (row * 2 * H + H + 4 * t.c4) * 4);
+        }
+        __syncthreads();                                         // every thread is done with the tile's LDS
+    }
+    t.column_sums(bsum, a.db_part, a.accumulate);
+}
+
+// de = (dx + dh_0)(1 - h_0^2) over Q rows of H floats (n4 float4): through x = h_0 = tanh(enc)
+__global__ __launch_bounds__(256) void commnet_de_kernel(const bp_f32x4* __restrict__ dx, const bp_f32x4* __restrict__ dh0,
+                                                         const bp_f32x4* __restrict__ h0, bp_f32x4* __restrict__ de, long long n4)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const bp_f32x4 x = h0[i];
+        de[i] = (dx[i] + dh0[i]) * (1.0f - x * x);
+    }
+}
+
+}  // namespace ic3
+
+extern "C" int ic3_commnet_backward_supported(const ic3_env* env, int H, int N)
+{
+    if (!env || N != env->dims.N || !ic3_commnet_forward_supported(H, N)) return 0;
+    return tanh_supported_wide(env, H);
+}
+
+extern "C" int ic3_commnet_pass_backward_partials(long long Q, int H) { return tanh_partials(Q, H, true); }
+
+// the pass launch alone (also the unit the tests drive): returns the number of partials written / added to
+extern "C" int ic3_commnet_pass_backward(const float* dh_in, const float* h_next, const float* dhead, const float* w_heads, int OT,
+                                         const float* f_weight, float* dxh, float* dz, float* dx, int dx_add, float* dbias_partials,
+                                         int accumulate, long long Q, int H, ic3_stream stream)
+{
+    using namespace ic3;
+    const char* const fn = "ic3_commnet_pass_backward: ";
+    if (!h_next || !f_weight || !dxh || !dz || !dx || !dbias_partials || Q <= 0 || (dhead && !w_heads))
+        return fail(-22, std::string(fn) + "null argument");
+    if (!tanh_size_ok(H, true)) return fail(-38, std::string(fn) + TANH_SIZES[1]);
+    if (!dhead) OT = 0;
+    else if (OT < 1) return fail(-22, std::string(fn) + "OT >= 1");
+    else if (OT > 16) return fail(-38, std::string(fn) + "at most 16 output columns");
+    if (Q >= (1ll << 36)) return fail(-22, std::string(fn) + "Q < 2^36");
+    const int grid = tanh_partials(Q, H, true);
+    const CommnetPassArgs a{ dh_in, h_next, dhead, w_heads, f_weight, dxh, dz, dx, dbias_partials, Q, OT, (int)((Q + 63) / 64),
+                             dx_add, accumulate };
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = H == 256   ? launch_kernel(commnet_pass_bwd_kernel<256>, dim3(grid), dim3(1024), TanhTile<256>::LDS_BYTES, s, a)
+                   : H == 128 ? launch_kernel(commnet_pass_bwd_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES, s, a)
+                              : launch_kernel(commnet_pass_bwd_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES, s, a);
+    return rc < 0 ? rc : grid;
+}
+
+// The steps of one chunk of a window: as many as keep every launch of the chain inside its 32-bit limits — the envs of a chunk as
+// one int (ic3_comm_backward, the forward: T' x E), its rows below 2^31 - 2^16 (the encoder's window form), the weight gradient's K
+// slices below 2 GB (rnn_wgrad_plan) — and at most `most` (> 0: the caller's bound).
+static int commnet_chunk_steps(int T, int E, int N, int H, int most)
+{
+    const long long R = (long long)E * N;
+    long long tc = std::min<long long>(T, ((1ll << 31) - (1ll << 16)) / R);
+    if (most > 0) tc = std::min<long long>(tc, most);
+    while (tc > 1 && !rnn_wgrad_plan(tc * R, H, H).fits) tc = (tc + 1) / 2;
+    return tc < 1 ? 0 : (int)tc;
+}
+
+extern "C" int ic3_commnet_backward_chunk_steps(const ic3_env* env, int T, int H, int max_chunk_steps)
+{
+    if (!env || T <= 0 || !tanh_size_ok(H, true)) return 0;
+    return commnet_chunk_steps(T, env->dims.E, env->dims.N, H, max_chunk_steps);
+}
+
+// scratch of a window run in chunks of Tc steps, in floats: [bias partials | dC partials | weight-gradient slices | heads] — each
+// the larger of what a full chunk and the short last one ask for (a larger launch may leave FEWER partials: more rounds)
+struct CommnetScratch {
+    size_t bias, dcw, wgrad, heads;
+    size_t total() const { return bias + dcw + wgrad + heads; }
+};
+static CommnetScratch commnet_scratch(int T, int Tc, int E, int N, int H)
+{
+    CommnetScratch sc{ 0, 0, 0, ic3_heads_grad_scratch_floats(H) };
+    for (const int tn : { Tc, T % Tc }) {
+        if (!tn) continue;
+        const long long Q = (long long)tn * E * N;
+        sc.bias = std::max(sc.bias, (size_t)tanh_partials(Q, H, true) * H);
+        sc.dcw = std::max(sc.dcw, (size_t)ic3_comm_backward_partials(tn * E, N) * H * H);
+        sc.wgrad = std::max(sc.wgrad, ic3_rnn_weight_grad_wide_scratch_floats(Q, H));
+    }
+    return sc;
+}
+
+extern "C" size_t ic3_commnet_backward_scratch_floats(const ic3_env* env, int T, int H, int max_chunk_steps)
+{
+    const int tc = ic3_commnet_backward_chunk_steps(env, T, H, max_chunk_steps);
+    if (!tc) return 0;
+    return commnet_scratch(T, tc, env->dims.E, env->dims.N, H).total();
+}
+
+extern "C" int ic3_commnet_backward(ic3_env* env, const ic3_commnet_bptt* b, ic3_stream stream)
+{
+    using namespace ic3;
+    const char* const fn = "ic3_commnet_backward";
+    const std::string f = std::string(fn) + ": ";
+    if (const int rc = window_open(fn, "ic3_commnet_bptt", env, b, tanh_supported_wide,
+                                   "hid_size 64 / 128 / 256, a grid whose encoder backward runs in its partial-sums form", true);
+        rc < 0)
+        return rc;
+    const int T = b->T, E = b->E, N = b->N, H = b->H, P = b->passes, OT = b->OT;
+    if (N > 64) return fail(-38, f + "at most 64 agents per env");
+    if (P < 1 || b->max_chunk_steps < 0) return fail(-22, f + "passes >= 1, max_chunk_steps >= 0");
+    if (!b->dhead || !b->snaps || !b->enc_wt || !b->enc_bias || !b->wp || !b->bias || !b->w_heads || !b->f_weight || !b->f_grad ||
+        !b->bias_grad || !b->h_pass || !b->dxh || !b->dz || !b->dx || !b->de || !b->dh || !b->scratch || !b->enc_work)
+        return fail(-22, f + "null argument");
+    if (!b->comm_zero && (!b->c_weight || !b->c_grad)) return fail(-22, f + "C's weights and their gradients");
+    if ((b->heads_w_grad != nullptr) != (b->heads_b_grad != nullptr)) return fail(-22, f + "heads_w_grad and heads_b_grad come together");
+    for (int i = 0; i < P; ++i)
+        if (!b->f_weight[i] || !b->f_grad[i] || !b->bias_grad[i] || (!b->comm_zero && (!b->c_weight[i] || !b->c_grad[i])))
+            return fail(-22, f + "null per-pass pointer");
+    if (b->enc_window && ic3_env_encode_backward_window_work(env, H) <= 0)
+        return fail(-22, f + "enc_window on a configuration without ic3_env_encode_backward_window");
+    const int Tc = commnet_chunk_steps(T, E, N, H, b->max_chunk_steps);
+    if (!Tc) return fail(-22, f + "one step of the window is past the launches' 32-bit limits");
+    const long long R = (long long)E * N;
+    const CommnetScratch sc = commnet_scratch(T, Tc, E, N, H);
+    float* const bias_parts = b->scratch;
+    float* const dcw_parts = bias_parts + sc.bias;
+    float* const wg_scratch = dcw_parts + sc.dcw;
+    float* const heads_scratch = wg_scratch + sc.wgrad;
+    hipStream_t s = (hipStream_t)stream;
+    int enc_first = b->enc_first;
+    for (int t0 = 0; t0 < T; t0 += Tc) {
+        const int tn = std::min(Tc, T - t0);
+        const long long Q = (long long)tn * R;
+        const size_t ring = (size_t)Q * H;                        // floats between two slots of the h_pass ring: this chunk's rows
+        const int32_t* snaps = b->snaps + (size_t)t0 * b->snap_words;
+        const int32_t* alive = b->alive ? b->alive + (size_t)t0 * R : nullptr;
+        const int32_t* gate = b->gate ? b->gate + (size_t)t0 * R : nullptr;
+        const float* dhead = b->dhead + (size_t)t0 * R * OT;
+        // 1. enc of every recorded step -> slot 0 of the ring
+        for (int t = 0; t < tn; ++t) {
+            const int rc = ic3_env_encode_at(env, snaps + (size_t)t * b->snap_words, b->enc_wt, b->enc_bias, b->loc_table,
+                                             b->h_pass + (size_t)t * R * H, H, H, stream);
+            if (rc < 0) return rc;
+        }
+        // 2. the forward again, h_0 .. h_P kept (h_0 over enc)
+        int rc = ic3_commnet_forward_record(b->h_pass, tn * E, N, H, P, b->wp, b->wp3, b->bias, nullptr, nullptr, nullptr, 0, b->mode_avg,
+                                            b->comm_zero, alive, gate, nullptr, nullptr, b->h_pass, stream);
+        if (rc < 0) return rc;
+        // 3. the passes, last to first
+        for (int i = P - 1; i >= 0; --i) {
+            const bool last = i == P - 1;
+            rc = ic3_commnet_pass_backward(last ? nullptr : b->dh, b->h_pass + (size_t)(i + 1) * ring, last ? dhead : nullptr, b->w_heads, OT,
+                                           b->f_weight[i], b->dxh, b->dz, b->dx, last ? 0 : 1, bias_parts, 0, Q, H, stream);
+            if (rc < 0) return rc;
+            const int nb = rc;
+            rc = ic3_comm_backward(b->dxh, 2 * H, b->h_pass + (size_t)i * ring, alive, gate, b->comm_zero ? nullptr : b->c_weight[i], nullptr,
+                                   b->dh, dcw_parts, 0, tn * E, N, H, b->mode_avg, b->comm_zero, stream);
+            if (rc < 0) return rc;
+            const int nc = rc;
+            rc = rnn_weight_grad(b->dz, b->h_pass + (size_t)i * ring, nullptr, Q, H, b->f_grad[i], 1, wg_scratch, stream, true);
+            if (rc < 0) return rc;
+            if (nc > 0 && (rc = wgrad_reduce(dcw_parts, nc, H * H, b->c_grad[i], 1, s)) < 0) return rc;
+            if ((rc = wgrad_reduce(bias_parts, nb, H, b->bias_grad[i], 1, s)) < 0) return rc;
+        }
+        // 4. through x = h_0 = tanh(enc)
+        {
+            const long long n4 = Q * (H / 4);
+            const int blocks = (int)std::min<long long>((n4 + 255) / 256, 4096);
+            rc = launch_kernel(commnet_de_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const bp_f32x4*>(b->dx),
+                               reinterpret_cast<const bp_f32x4*>(b->dh), reinterpret_cast<const bp_f32x4*>(b->h_pass),
+                               reinterpret_cast<bp_f32x4*>(b->de), n4);
+            if (rc < 0) return rc;
+        }
+        // 5. the sparse encoder's stage 1 over the de ring
+        rc = encoder_tail(env, snaps, b->snap_words, tn, b->de, H, R * H, H, b->enc_work, enc_first, b->enc_window != 0, stream);
+        if (rc < 0) return rc;
+        enc_first = 0;
+        // 6. the heads' gradient on h_P
+        if (b->heads_w_grad) {
+            rc = ic3_heads_grad(dhead, b->h_pass + (size_t)P * ring, Q, H, OT, b->heads_w_grad, b->heads_b_grad, heads_scratch, stream);
+            if (rc < 0) return rc;
+        }
+    }
+    return (T + Tc - 1) / Tc;     // chunks run
+}

@@ -61,6 +61,10 @@ struct CommnetArgs {
     StepOut so;
     PPState pp;
     TJState tj;
+    // ic3_commnet_forward_record (RECORD): h_0 .. h_passes of every row, slot i at h_pass + i * h_pass_stride floats.  Behind every
+    // other field: the offsets the other instantiations read their arguments at stay where they were.
+    float* h_pass;             // [passes + 1][R][H]
+    long long h_pass_stride;
 };
 
 // Wave priority (policy_step.hip: the phases around a matrix product are dependent chains on the tile's critical path, the
@@ -71,9 +75,13 @@ struct CommnetArgs {
 // recurrence — keeps only the h half of the A tile (33.8 instead of 66.5 KB at H = 128; the heads' weights in a region of their
 // own): THREE workgroups per CU instead of two, so that the obs stores of one tile overlap the matrix work / dependent chains of
 // two others (the kernel has no in-stream store pacing: a tile's stores and its products do not overlap inside a workgroup).
-template <int H, int KIND = 0, bool NARROW = false>
+// RECORD (ic3_commnet_forward_record, KIND 0, the wide tile): the tile's h rows also go to the h_pass ring behind x and behind every
+// pass — what the window backward of the module differentiates (ic3_commnet_backward); `out` may be null there (no heads).  A
+// template flag: the other instantiations carry no trace of it.
+template <int H, int KIND = 0, bool NARROW = false, bool RECORD = false>
 __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void commnet_forward_kernel(const CommnetArgs a)
 {
+    static_assert(!RECORD || (KIND == 0 && !NARROW), "the recording instantiation is the plain forward's");
     CN_PRIO(3);
     constexpr int K = 2 * H, LDA = (NARROW ? H : K) + 4, LDA4 = LDA / 4, NT = 2 * H, H4 = H / 4, KB = K / 8, BM = 64;
     constexpr int HO = NARROW ? 0 : H, HO4 = HO / 4;             // column of the h half inside the tile
@@ -209,6 +217,15 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
         for (int j = 0; j < N; ++j) n_alive += sal[el * N + j];
         sscale[el] = (a.mode_avg && n_alive > 1) ? 1.0f / (float)(n_alive - 1) : 1.0f;
     }
+    // RECORD: the tile's h rows -> slot `slot` of the ring (16 bytes per lane; a workgroup owns its rows: slot 0 may be `enc` itself)
+    auto record = [&](int slot) __attribute__((always_inline)) {
+        float* dst = a.h_pass + (size_t)slot * (size_t)a.h_pass_stride;
+        for (int idx = tid; idx < rows * H4; idx += NT) {
+            const int row = idx / H4, c4 = idx - row * H4;
+            *reinterpret_cast<cn_f32x4*>(dst + (r0 + row) * H + 4 * c4) = As4[row * LDA4 + HO4 + c4];
+        }
+    };
+    if constexpr (RECORD) record(0);
     float xr[2][16];                                             // x in the MFMA C/D layout, kept for every pass
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
@@ -348,6 +365,10 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
                 As[lr * LDA + HO + col] = fast_tanh(xr[rt][reg] + acc[rt][reg] + b);
             }
         __syncthreads();
+        if constexpr (RECORD) record(pass + 1);
+    }
+    if constexpr (RECORD) {
+        if (!a.out) return;                                      // (workgroup-uniform: the window backward needs no heads)
     }
 
     // ---- heads + value head (comm.py:228,239): weights -> rows [0, OT) of the comm half, logits -> zl ------------------------
@@ -485,20 +506,28 @@ extern "C" int ic3_commnet_pack(const float* C_weight, const float* f_weight, fl
     return 0;
 }
 
-extern "C" int ic3_commnet_forward(const float* enc, int E, int N, int H, int comm_passes, const float* wp, const void* wp3,
-                                   const float* bias,
-                                   const float* head_w, const float* head_b, const int32_t* head_sizes, int nheads,
-                                   int mode_avg, int comm_zero, const int32_t* alive_in, const int32_t* comm_in, float* out,
-                                   float* h_out, ic3_stream stream)
+// ic3_commnet_forward (h_pass null) and ic3_commnet_forward_record (the RECORD instantiation; `out` null: no heads, their
+// arguments are not read)
+static int commnet_forward(const char* fn, const float* enc, int E, int N, int H, int comm_passes, const float* wp, const void* wp3,
+                           const float* bias, const float* head_w, const float* head_b, const int32_t* head_sizes, int nheads,
+                           int mode_avg, int comm_zero, const int32_t* alive_in, const int32_t* comm_in, float* out, float* h_out,
+                           float* h_pass, ic3_stream stream)
 {
     using namespace ic3;
-    if (!enc || !wp || !bias || !head_w || !head_b || !head_sizes || !out || E <= 0 || comm_passes < 1)
-        return fail(-22, "ic3_commnet_forward: bad arguments");
+    const bool heads = out || !h_pass;
+    if (!enc || !wp || !bias || (heads && (!head_w || !head_b || !head_sizes || !out)) || E <= 0 || comm_passes < 1)
+        return fail(-22, std::string(fn) + ": bad arguments");
     if (!ic3_commnet_forward_supported(H, N))
-        return fail(-38, "ic3_commnet_forward: needs hid_size 64/128/256 and <= 64 agents per env");
+        return fail(-38, std::string(fn) + ": needs hid_size 64/128/256 and <= 64 agents per env");
     CommnetArgs a{};
-    int sz[4];
-    if (int rc = parse_heads(head_sizes, nheads, "ic3_commnet_forward", a.OT, sz)) return rc;
+    int sz[4] = { 0, 0, 0, 0 };
+    if (heads) {
+        if (int rc = parse_heads(head_sizes, nheads, fn, a.OT, sz)) return rc;
+    } else {
+        nheads = 0;
+    }
+    a.h_pass = h_pass;
+    a.h_pass_stride = (long long)E * N * H;
     a.enc = enc;
     a.wp = wp;
     a.wp3 = wp3;
@@ -527,8 +556,29 @@ extern "C" int ic3_commnet_forward(const float* enc, int E, int N, int H, int co
     hipStream_t s = (hipStream_t)stream;
     return with_hid(H, [&](auto hid) {
         constexpr int HH = decltype(hid)::value;
+        if (h_pass) return launch_kernel(commnet_forward_kernel<HH, 0, false, true>, dim3(tiles), dim3(2 * HH), lds, s, a);
         return launch_kernel(commnet_forward_kernel<HH, 0>, dim3(tiles), dim3(2 * HH), lds, s, a);
     });
+}
+
+extern "C" int ic3_commnet_forward(const float* enc, int E, int N, int H, int comm_passes, const float* wp, const void* wp3,
+                                   const float* bias,
+                                   const float* head_w, const float* head_b, const int32_t* head_sizes, int nheads,
+                                   int mode_avg, int comm_zero, const int32_t* alive_in, const int32_t* comm_in, float* out,
+                                   float* h_out, ic3_stream stream)
+{
+    return commnet_forward("ic3_commnet_forward", enc, E, N, H, comm_passes, wp, wp3, bias, head_w, head_b, head_sizes, nheads, mode_avg,
+                           comm_zero, alive_in, comm_in, out, h_out, nullptr, stream);
+}
+
+extern "C" int ic3_commnet_forward_record(const float* enc, int E, int N, int H, int comm_passes, const float* wp, const void* wp3,
+                                          const float* bias, const float* head_w, const float* head_b, const int32_t* head_sizes,
+                                          int nheads, int mode_avg, int comm_zero, const int32_t* alive_in, const int32_t* comm_in,
+                                          float* out, float* h_out, float* h_pass, ic3_stream stream)
+{
+    if (!h_pass) return ic3::fail(-22, "ic3_commnet_forward_record: bad arguments");
+    return commnet_forward("ic3_commnet_forward_record", enc, E, N, H, comm_passes, wp, wp3, bias, head_w, head_b, head_sizes, nheads,
+                           mode_avg, comm_zero, alive_in, comm_in, out, h_out, h_pass, stream);
 }
 
 // Envs per tile of the NARROW Predator-Prey launch (the IC baseline's stand-in, the tanh recurrence).  That launch is bound by its

@@ -53,7 +53,10 @@ def _hip_graph_mode(v):
 
 
 _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_graph', True), ('tune_gemm', 'flag', False),
-                 ('dist_backend', str, 'nccl')]     # 'nccl' = RCCL over xGMI; 'gloo' for several ranks on one GPU (tests)
+                 ('dist_backend', str, 'nccl'),     # 'nccl' = RCCL over xGMI; 'gloo' for several ranks on one GPU (tests)
+                 # 1: the non-recurrent CommNet module's update runs window-wide launches (bptt._backward_window_commnet);
+                 # 0: the per-step loop (bptt._backward_episode_commnet)
+                 ('commnet_window_backward', int, 1)]
 
 
 def build_parser(argv):

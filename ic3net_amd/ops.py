@@ -579,6 +579,141 @@ def mlp_backward(env, T, E, N, H, h, dhead, snaps, enc_wt, enc_bias, a2, w_heads
     check(_lib.lib().ic3_mlp_backward_wide(env._h, C.byref(b), stream()))
 
 
+def commnet_backward_supported(env, H, N):
+    """ic3_commnet_backward_supported: the non-recurrent CommNet module's window backward runs for this env handle at hid_size H."""
+    return bool(_lib.lib().ic3_commnet_backward_supported(env._h, int(H), int(N)))
+
+
+def commnet_backward_chunk_steps(env, T, H, max_chunk_steps=0):
+    """Steps per chunk of an ic3_commnet_backward window of T steps — what its rings are sized for (0: the call cannot run)."""
+    return int(_lib.lib().ic3_commnet_backward_chunk_steps(env._h, int(T), int(H), int(max_chunk_steps)))
+
+
+def commnet_backward_ring_floats(env, T, E, N, H, P, max_chunk_steps=0):
+    """Floats of the rings + scratch ops.commnet_backward allocates for a window: with Qc = chunk steps x E x N rows, the enc /
+    h_pass ring (P + 1) Qc H, dxh Qc 2H, dz, dx, de, dh Qc H each — (P + 7) Qc H — and ic3_commnet_backward_scratch_floats."""
+    tc = commnet_backward_chunk_steps(env, T, H, max_chunk_steps)
+    return (P + 7) * tc * E * N * H + int(_lib.lib().ic3_commnet_backward_scratch_floats(env._h, int(T), int(H), int(max_chunk_steps)))
+
+
+def commnet_pass_backward_partials(Q, H):
+    return int(_lib.lib().ic3_commnet_pass_backward_partials(int(Q), int(H)))
+
+
+def commnet_pass_backward(dh_in, h_next, dhead, w_heads, f_weight, dxh, dz, dx, dbias_partials, dx_add=False, accumulate=False):
+    """ic3_commnet_pass_backward: one communication pass of the module's backward over Q independent rows in one launch —
+    dz = (dh_in + dhead . w_heads) * (1 - h_next^2) (either addend may be None) -> dz (Q, H) and dxh[:, :H]; dz . f_weight ->
+    dxh[:, H:]; dx = dz or (dx_add) dx += dz; column sums of dz into dbias_partials (commnet_pass_backward_partials(Q, H) rows)."""
+    _need_cuda(h_next, "commnet_pass_backward")
+    Q, H = h_next.shape
+    for v in (dh_in, h_next, dz, dx):
+        assert v is None or (v.is_contiguous() and tuple(v.shape) == (Q, H) and v.dtype == torch.float32)
+    assert dxh.is_contiguous() and tuple(dxh.shape) == (Q, 2 * H) and dxh.dtype == torch.float32
+    OT = 0
+    if dhead is not None:
+        OT = dhead.shape[-1]
+        assert dhead.is_contiguous() and tuple(dhead.shape) == (Q, OT) and dhead.dtype == torch.float32
+        assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and w_heads.dtype == torch.float32
+    assert f_weight.is_contiguous() and tuple(f_weight.shape) == (H, H) and f_weight.dtype == torch.float32
+    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (commnet_pass_backward_partials(Q, H), H)
+    return check(_lib.lib().ic3_commnet_pass_backward(ptr(dh_in), ptr(h_next), ptr(dhead), ptr(w_heads) if dhead is not None else None, OT,
+                                                      ptr(f_weight), ptr(dxh), ptr(dz), ptr(dx), int(bool(dx_add)), ptr(dbias_partials),
+                                                      int(bool(accumulate)), Q, H, stream()))
+
+
+def commnet_forward_record(enc, E, N, wp, bias, mode_avg, comm_zero, alive_in, comm_in, h_pass, wp3=None):
+    """ic3_commnet_forward_record without the heads: h_pass (P + 1, E * N, H) <- h_0 = tanh(enc) .. h_P of every row; enc (E * N, H)
+    may be h_pass[0] itself."""
+    _need_cuda(enc, "commnet_forward_record")
+    R, H = enc.shape
+    P = wp.shape[0]
+    assert R == E * N and enc.is_contiguous() and enc.dtype == torch.float32
+    assert h_pass.is_contiguous() and tuple(h_pass.shape) == (P + 1, R, H) and h_pass.dtype == torch.float32
+    for m in (alive_in, comm_in):
+        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
+    assert wp3 is None or (wp3.is_contiguous() and tuple(wp3.shape) == (P, 3 * H * H))
+    check(_lib.lib().ic3_commnet_forward_record(ptr(enc), E, N, H, P, ptr(wp), ptr(wp3), ptr(bias), None, None, None, 0,
+                                                int(bool(mode_avg)), int(bool(comm_zero)), ptr(alive_in), ptr(comm_in), None, None,
+                                                ptr(h_pass), stream()))
+    return h_pass
+
+
+def commnet_backward(env, T, E, N, H, dhead, snaps, alive, gate, enc_wt, enc_bias, wp, bias, w_heads, f_weights, c_weights, f_grads,
+                     c_grads, bias_grads, heads_w_grad=None, heads_b_grad=None, wp3=None, loc_table=None, mode_avg=True, comm_zero=False,
+                     enc_first=True, enc_window=True, max_chunk_steps=0, work=None):
+    """ic3_commnet_backward: the backward through a window of T recorded steps of the non-recurrent CommNet module as one host call
+    (csrc/bptt_kernels.hip) — T encoder launches, the recording forward over T x E envs, per pass the pass launch, ic3_comm_backward
+    and the weight gradient over all rows, the pointwise step through x, the encoder's first stage, the heads' gradient.  dhead
+    (T, R, OT), alive / gate (T, E, N) int32 or None, f_weights / c_weights: lists of P (H, H) weights as stored, f_grads / c_grads
+    (H, H) / bias_grads (H,): lists of P DISTINCT tensors, added to; heads_w_grad (OT, H) / heads_b_grad (OT,) added to.  The rings
+    (commnet_backward_ring_floats) live in `work` between calls.  Returns (rings dict, chunks run)."""
+    import ctypes as C
+    _need_cuda(dhead, "commnet_backward")
+    R, P = E * N, len(f_weights)
+    OT = dhead.shape[-1]
+    dev = dhead.device
+    assert dhead.is_contiguous() and dhead.numel() == T * R * OT and dhead.dtype == torch.float32
+    assert snaps.is_contiguous() and snaps.dtype == torch.int32 and snaps.shape[0] >= T
+    for m in (alive, gate):
+        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and tuple(m.shape) == (T, E, N))
+    assert enc_wt.is_contiguous() and enc_wt.dtype == torch.float32 and tuple(enc_wt.shape) == (env.obs_dim, H)
+    assert enc_bias.is_contiguous() and enc_bias.numel() == H
+    assert wp.is_contiguous() and tuple(wp.shape) == (P, 2 * H * H) and bias.is_contiguous() and tuple(bias.shape) == (P, H)
+    assert wp3 is None or (wp3.is_contiguous() and tuple(wp3.shape) == (P, 3 * H * H))
+    assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H)
+    mats = list(f_weights) + list(f_grads) + ([] if comm_zero else list(c_weights) + list(c_grads))
+    assert len(f_grads) == len(bias_grads) == P and (comm_zero or len(c_weights) == len(c_grads) == P)
+    for v in mats:
+        assert v.is_contiguous() and tuple(v.shape) == (H, H) and v.dtype == torch.float32
+    for v in bias_grads:
+        assert v.is_contiguous() and v.numel() == H and v.dtype == torch.float32
+    assert len(set(v.data_ptr() for v in f_grads)) == P and len(set(v.data_ptr() for v in bias_grads)) == P
+    tc = commnet_backward_chunk_steps(env, T, H, max_chunk_steps)
+    if tc < 1:
+        raise NotImplementedError("commnet_backward: hid_size %d / this window cannot run" % H)
+    Qc = tc * R
+    nscr = int(_lib.lib().ic3_commnet_backward_scratch_floats(env._h, T, H, int(max_chunk_steps)))
+    buf = _scratch(work, 'commnet_bwd', (P + 7) * Qc * H + nscr, dev)
+    off = [0]
+
+    def take(*shape):
+        n = 1
+        for s in shape:
+            n *= s
+        v = buf[off[0]:off[0] + n].view(*shape)
+        off[0] += n
+        return v
+    rings = dict(h_pass=take(P + 1, Qc, H), dxh=take(Qc, 2 * H), dz=take(Qc, H), dx=take(Qc, H), de=take(Qc, H), dh=take(Qc, H))
+    scratch = take(nscr)
+    arr = lambda lst: (C.c_void_p * P)(*[v.data_ptr() for v in lst])
+    b = _lib.CommnetBptt()
+    b.struct_size = C.sizeof(b)
+    b.T, b.E, b.N, b.H, b.OT, b.passes = T, E, N, H, OT, P
+    b.mode_avg, b.comm_zero, b.enc_first, b.enc_window = int(bool(mode_avg)), int(bool(comm_zero)), int(bool(enc_first)), int(bool(enc_window))
+    b.max_chunk_steps = int(max_chunk_steps)
+    b.dhead, b.snaps, b.snap_words = dhead.data_ptr(), snaps.data_ptr(), snaps.stride(0)
+    b.alive = alive.data_ptr() if alive is not None else None
+    b.gate = gate.data_ptr() if gate is not None else None
+    b.enc_wt, b.enc_bias = enc_wt.data_ptr(), enc_bias.data_ptr()
+    b.loc_table = loc_table.data_ptr() if loc_table is not None else None
+    b.wp, b.bias, b.w_heads = wp.data_ptr(), bias.data_ptr(), w_heads.data_ptr()
+    b.wp3 = wp3.data_ptr() if wp3 is not None else None
+    keep = [arr(f_weights), arr(f_grads), arr(bias_grads)]      # (alive until the call has returned)
+    b.f_weight, b.f_grad, b.bias_grad = keep
+    if not comm_zero:
+        keep += [arr(c_weights), arr(c_grads)]
+        b.c_weight, b.c_grad = keep[3:]
+    if heads_w_grad is not None:
+        assert heads_w_grad.is_contiguous() and tuple(heads_w_grad.shape) == (OT, H) and heads_b_grad.is_contiguous() and heads_b_grad.numel() == OT
+        b.heads_w_grad, b.heads_b_grad = heads_w_grad.data_ptr(), heads_b_grad.data_ptr()
+    for k, v in rings.items():
+        setattr(b, k, v.data_ptr())
+    b.scratch = scratch.data_ptr()
+    b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
+    chunks = check(_lib.lib().ic3_commnet_backward(env._h, C.byref(b), stream()))
+    return rings, chunks
+
+
 HEADS_GRAD_MAX_OT = 16      # ic3_heads_grad: at most 16 output columns (the heads' actions in total + the value)
 
 

@@ -757,6 +757,86 @@ int ic3_commnet_forward(const float* enc, int E, int N, int H, int comm_passes, 
                         const float* head_w, const float* head_b, const int32_t* head_sizes, int nheads, int mode_avg,
                         int comm_zero, const int32_t* alive_in, const int32_t* comm_in, float* out, float* h_out /* or NULL */,
                         ic3_stream stream);
+/* ic3_commnet_forward that also KEEPS the hidden state of every pass (an instantiation of its own of the same kernel: the launches
+ * above are untouched): h_pass [comm_passes + 1][E*N][H], slot i = h_i — slot 0 = x = tanh(enc), slot comm_passes = what h_out
+ * receives, bit for bit.  Slot 0 may be `enc` itself (a workgroup reads the enc rows of its envs before it writes them).  out may be
+ * NULL: no heads are evaluated and head_w / head_b / head_sizes are not read.  Same sizes and return codes; h_pass NULL: -EINVAL. */
+int ic3_commnet_forward_record(const float* enc, int E, int N, int H, int comm_passes, const float* wp, const void* wp3 /* or NULL */,
+                               const float* bias, const float* head_w, const float* head_b, const int32_t* head_sizes, int nheads,
+                               int mode_avg, int comm_zero, const int32_t* alive_in, const int32_t* comm_in, float* out /* or NULL */,
+                               float* h_out /* or NULL */, float* h_pass, ic3_stream stream);
+
+/* The backward through a window of T recorded steps of the NON-recurrent CommNet module (the forward above) as ONE host call.  No
+ * state crosses a step, so the window is Q = T x R independent rows in T x E independent envs, and the chain is window-wide
+ * launches on the caller's stream, nothing on the host between them:
+ *   T x ic3_env_encode_at -> slot 0 of h_pass;  ic3_commnet_forward_record over T x E envs (h_0 over enc);
+ *   per pass i = P - 1 .. 0:  ic3_commnet_pass_backward: dz_i = (dh_{i+1} [+ d . W_heads on the last pass]) (1 - h_{i+1}^2) ->
+ *       dxh = [dz_i | dz_i . F_i], dz, dx (+)= dz_i, column sums of dz_i;  ic3_comm_backward on dxh with h_prev = h_i, C = C_i:
+ *       dh = dz_i F_i + mix(dz_i) C_i and dC_i's partials;  ic3_rnn_weight_grad_wide: f_grad[i] += dz_i^T h_i;  the partials of
+ *       dC_i and of the column sums added to c_grad[i] / bias_grad[i] in partial order;
+ *   de = (dx + dh)(1 - h_0^2);  the encoder's first stage over the de ring (enc_window != 0: ic3_env_encode_backward_window, finish
+ *   with ic3_env_encode_backward_window_finish[_ordered]; 0: ic3_env_encode_backward_accumulate per step, finish with
+ *   ic3_env_encode_backward_finish);  with heads_w_grad: ic3_heads_grad(dhead, h_P) += into heads_w_grad [OT][H] / heads_b_grad [OT].
+ * The window runs in chunks of whole steps, ic3_commnet_backward_chunk_steps(env, T, H, max_chunk_steps) each (the last may be
+ * shorter): as many as keep every launch inside its 32-bit limits (a chunk's envs and rows as int32, the encoder window form's
+ * T x R < 2^31 - 2^16, a weight-gradient K slice below 2 GB), at most max_chunk_steps when that is > 0.  The rings hold ONE chunk
+ * (Qc = chunk steps x R rows): h_pass [(P + 1) Qc H], dxh [Qc][2H], dz, dx, de, dh [Qc][H] (all written); scratch:
+ * ic3_commnet_backward_scratch_floats(env, T, H, max_chunk_steps) floats.
+ *   dhead [T][R][OT] (OT <= 16);  snaps: T snapshots, snap_words int32 apart;  alive / gate [T][E][N] int32 or NULL (everyone alive /
+ *   talking; collection mode: the caller fills in the rows of envs that start an episode);  enc_wt / enc_bias / loc_table:
+ *   ic3_env_encode_at's;  wp / wp3 / bias: ic3_commnet_forward's;  w_heads [OT][H];  f_weight / c_weight: HOST arrays of `passes`
+ *   device pointers to f_modules[i].weight / C_modules[i].weight as stored ([H][H]; c_weight, c_grad unused with comm_zero);
+ *   f_grad / c_grad ([H][H]) / bias_grad ([H]: C_i.bias's = f_i.bias's gradient): HOST arrays of device pointers, ADDED to, last
+ *   pass first (with shared weights two passes name the same weight; ic3net_amd hands a gradient buffer per pass and sums them
+ *   afterwards);  enc_work as the encoder form asks, enc_first != 0: this window starts the accumulation.
+ * No float atomics: every buffer and gradient is identical run to run (the plain window finish of the encoder aside).
+ * Returns the number of chunks run; -EINVAL: a null or ill-sized argument, a struct_size mismatch, T / E / N not the handle's;
+ * -ENOSYS: hid_size other than 64 / 128 / 256, more than 16 output columns or 64 agents, a grid whose encoder backward lacks the
+ * partial-sums form (ic3_commnet_backward_supported(env, H, N) answers 0 there).
+ * ic3_commnet_pass_backward: the pass launch alone over Q rows (64-bit row offsets, 16-byte stores) — dh_in NULL: zeros; dhead NULL:
+ * no heads' share (OT ignored); dx_add 0: dx = dz, else dx += dz; dbias_partials [ic3_commnet_pass_backward_partials(Q, H)][H]
+ * written (accumulate == 0) or added to; returns the number of partials. */
+typedef struct ic3_commnet_bptt {
+    uint32_t struct_size;   /* sizeof(ic3_commnet_bptt) of the caller's header (checked first: -EINVAL on mismatch) */
+    int32_t T, E, N, H, OT, passes;
+    int32_t mode_avg, comm_zero, enc_first, enc_window;
+    int32_t max_chunk_steps;   /* 0: the library chooses; > 0: at most this many steps per chunk */
+    const float* dhead;
+    const int32_t* snaps;
+    int64_t snap_words;
+    const int32_t* alive;
+    const int32_t* gate;
+    const float* enc_wt;
+    const float* enc_bias;
+    const float* loc_table;
+    const float* wp;
+    const void* wp3;
+    const float* bias;
+    const float* w_heads;
+    const float* const* f_weight;
+    const float* const* c_weight;
+    float* const* f_grad;
+    float* const* c_grad;
+    float* const* bias_grad;
+    float* heads_w_grad;    /* or NULL (both): the caller runs ic3_heads_grad on slot P of h_pass itself (one chunk) */
+    float* heads_b_grad;
+    float* h_pass;
+    float* dxh;
+    float* dz;
+    float* dx;
+    float* de;
+    float* dh;
+    float* scratch;
+    float* enc_work;
+} ic3_commnet_bptt;
+int ic3_commnet_backward_supported(const ic3_env* env, int H, int N);
+int ic3_commnet_backward_chunk_steps(const ic3_env* env, int T, int H, int max_chunk_steps);
+size_t ic3_commnet_backward_scratch_floats(const ic3_env* env, int T, int H, int max_chunk_steps);
+int ic3_commnet_pass_backward_partials(long long Q, int H);
+int ic3_commnet_pass_backward(const float* dh_in /* or NULL */, const float* h_next, const float* dhead /* or NULL */,
+                              const float* w_heads, int OT, const float* f_weight, float* dxh, float* dz, float* dx, int dx_add,
+                              float* dbias_partials, int accumulate, long long Q, int H, ic3_stream stream);
+int ic3_commnet_backward(ic3_env* env, const ic3_commnet_bptt* b, ic3_stream stream);
 
 /* The whole rollout iteration of trainer.py:43-108 for the NON-recurrent module as ONE launch — what ic3_policy_step is for
  * the recurrent policy: the sparse encoder on the env's integer state (enc_wt [obs_dim][H] = encoder.weight^T, enc_bias [H] =
