@@ -148,15 +148,20 @@ def test_commnet_step_refuses_what_it_does_not_cover():
     assert ops.commnet_step_supported(raw, 128)          # (round 5: episode starts inside the launch are handled here too)
 
 
-@pytest.mark.parametrize("wl", ["pp_hard_ic", "pp_hard_iric_tanh"])
-def test_narrow_launch_does_not_depend_on_its_tile_plan(wl):
+@pytest.mark.parametrize("wl,over", [("pp_hard_ic", dict()), ("pp_hard_iric_tanh", dict()),
+                                     ("pp_hard_ic", dict(hid_size=64)), ("pp_hard_iric_tanh", dict(hid_size=64)),
+                                     ("pp_hard_ic", dict(hid_size=256)), ("pp_hard_iric_tanh", dict(hid_size=256))],
+                         ids=["pp_hard_ic", "pp_hard_iric_tanh", "pp_hard_ic_h64", "pp_hard_iric_tanh_h64", "pp_hard_ic_h256",
+                              "pp_hard_iric_tanh_h256"])
+def test_narrow_launch_does_not_depend_on_its_tile_plan(wl, over):
     """The narrow Predator-Prey launch picks its envs per tile from the env count (plan_store_bound_ept in csrc/commnet_fwd.hip:
     2 / 3 / 6 / 4 envs per tile at the counts below).  An env's trajectory is keyed by (seed, env id) alone: the first 24 envs of
-    every run — obs rows, log-probs, values, draws, rewards — are the same bits whatever tile they sat in."""
+    every run — obs rows, log-probs, values, draws, rewards — are the same bits whatever tile they sat in.  At hid 64 / 128 / 256:
+    with test_baseline_step_onehop_gpu.py's small launches this ties the large ones of every size to float64."""
     import bench
     runs = []
     for E in (24, 600, 1536, 2048):
-        tr, a = bench.build_trainer(wl, E, 3, 40, 0, max_steps=6)
+        tr, a = bench.build_trainer(wl, E, 3, 40, 0, max_steps=6, **over)
         tr.begin_episode(0)
         rec = []
         for t in range(6):
