@@ -40,7 +40,16 @@ class Stats(C.Structure):
                 ("auto_env_steps", C.c_int64)]
 
 
-class Policy(C.Structure):
+class _SizedStruct(C.Structure):
+    """A struct of include/ic3_rollout.h whose first field is its own size: filled at construction (the library refuses a
+    struct whose struct_size is not the size it was compiled with)."""
+
+    def __init__(self, *a, **kw):             # positional arguments start at the field behind struct_size
+        super().__init__(*((0,) + a if a else a), **kw)
+        self.struct_size = C.sizeof(self)
+
+
+class Policy(_SizedStruct):
     """ic3_policy (include/ic3_rollout.h): host struct of device pointers for ic3_policy_step."""
     _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("nheads", C.c_int32), ("head_sizes", C.c_int32 * 4), ("mode_avg", C.c_int32),
                 ("comm_zero", C.c_int32), ("enc_wt", C.c_void_p), ("enc_bias", C.c_void_p), ("loc_table", C.c_void_p),
@@ -48,12 +57,8 @@ class Policy(C.Structure):
                 ("head_b", C.c_void_p), ("pass_index", C.c_int32), ("inner_pass", C.c_int32), ("gate_split", C.c_int32),
                 ("npasses", C.c_int32), ("lstm_wp3", C.c_void_p), ("c_wp_pass", C.c_void_p * 4), ("enc_bias_pass", C.c_void_p * 4)]
 
-    def __init__(self, *a, **kw):             # positional arguments start at the field behind struct_size
-        super().__init__(*((0,) + a if a else a), **kw)
-        self.struct_size = C.sizeof(self)
 
-
-class Episode(C.Structure):
+class Episode(_SizedStruct):
     """ic3_episode (include/ic3_rollout.h): episode buffers in, masks and reduced statistics out."""
     _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("E", C.c_int32), ("N", C.c_int32), ("auto_reset", C.c_int32),
                 ("forced_last", C.c_int32), ("gate_ones", C.c_int32), ("done", C.c_void_p), ("alive", C.c_void_p),
@@ -62,12 +67,8 @@ class Episode(C.Structure):
                 ("episode_mini_mask", C.c_void_p), ("live_after", C.c_void_p), ("stats", C.c_void_p),
                 ("scratch", C.c_void_p), ("counter", C.c_void_p)]
 
-    def __init__(self, *a, **kw):             # positional arguments start at the field behind struct_size
-        super().__init__(*((0,) + a if a else a), **kw)
-        self.struct_size = C.sizeof(self)
 
-
-class Bptt(C.Structure):
+class Bptt(_SizedStruct):
     """ic3_bptt (include/ic3_rollout.h): one window of the recorded-gates backward through time."""
     _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "mode_avg", "comm_zero",
                                                                         "detach_gap", "enc_first")] + \
@@ -79,7 +80,7 @@ class Bptt(C.Structure):
                 ("dxh_step", C.c_int64), ("two_chains", C.c_int32), ("gate_events", C.POINTER(C.c_void_p))]
 
 
-class RnnBptt(C.Structure):
+class RnnBptt(_SizedStruct):
     """ic3_rnn_bptt (include/ic3_rollout.h): one window of the tanh-recurrence baseline's backward through time."""
     _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "detach_gap", "enc_first",
                                                                         "enc_window")] + \
@@ -89,7 +90,7 @@ class RnnBptt(C.Structure):
                 ("wgrad_scratch", C.c_void_p)]
 
 
-class MlpBptt(C.Structure):
+class MlpBptt(_SizedStruct):
     """ic3_mlp_bptt (include/ic3_rollout.h): one window of the IC baseline's (models.MLP) backward."""
     _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "enc_first", "enc_window")] + \
                [("h", C.c_void_p), ("dhead", C.c_void_p), ("snaps", C.c_void_p), ("snap_words", C.c_int64), ("enc_wt", C.c_void_p),
@@ -98,7 +99,7 @@ class MlpBptt(C.Structure):
                 ("a2_grad", C.c_void_p), ("wgrad_scratch", C.c_void_p)]
 
 
-class CommnetBptt(C.Structure):
+class CommnetBptt(_SizedStruct):
     """ic3_commnet_bptt (include/ic3_rollout.h): one window of the non-recurrent CommNet module's backward."""
     _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "passes", "mode_avg", "comm_zero",
                                                                         "enc_first", "enc_window", "max_chunk_steps")] + \
@@ -295,6 +296,11 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def int32_array(values, n=None):
+    """A C array of int32 from a Python sequence (the head_sizes argument of the policy entry points); n: its length, zero-filled
+    behind the values (ic3_policy.head_sizes)."""
+    return (C.c_int32 * (len(values) if n is None else n))(*[int(a) for a in values])
+
+
 def stream():
-    import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -52,6 +52,7 @@ class _BatchedEnv(object):
         self.dispatch_events = False   # step_timer pairs stamped by the dispatch (DispatchEvent) instead of records
         self.out = None           # optional {'reward','done','alive','is_completed'} output tensors for step()
         self._last = None
+        self._scratch = {}        # float32 work buffers of the encoder backward, by (kind, H): _work()
 
     # --- handle ---------------------------------------------------------------------------------
     def _finish_init(self, handle, device):
@@ -146,20 +147,24 @@ class _BatchedEnv(object):
         check(_lib.lib().ic3_env_observe(self._h, ptr(self._obs), stream()))
         return self._obs
 
+    def _encode_args(self, name, weight_t, out):
+        """What encode() and encode_at() share: the weight check, the output and its row stride.  -> (H, out, ldo)"""
+        self._require()
+        H = weight_t.shape[1]
+        if weight_t.shape[0] != self.obs_dim or not weight_t.is_contiguous() or weight_t.dtype != torch.float32:
+            raise ValueError("%s: weight_t must be a contiguous float32 (obs_dim, H) tensor" % name)
+        if out is None:
+            out = torch.empty((self.nenvs, self.nagents_env, H), dtype=torch.float32, device=self.device)
+        return H, out, H if out.dim() == 3 else out.stride(0)     # (E*N, H) column slice of a wider buffer: row stride
+
     def encode(self, weight_t, bias, out=None, loc_table=None):
         """encoder(obs(current state)) as a sparse gather (ic3_env_encode): weight_t = encoder.weight.t()
         contiguous (obs_dim, H), bias (H,) -> (E, N, H) float32.  Equals self.observe() @ weight_t + bias.
         loc_table = self.encode_table(weight_t) (valid while the weights are unchanged) makes it cheaper."""
-        self._require()
-        H = weight_t.shape[1]
-        if weight_t.shape[0] != self.obs_dim or not weight_t.is_contiguous() or weight_t.dtype != torch.float32:
-            raise ValueError("encode: weight_t must be a contiguous float32 (obs_dim, H) tensor")
+        H, out, ldo = self._encode_args("encode", weight_t, out)
         if loc_table is not None and (tuple(loc_table.shape) != (self.dims.grid_h * self.dims.grid_w, H)
                                       or not loc_table.is_contiguous() or loc_table.dtype != torch.float32):
             raise ValueError("encode: loc_table must be the contiguous float32 (grid_h*grid_w, H) tensor of encode_table")
-        if out is None:
-            out = torch.empty((self.nenvs, self.nagents_env, H), dtype=torch.float32, device=self.device)
-        ldo = H if out.dim() == 3 else out.stride(0)     # (E*N, H) column slice of a wider buffer: row stride
         check(_lib.lib().ic3_env_encode(self._h, ptr(weight_t), ptr(bias), ptr(loc_table), ptr(out), ldo, H, stream()))
         return out
 
@@ -174,15 +179,8 @@ class _BatchedEnv(object):
     def encode_at(self, snap, weight_t, bias, out=None, loc_table=None):
         """encode() for the state held in `snap` (a snapshot() tensor; None = the live state) — ic3_env_encode_at: the
         update half re-evaluates the encoder of a past step from its state snapshot."""
-        self._require()
-        H = weight_t.shape[1]
-        if weight_t.shape[0] != self.obs_dim or not weight_t.is_contiguous() or weight_t.dtype != torch.float32:
-            raise ValueError("encode_at: weight_t must be a contiguous float32 (obs_dim, H) tensor")
-        if out is None:
-            out = torch.empty((self.nenvs, self.nagents_env, H), dtype=torch.float32, device=self.device)
-        ldo = H if out.dim() == 3 else out.stride(0)
-        check(_lib.lib().ic3_env_encode_at(self._h, ptr(snap) if snap is not None else None, ptr(weight_t), ptr(bias),
-                                           ptr(loc_table), ptr(out), ldo, H, stream()))
+        H, out, ldo = self._encode_args("encode_at", weight_t, out)
+        check(_lib.lib().ic3_env_encode_at(self._h, ptr(snap), ptr(weight_t), ptr(bias), ptr(loc_table), ptr(out), ldo, H, stream()))
         return out
 
     def encode_table(self, weight_t):
@@ -201,6 +199,22 @@ class _BatchedEnv(object):
         check(_lib.lib().ic3_env_snapshot(self._h, ptr(out), stream()))
         return out
 
+    def _work(self, kind, H, query):
+        """The float32 work buffer `kind` for hid_size H, created on first use with the size the library's `query` answers (an
+        empty tensor where it answers 0)."""
+        key = (kind, H)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty((check(int(query(self._h, H))),), dtype=torch.float32, device=self.device)
+        return self._scratch[key]
+
+    def _encb_work(self, H):
+        return self._work('encb', H, _lib.lib().ic3_env_encode_backward_work)
+
+    def _enc_grads(self, H, want_bias):
+        """The outputs of the encoder backward: (dWt (obs_dim, H), dbias (H,) or None)."""
+        dwt = torch.empty((self.obs_dim, H), dtype=torch.float32, device=self.device)
+        return dwt, torch.empty((H,), dtype=torch.float32, device=self.device) if want_bias else None
+
     def encode_backward(self, grad_out, snap=None, want_bias=True):
         """Gradient of encode() w.r.t. (weight_t, bias) for the state in `snap` (None = current state):
         returns (obs^T @ grad_out as (obs_dim, H), grad_out.sum over rows as (H,))  — ic3_env_encode_backward."""
@@ -209,32 +223,10 @@ class _BatchedEnv(object):
         g = grad_out.reshape(-1, H)
         if g.dtype != torch.float32 or g.stride(1) != 1 or g.shape[0] != self.nenvs * self.nagents_env:
             raise ValueError("encode_backward: grad_out must be float32 (E*N, H) with unit inner stride")
-        key = ('encb', H)
-        work = self._scratch.get(key) if hasattr(self, '_scratch') else None
-        if work is None:
-            if not hasattr(self, '_scratch'):
-                self._scratch = {}
-            n = _lib.lib().ic3_env_encode_backward_work(self._h, H)
-            if n < 0:
-                check(int(n))
-            work = self._scratch[key] = torch.empty((n,), dtype=torch.float32, device=self.device)
-        dwt = torch.empty((self.obs_dim, H), dtype=torch.float32, device=self.device)
-        dbias = torch.empty((H,), dtype=torch.float32, device=self.device) if want_bias else None
-        check(_lib.lib().ic3_env_encode_backward(self._h, ptr(snap) if snap is not None else None, ptr(g), g.stride(0), H,
-                                                 ptr(dwt), ptr(dbias) if want_bias else None, ptr(work), stream()))
+        work = self._encb_work(H)
+        dwt, dbias = self._enc_grads(H, want_bias)
+        check(_lib.lib().ic3_env_encode_backward(self._h, ptr(snap), ptr(g), g.stride(0), H, ptr(dwt), ptr(dbias), ptr(work), stream()))
         return dwt, dbias
-
-    def _encb_work(self, H):
-        key = ('encb', H)
-        if not hasattr(self, '_scratch'):
-            self._scratch = {}
-        work = self._scratch.get(key)
-        if work is None:
-            n = _lib.lib().ic3_env_encode_backward_work(self._h, H)
-            if n < 0:
-                check(int(n))
-            work = self._scratch[key] = torch.empty((n,), dtype=torch.float32, device=self.device)
-        return work
 
     def encode_backward_accumulate(self, grad_out, snap, first):
         """encode_backward over several states with ONE expansion at the end (ic3_env_encode_backward_accumulate): adds this
@@ -245,8 +237,8 @@ class _BatchedEnv(object):
         g = grad_out.reshape(-1, H) if grad_out.is_contiguous() else grad_out
         if g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1 or g.shape[0] != self.nenvs * self.nagents_env:
             raise ValueError("encode_backward_accumulate: grad_out must be float32 (E*N, H) with unit inner stride")
-        rc = _lib.lib().ic3_env_encode_backward_accumulate(self._h, ptr(snap) if snap is not None else None, ptr(g), g.stride(0),
-                                                           H, ptr(self._encb_work(H)), int(bool(first)), stream())
+        rc = _lib.lib().ic3_env_encode_backward_accumulate(self._h, ptr(snap), ptr(g), g.stride(0), H, ptr(self._encb_work(H)),
+                                                           int(bool(first)), stream())
         if rc == -38:
             return False
         check(rc)
@@ -255,25 +247,16 @@ class _BatchedEnv(object):
     def encode_backward_finish(self, H, want_bias=True):
         """(dWt (obs_dim, H), dbias (H,)) of everything accumulated since the `first` encode_backward_accumulate call."""
         self._require()
-        dwt = torch.empty((self.obs_dim, H), dtype=torch.float32, device=self.device)
-        dbias = torch.empty((H,), dtype=torch.float32, device=self.device) if want_bias else None
-        check(_lib.lib().ic3_env_encode_backward_finish(self._h, H, ptr(dwt), ptr(dbias) if want_bias else None,
-                                                        ptr(self._encb_work(H)), stream()))
+        dwt, dbias = self._enc_grads(H, want_bias)
+        check(_lib.lib().ic3_env_encode_backward_finish(self._h, H, ptr(dwt), ptr(dbias), ptr(self._encb_work(H)), stream()))
         return dwt, dbias
 
     def encode_window_work(self, H):
         """Scratch of the window form of the encoder backward (ic3_env_encode_backward_window), or None when this configuration
         has none."""
         self._require()
-        key = ('encw', H)
-        if not hasattr(self, '_scratch'):
-            self._scratch = {}
-        if key not in self._scratch:
-            n = _lib.lib().ic3_env_encode_backward_window_work(self._h, H)
-            if n < 0:
-                check(int(n))
-            self._scratch[key] = torch.empty((n,), dtype=torch.float32, device=self.device) if n > 0 else None
-        return self._scratch[key]
+        work = self._work('encw', H, _lib.lib().ic3_env_encode_backward_window_work)
+        return work if work.numel() else None
 
     def encode_backward_window(self, grad_out, snaps, H, first=True):
         """Stage 1 of the encoder backward over a window of states in one launch: grad_out (T, E*N, >= H) float32 with unit inner
@@ -290,29 +273,21 @@ class _BatchedEnv(object):
     def encode_backward_window_finish(self, H, want_bias=True):
         """(dWt (obs_dim, H), dbias (H,)) of what the window form accumulated."""
         self._require()
-        dwt = torch.empty((self.obs_dim, H), dtype=torch.float32, device=self.device)
-        dbias = torch.empty((H,), dtype=torch.float32, device=self.device) if want_bias else None
-        check(_lib.lib().ic3_env_encode_backward_window_finish(self._h, H, ptr(dwt), ptr(dbias) if want_bias else None,
-                                                               ptr(self.encode_window_work(H)), stream()))
+        dwt, dbias = self._enc_grads(H, want_bias)
+        check(_lib.lib().ic3_env_encode_backward_window_finish(self._h, H, ptr(dwt), ptr(dbias), ptr(self.encode_window_work(H)),
+                                                               stream()))
         return dwt, dbias
 
     def encode_backward_window_finish_ordered(self, H, want_bias=True):
         """encode_backward_window_finish with every sum in a fixed order (ic3_env_encode_backward_window_finish_ordered): the
         same (dWt, dbias), identical run to run."""
         self._require()
-        key = ('encw_fold', H)
-        if not hasattr(self, '_scratch'):
-            self._scratch = {}
-        if key not in self._scratch:
-            n = _lib.lib().ic3_env_encode_backward_window_finish_scratch(self._h, H)
-            if n <= 0:
-                check(int(n) if n < 0 else -38)
-            self._scratch[key] = torch.empty((n,), dtype=torch.float32, device=self.device)
-        dwt = torch.empty((self.obs_dim, H), dtype=torch.float32, device=self.device)
-        dbias = torch.empty((H,), dtype=torch.float32, device=self.device) if want_bias else None
-        check(_lib.lib().ic3_env_encode_backward_window_finish_ordered(self._h, H, ptr(dwt), ptr(dbias) if want_bias else None,
-                                                                      ptr(self.encode_window_work(H)), ptr(self._scratch[key]),
-                                                                      stream()))
+        fold = self._work('encw_fold', H, _lib.lib().ic3_env_encode_backward_window_finish_scratch)
+        if not fold.numel():
+            check(-38)                                  # this configuration has no ordered finish
+        dwt, dbias = self._enc_grads(H, want_bias)
+        check(_lib.lib().ic3_env_encode_backward_window_finish_ordered(self._h, H, ptr(dwt), ptr(dbias), ptr(self.encode_window_work(H)),
+                                                                      ptr(fold), stream()))
         return dwt, dbias
 
     def set_auto_reset(self, max_steps):
@@ -325,8 +300,7 @@ class _BatchedEnv(object):
     def set_record_out(self, gates, xh=None):
         """One-shot (ic3_env_set_record_out): the next ic3_policy_step also stores its cell's activated gates (R, 4H) there
         and, with `xh` (R, 2H), the inp half of its rows."""
-        check(_lib.lib().ic3_env_set_record_out(self._h, ptr(gates) if gates is not None else None,
-                                                ptr(xh) if xh is not None else None))
+        check(_lib.lib().ic3_env_set_record_out(self._h, ptr(gates), ptr(xh)))
 
     def set_hidden_out(self, h_out, c_out):
         """One-shot (ic3_env_set_hidden_out): the next ic3_policy_step writes h', c' there instead of in place."""
@@ -364,30 +338,26 @@ class _BatchedEnv(object):
         o = self.out or {}
         reward, done = o.get('reward', self._reward), o.get('done', self._done)
         alive, completed = o.get('alive', self._alive), o.get('is_completed', self._completed)
-        if self.obs_timer is None and observe:
-            check(_lib.lib().ic3_env_step(self._h, ptr(a), ptr(self._obs), ptr(reward), ptr(done),
-                                          ptr(alive), ptr(completed), stream()))
-        else:
-            check(_lib.lib().ic3_env_step(self._h, ptr(a), None, ptr(reward), ptr(done),
-                                          ptr(alive), ptr(completed), stream()))
-            if observe:
-                self.observe_timed()
+        fused_obs = self.obs_timer is None and observe      # the step launch writes the observation itself
+        check(_lib.lib().ic3_env_step(self._h, ptr(a), ptr(self._obs) if fused_obs else None, ptr(reward), ptr(done),
+                                      ptr(alive), ptr(completed), stream()))
+        if observe and not fused_obs:
+            self.observe_timed()
         self._last = (reward, done, alive, completed)
         return self._obs, reward, done
 
     def observe_timed(self, snap=None):
         """The obs-assembly launch (of the current state, or of a snapshot), bracketed by HIP events on the launch
         stream when `obs_timer` is a list."""
-        sp = ptr(snap) if snap is not None else None
-        if self.obs_timer is None:
-            check(_lib.lib().ic3_env_observe_at(self._h, sp, ptr(self._obs), stream()))
-            return self._obs
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream())
-        check(_lib.lib().ic3_env_observe_at(self._h, sp, ptr(self._obs), stream()))
-        e1.record(torch.cuda.current_stream())
-        self.obs_timer.append((e0, e1))
+        timed = self.obs_timer is not None
+        if timed:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(torch.cuda.current_stream())
+        check(_lib.lib().ic3_env_observe_at(self._h, ptr(snap), ptr(self._obs), stream()))
+        if timed:
+            e1.record(torch.cuda.current_stream())
+            self.obs_timer.append((e0, e1))
         return self._obs
 
     has_terminal_reward = False                    # reward_terminal() is identically zero: the Trainer skips the add

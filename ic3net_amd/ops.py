@@ -1,13 +1,46 @@
 """torch-facing wrappers of the two custom HIP policy ops (include/ic3_rollout.h).  No CPU fallback."""
+import ctypes as C
+from functools import partial
+
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream
+from ._lib import check, int32_array, ptr, stream
 
 
 def _need_cuda(t, name):
     if not t.is_cuda:
         raise _lib.IC3Error("%s: expected a CUDA (ROCm) tensor — the HIP op has no CPU fallback" % name)
+
+
+def _dense(t, shape=None, dtype=None, none_ok=False):
+    """What the wrappers assert of a buffer: a contiguous tensor, of `dtype` when given, of `shape` when given (a tuple: the
+    shape itself; an int: that many elements).  None passes only where the argument is optional (`none_ok`)."""
+    if t is None:
+        return none_ok
+    if not t.is_contiguous() or (dtype is not None and t.dtype != dtype):
+        return False
+    if shape is None:
+        return True
+    return t.numel() == shape if isinstance(shape, int) else t.shape == shape
+
+
+_f32 = partial(_dense, dtype=torch.float32)
+_i32 = partial(_dense, dtype=torch.int32)
+
+
+def _mask(m, R, none_ok=True):
+    """An int32 row mask (alive / gate) of R rows, or None: nobody masked."""
+    return _i32(m, R, none_ok=none_ok)
+
+
+def _set_ptrs(struct, tensors=(), **optional):
+    """struct.<field> = the tensor's device pointer for every field named: `tensors`, a dict, holds the arguments that must be
+    tensors; the keyword ones may be None (-> NULL)."""
+    for name in tensors:
+        setattr(struct, name, tensors[name].data_ptr())
+    for name, t in optional.items():
+        setattr(struct, name, None if t is None else t.data_ptr())
 
 
 class _CommMaskedMean(torch.autograd.Function):
@@ -75,11 +108,9 @@ def comm_masked_mean_raw(h, alive, comm_action, mode_avg, mask_self, out=None, a
         out = torch.empty((E, N, H), dtype=torch.float32, device=h.device)
     if addend is not None:
         ak, lda = _rows(addend, H)
-        if row_scale is not None:
-            assert row_scale.is_contiguous() and row_scale.dtype == torch.float32 and row_scale.numel() == E * N
-        check(_lib.lib().ic3_comm_masked_mean_add(ptr(hk), ldh, ptr(alive), ptr(comm_action), ptr(ak), lda,
-                                                  ptr(row_scale) if row_scale is not None else None, ptr(out), E, N, H,
-                                                  int(mode_avg), int(mask_self), stream()))
+        assert _f32(row_scale, E * N, none_ok=True)
+        check(_lib.lib().ic3_comm_masked_mean_add(ptr(hk), ldh, ptr(alive), ptr(comm_action), ptr(ak), lda, ptr(row_scale), ptr(out),
+                                                  E, N, H, int(mode_avg), int(mask_self), stream()))
         return out
     assert row_scale is None, "row_scale comes with an addend"
     check(_lib.lib().ic3_comm_masked_mean(ptr(hk), ldh, ptr(alive), ptr(comm_action), ptr(out), E, N, H,
@@ -92,7 +123,7 @@ def lstm_cell_(gates, c, h_out):
     with unit column stride (may be a column slice of a wider buffer)."""
     _need_cuda(gates, "lstm_cell")
     R, H = c.shape
-    assert gates.is_contiguous() and c.is_contiguous() and h_out.stride(1) == 1
+    assert _dense(gates) and _dense(c) and h_out.stride(1) == 1
     check(_lib.lib().ic3_lstm_cell(ptr(gates), ptr(c), ptr(h_out), h_out.stride(0), R, H, stream()))
     return h_out, c
 
@@ -108,14 +139,10 @@ def lstm_cell_backward(gates, c_prev, dh, dc, dgates, dc_prev, dbias_partials=No
     _need_cuda(gates, "lstm_cell_backward")
     R, H = c_prev.shape
     for t in (gates, c_prev, dh, dgates, dc_prev):
-        assert t.is_contiguous() and t.dtype == torch.float32
-    if dbias_partials is not None:
-        assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (LSTM_BWD_MAX_PARTIALS, 4 * H)
-    n = _lib.lib().ic3_lstm_cell_backward(ptr(gates), ptr(c_prev), ptr(dh), ptr(dc) if dc is not None else None,
-                                          ptr(dgates), ptr(dc_prev),
-                                          ptr(dbias_partials) if dbias_partials is not None else None, R, H, stream())
-    if n < 0:
-        check(n)
+        assert _f32(t)
+    assert _dense(dbias_partials, (LSTM_BWD_MAX_PARTIALS, 4 * H), none_ok=True)
+    n = check(_lib.lib().ic3_lstm_cell_backward(ptr(gates), ptr(c_prev), ptr(dh), ptr(dc), ptr(dgates), ptr(dc_prev),
+                                                ptr(dbias_partials), R, H, stream()))
     return dbias_partials[:n] if dbias_partials is not None else None
 
 
@@ -123,14 +150,21 @@ def commnet_forward_supported(H, N):
     return bool(_lib.lib().ic3_commnet_forward_supported(int(H), int(N)))
 
 
+def _commnet_pack_passes(entry, c_weights, f_weights, out):
+    """out[i] <- entry([C_i | F_i]) for every communication pass i."""
+    H = c_weights[0].shape[0]
+    for i in range(len(c_weights)):
+        check(entry(ptr(c_weights[i].detach().contiguous().float()), ptr(f_weights[i].detach().contiguous().float()), ptr(out[i]), H,
+                    stream()))
+    return out
+
+
 def commnet_pack(c_weights, f_weights, c_biases, f_biases):
     """Per-pass [C_i | F_i] in the layout ic3_commnet_forward streams + the summed biases: lists of (H,H) / (H,) tensors."""
     _need_cuda(c_weights[0], "commnet_pack")
     H, P, dev = c_weights[0].shape[0], len(c_weights), c_weights[0].device
-    wp = torch.empty((P, 2 * H * H), dtype=torch.float32, device=dev)
-    for i in range(P):
-        check(_lib.lib().ic3_commnet_pack(ptr(c_weights[i].detach().contiguous().float()),
-                                          ptr(f_weights[i].detach().contiguous().float()), ptr(wp[i]), H, stream()))
+    wp = _commnet_pack_passes(_lib.lib().ic3_commnet_pack, c_weights, f_weights,
+                              torch.empty((P, 2 * H * H), dtype=torch.float32, device=dev))
     bias = torch.stack([(c_biases[i] + f_biases[i]).detach().float() for i in range(P)]).contiguous()
     return wp, bias
 
@@ -141,28 +175,23 @@ def commnet_pack_split(c_weights, f_weights):
     H, P, dev = c_weights[0].shape[0], len(c_weights), c_weights[0].device
     if H % 32:
         return None
-    wp3 = torch.empty((P, 3 * H * H), dtype=torch.float32, device=dev)
-    for i in range(P):
-        check(_lib.lib().ic3_commnet_pack_split(ptr(c_weights[i].detach().contiguous().float()),
-                                                ptr(f_weights[i].detach().contiguous().float()), ptr(wp3[i]), H, stream()))
-    return wp3
+    return _commnet_pack_passes(_lib.lib().ic3_commnet_pack_split, c_weights, f_weights,
+                                torch.empty((P, 3 * H * H), dtype=torch.float32, device=dev))
 
 
 def commnet_forward(enc, E, N, wp, bias, head_w, head_b, head_sizes, mode_avg, comm_zero, alive_in, comm_in, out=None,
                     h_out=None, wp3=None):
     """The non-recurrent CommNet module after the encoder, every communication pass in one launch (ic3_commnet_forward):
     enc (E*N, H) = encoder(obs) incl. bias -> out (E*N, OT) = [log-probs of every head | value]."""
-    import ctypes as C
     _need_cuda(enc, "commnet_forward")
     R, H = enc.shape
-    assert R == E * N and enc.is_contiguous() and enc.dtype == torch.float32
-    for m in (alive_in, comm_in):
-        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
+    assert R == E * N and _f32(enc)
+    assert _mask(alive_in, R) and _mask(comm_in, R)
     OT = sum(int(a) for a in head_sizes) + 1
     if out is None:
         out = torch.empty((R, OT), dtype=torch.float32, device=enc.device)
-    sizes = (C.c_int32 * len(head_sizes))(*[int(a) for a in head_sizes])
-    assert wp3 is None or (wp3.is_contiguous() and tuple(wp3.shape) == (wp.shape[0], 3 * H * H))
+    sizes = int32_array(head_sizes)
+    assert _dense(wp3, (wp.shape[0], 3 * H * H), none_ok=True)
     check(_lib.lib().ic3_commnet_forward(ptr(enc), E, N, H, wp.shape[0], ptr(wp), ptr(wp3), ptr(bias), ptr(head_w), ptr(head_b), sizes,
                                          len(head_sizes), int(bool(mode_avg)), int(bool(comm_zero)), ptr(alive_in),
                                          ptr(comm_in), ptr(out), ptr(h_out), stream()))
@@ -178,16 +207,12 @@ def commnet_step(env, cn, H, head_sizes, mode_avg, comm_zero, alive_in, comm_in,
     """One whole rollout iteration of the NON-recurrent module (sparse encoder -> communication passes -> heads -> draws ->
     env.step, + the dense obs rows of the state acted on) in one launch — ic3_commnet_step.  `cn`: the module's derived
     weights (wt, enc_bias, loc_table, wp, bias, w_heads, b_heads; wp3 = the split planes or None: the fp32 instruction)."""
-    import ctypes as C
     _need_cuda(out, "commnet_step")
     R = out.shape[0]
-    assert out.is_contiguous() and action.is_contiguous() and action.dtype == torch.int32
-    assert action.numel() == len(head_sizes) * R and out.shape[1] == sum(int(a) for a in head_sizes) + 1
-    for m in (alive_in, comm_in):
-        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
-    for v in (h_in, h_out):
-        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == R * int(H))
-    sizes = (C.c_int32 * len(head_sizes))(*[int(a) for a in head_sizes])
+    assert _dense(out) and _i32(action, len(head_sizes) * R) and out.shape[1] == sum(int(a) for a in head_sizes) + 1
+    assert _mask(alive_in, R) and _mask(comm_in, R)
+    assert _f32(h_in, R * int(H), none_ok=True) and _f32(h_out, R * int(H), none_ok=True)
+    sizes = int32_array(head_sizes)
     check(_lib.lib().ic3_commnet_step(env._h, ptr(cn['wt']), ptr(cn['enc_bias']), ptr(cn['loc_table']), int(H),
                                       cn['wp'].shape[0], ptr(cn['wp']), ptr(cn.get('wp3')), ptr(cn['bias']), ptr(cn['w_heads']),
                                       ptr(cn['b_heads']),
@@ -205,42 +230,26 @@ def lstm_gates_backward(xh, lstm_wp, bias, c_prev, dh, dc, dgates, dc_prev, dbia
                         h_prev=None, lstm_wp3=None, lstm_wp3_bwd=None, dxh=None):
     """Gate recompute + LSTM cell backward in one launch (ic3_lstm_gates_backward): xh (R,2H) = [inp | h_prev] rows (unit
     column stride; with h_prev (R,H) given the launch fills the h half of xh from it), lstm_wp = policy_step_pack's 'ps_l_wp', bias (4H,) = b_ih + b_hh; c_prev, dh, dc (or None) (R,H) ->
-    dgates (R,4H), dc_prev (R,H; may alias dc).  dbias_partials: (ceil(R/64), 4H), written (or added to: `accumulate`)."""
+    dgates (R,4H), dc_prev (R,H; may alias dc).  dbias_partials: (ceil(R/64), 4H), written (or added to: `accumulate`).
+    lstm_wp3: the split gate product.  dxh (R,2H) with lstm_wp3 and lstm_wp3_bwd: + the input gradient [d inp | d h_prev] =
+    dgates . [W_ih | W_hh] in the same launch (ic3_lstm_gates_backward_dx)."""
     _need_cuda(xh, "lstm_gates_backward")
     R, H = c_prev.shape
     assert xh.dtype == torch.float32 and xh.stride(1) == 1 and xh.shape == (R, 2 * H)
     for t in (c_prev, dh, dgates, dc_prev, bias, lstm_wp):
-        assert t.is_contiguous() and t.dtype == torch.float32
-    tiles = (R + 63) // 64
-    if dbias_partials is not None:
-        assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (tiles, 4 * H)
-    if h_prev is not None:
-        assert h_prev.is_contiguous() and h_prev.dtype == torch.float32 and tuple(h_prev.shape) == (R, H)
-    if dxh is not None:       # + the input gradient [d inp | d h_prev] = dgates . [W_ih | W_hh] in the same launch
-        assert lstm_wp3 is not None and lstm_wp3_bwd is not None and dxh.is_contiguous() and tuple(dxh.shape) == (R, 2 * H)
-        n = _lib.lib().ic3_lstm_gates_backward_dx(ptr(xh), xh.stride(0), ptr(h_prev) if h_prev is not None else None, ptr(lstm_wp),
-                                                  ptr(lstm_wp3), ptr(lstm_wp3_bwd), ptr(bias), ptr(c_prev), ptr(dh),
-                                                  ptr(dc) if dc is not None else None, ptr(dgates), ptr(dc_prev),
-                                                  ptr(dbias_partials) if dbias_partials is not None else None,
-                                                  int(bool(accumulate)), ptr(dxh), R, H, stream())
-        if n < 0:
-            check(n)
-        return n
-    n = _lib.lib().ic3_lstm_gates_backward(ptr(xh), xh.stride(0), ptr(h_prev) if h_prev is not None else None, ptr(lstm_wp),
-                                           ptr(lstm_wp3) if lstm_wp3 is not None else None,   # split gate product
-                                           ptr(bias), ptr(c_prev), ptr(dh),
-                                           ptr(dc) if dc is not None else None, ptr(dgates), ptr(dc_prev),
-                                           ptr(dbias_partials) if dbias_partials is not None else None,
-                                           int(bool(accumulate)), R, H, stream())
-    if n < 0:
-        check(n)
-    return n
+        assert _f32(t)
+    assert _dense(dbias_partials, ((R + 63) // 64, 4 * H), none_ok=True)
+    assert _f32(h_prev, (R, H), none_ok=True)
+    entry, bwd_planes, dx = _lib.lib().ic3_lstm_gates_backward, (), ()
+    if dxh is not None:
+        assert lstm_wp3 is not None and lstm_wp3_bwd is not None and _dense(dxh, (R, 2 * H))
+        entry, bwd_planes, dx = _lib.lib().ic3_lstm_gates_backward_dx, (ptr(lstm_wp3_bwd),), (ptr(dxh),)
+    return check(entry(ptr(xh), xh.stride(0), ptr(h_prev), ptr(lstm_wp), ptr(lstm_wp3), *bwd_planes, ptr(bias), ptr(c_prev), ptr(dh),
+                       ptr(dc), ptr(dgates), ptr(dc_prev), ptr(dbias_partials), int(bool(accumulate)), *dx, R, H, stream()))
 
 
 def _rowvec(v, R):
-    if v is None:
-        return None
-    assert v.is_contiguous() and v.dtype == torch.float32 and v.numel() == R
+    assert _f32(v, R, none_ok=True)
     return ptr(v)
 
 
@@ -254,35 +263,32 @@ def lstm_gates_backward_given(gates, c_prev, dh, dc, dgates, dc_prev, dbias_part
     zeros (a detach point of the recurrence; no buffer is read) — dh None needs dhead, row_keep needs dc."""
     _need_cuda(gates, "lstm_gates_backward_given")
     R, H = c_prev.shape
-    for t in (gates, c_prev, dgates, dc_prev) + tuple(v for v in (dh, dc) if v is not None):
-        assert t.is_contiguous() and t.dtype == torch.float32
+    for t in (gates, c_prev, dgates, dc_prev):
+        assert _f32(t)
+    assert _f32(dh, none_ok=True) and _f32(dc, none_ok=True)
     assert dh is not None or dhead is not None      # (dh None = zeros: a detach point, the heads' share alone reaches the cell)
     assert tuple(gates.shape) == (R, 4 * H) and tuple(dgates.shape) == (R, 4 * H)
-    tiles = (R + 63) // 64
-    if dbias_partials is not None:
-        assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (tiles, 4 * H)
+    assert _dense(dbias_partials, ((R + 63) // 64, 4 * H), none_ok=True)
+    ldxh = 0
     if xh is not None:
         assert h_prev is not None and xh.dtype == torch.float32 and xh.stride(1) == 1 and xh.shape == (R, 2 * H)
-        assert h_prev.is_contiguous() and tuple(h_prev.shape) == (R, H)
+        assert _dense(h_prev, (R, H))
+        ldxh = xh.stride(0)
     if dxh is not None:
-        assert lstm_wp3_bwd is not None and dxh.is_contiguous() and tuple(dxh.shape) == (R, 2 * H)
+        assert lstm_wp3_bwd is not None and _dense(dxh, (R, 2 * H))
     OT = 0
     if dhead is not None:
         OT = dhead.shape[1]
-        assert w_heads is not None and dhead.is_contiguous() and dhead.dtype == torch.float32 and dhead.shape[0] == R
-        assert w_heads.is_contiguous() and w_heads.dtype == torch.float32 and tuple(w_heads.shape) == (OT, H)
-    n = _lib.lib().ic3_lstm_gates_backward_given(ptr(gates), ptr(xh) if xh is not None else None, xh.stride(0) if xh is not None else 0,
-                                                 ptr(h_prev) if xh is not None else None,
-                                                 ptr(lstm_wp3_bwd) if dxh is not None else None, ptr(c_prev), ptr(dh),
-                                                 ptr(dc) if dc is not None else None, ptr(dgates), ptr(dc_prev),
-                                                 ptr(dbias_partials) if dbias_partials is not None else None,
-                                                 int(bool(accumulate)), ptr(dxh) if dxh is not None else None,
-                                                 _rowvec(row_live, R), _rowvec(row_keep, R),
-                                                 ptr(dhead) if dhead is not None else None,
-                                                 ptr(w_heads) if dhead is not None else None, OT, R, H, stream())
-    if n < 0:
-        check(n)
-    return n
+        assert w_heads is not None and _f32(dhead) and dhead.shape[0] == R
+        assert _f32(w_heads, (OT, H))
+    # three arguments count only beside another one: without it the library is handed NULL whatever the caller passed
+    h_prev = h_prev if xh is not None else None                    # (copied into xh)
+    lstm_wp3_bwd = lstm_wp3_bwd if dxh is not None else None       # (the product that fills dxh)
+    w_heads = w_heads if dhead is not None else None               # (dhead's weights)
+    return check(_lib.lib().ic3_lstm_gates_backward_given(ptr(gates), ptr(xh), ldxh, ptr(h_prev), ptr(lstm_wp3_bwd), ptr(c_prev), ptr(dh),
+                                                          ptr(dc), ptr(dgates), ptr(dc_prev), ptr(dbias_partials),
+                                                          int(bool(accumulate)), ptr(dxh), _rowvec(row_live, R), _rowvec(row_keep, R),
+                                                          ptr(dhead), ptr(w_heads), OT, R, H, stream()))
 
 
 def comm_backward_partials(E, N):
@@ -297,18 +303,14 @@ def comm_backward(dxh, h_prev, alive, gate, c_weight, dh_out, dcw_partials, E, N
     _need_cuda(dxh, "comm_backward")
     R, H2 = dxh.shape
     H = H2 // 2
-    assert R == E * N and dxh.is_contiguous() and dxh.dtype == torch.float32 and dh_out.is_contiguous() and tuple(dh_out.shape) == (R, H)
+    assert R == E * N and _f32(dxh) and _dense(dh_out, (R, H))
     if not comm_zero:
-        assert h_prev.is_contiguous() and tuple(h_prev.shape) == (R, H) and c_weight.is_contiguous() and tuple(c_weight.shape) == (H, H)
-        assert dcw_partials.is_contiguous() and tuple(dcw_partials.shape) == (comm_backward_partials(E, N), H, H)
-        for m in (alive, gate):
-            assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
-    n = _lib.lib().ic3_comm_backward(ptr(dxh), 2 * H, ptr(h_prev), ptr(alive), ptr(gate), ptr(c_weight), _rowvec(out_scale, R),
-                                     ptr(dh_out), ptr(dcw_partials), int(bool(accumulate)), E, N, H, int(bool(mode_avg)),
-                                     int(bool(comm_zero)), stream())
-    if n < 0:
-        check(n)
-    return n
+        assert _dense(h_prev, (R, H)) and _dense(c_weight, (H, H))
+        assert _dense(dcw_partials, (comm_backward_partials(E, N), H, H))
+        assert _mask(alive, R) and _mask(gate, R)
+    return check(_lib.lib().ic3_comm_backward(ptr(dxh), 2 * H, ptr(h_prev), ptr(alive), ptr(gate), ptr(c_weight), _rowvec(out_scale, R),
+                                              ptr(dh_out), ptr(dcw_partials), int(bool(accumulate)), E, N, H, int(bool(mode_avg)),
+                                              int(bool(comm_zero)), stream()))
 
 
 def _scratch(work, key, n, device):
@@ -331,10 +333,9 @@ def lstm_weight_grad(inp, h_prev, dgates, dW, row_live=None, accumulate=True, wo
     Q = dgates.numel() // (4 * H)
     inp2 = inp.reshape(Q, inp.shape[-1])
     assert inp2.stride(1) == 1 and inp2.shape[1] >= H and inp2.dtype == torch.float32
-    assert h_prev.is_contiguous() and h_prev.numel() == Q * H and dgates.is_contiguous() and dgates.dtype == torch.float32
-    assert dW.is_contiguous() and tuple(dW.shape) == (2 * H, 4 * H)
-    if row_live is not None:
-        assert row_live.is_contiguous() and row_live.dtype == torch.float32 and row_live.numel() == Q
+    assert _dense(h_prev, Q * H) and _f32(dgates)
+    assert _dense(dW, (2 * H, 4 * H))
+    assert _f32(row_live, Q, none_ok=True)
     n = int(_lib.lib().ic3_lstm_weight_grad_wide_scratch_floats(Q, H, inp2.stride(0)))
     if n == 0:
         raise NotImplementedError("lstm_weight_grad: hid_size 64 / 128 / 256")
@@ -364,6 +365,31 @@ def record_xh_width(H):
     return H if H == 256 else 2 * H
 
 
+# ---- what the four window backwards (ic3_bptt_backward, ic3_rnn_backward_wide, ic3_mlp_backward_wide, ic3_commnet_backward) share
+def _window_inputs(dhead, snaps, T, R):
+    """The checks of dhead (T, R, OT) and of the state snapshots snaps (>= T, words); returns OT."""
+    OT = dhead.shape[-1]
+    assert _f32(dhead, T * R * OT)
+    assert _i32(snaps) and snaps.shape[0] >= T
+    return OT
+
+
+def _enc_work(env, H, window):
+    """Device pointer of the encoder backward's partial sums: the window form's, or the per-step form's."""
+    return (env.encode_window_work(H) if window else env._encb_work(H)).data_ptr()
+
+
+def _a2_grad_fill(b, a2_grad, work, Q, H, device):
+    """affine2's weight gradient over a window's Q rows (ic3_rnn_bptt / ic3_mlp_bptt: a2_grad + wgrad_scratch).  Returns the
+    scratch tensor: the caller holds it until the call has returned."""
+    if a2_grad is None:
+        return None
+    assert _f32(a2_grad, (H, H))
+    scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_wide_scratch_floats(Q, H)), device)
+    _set_ptrs(b, dict(a2_grad=a2_grad, wgrad_scratch=scratch))
+    return scratch
+
+
 def bptt_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lstm_wp3_bwd, w_heads, c_weight, dh, dc, dxh,
                   dbias_partials, dcw_partials, mode_avg=True, comm_zero=False, detach_gap=0, row_live=None, row_keep=None,
                   enc_first=True, gate_events=None, two_chains=False):
@@ -371,54 +397,39 @@ def bptt_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lst
     record, communication backward, encoder backward stage 1 — three launches per step).  alive / gate: lists of T tensors
     (E, N) int32 or None entries, or None.  gate_events: a list that receives (start, stop, t) DispatchEvent triples stamped
     around every step's gate launch (measurement: bench.py --mode train)."""
-    import ctypes as C
     _need_cuda(gates, "bptt_backward")
     R = E * N
-    OT = dhead.shape[-1]
-    assert gates.is_contiguous() and gates.numel() == T * R * 4 * H and gates.dtype == torch.float32
-    assert hs.is_contiguous() and cs.is_contiguous() and hs.shape[0] >= T and tuple(hs.shape[1:]) == (R, H) == tuple(cs.shape[1:])
-    assert dhead.is_contiguous() and dhead.numel() == T * R * OT and dhead.dtype == torch.float32
-    assert snaps.is_contiguous() and snaps.dtype == torch.int32 and snaps.shape[0] >= T
-    for v in (dh, dc):
-        assert v.is_contiguous() and tuple(v.shape) == (R, H) and v.dtype == torch.float32
-    assert dxh.is_contiguous() and tuple(dxh.shape) in ((R, 2 * H), (T, R, 2 * H))      # one buffer, or a ring of T (dxh_step)
-    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == ((R + 63) // 64, 4 * H)
-    two_chains = bool(two_chains) and dxh.dim() == 3 and first_chain_envs(E, N) < E
+    assert _f32(gates, T * R * 4 * H)
+    assert _dense(hs) and _dense(cs) and hs.shape[0] >= T and tuple(hs.shape[1:]) == (R, H) == tuple(cs.shape[1:])
+    OT = _window_inputs(dhead, snaps, T, R)
+    assert _f32(dh, (R, H)) and _f32(dc, (R, H))
+    assert _dense(dxh) and tuple(dxh.shape) in ((R, 2 * H), (T, R, 2 * H))      # one buffer, or a ring of T (dxh_step)
+    assert _dense(dbias_partials, ((R + 63) // 64, 4 * H))
+    ring = dxh.dim() == 3
+    two_chains = bool(two_chains) and ring and first_chain_envs(E, N) < E
     if not comm_zero:
-        assert dcw_partials.is_contiguous() and tuple(dcw_partials.shape) == (bptt_dcw_partials(E, N, two_chains), H, H)
-        assert c_weight.is_contiguous() and tuple(c_weight.shape) == (H, H)
-    for v in (row_live, row_keep):
-        assert v is None or (v.is_contiguous() and v.dtype == torch.float32 and tuple(v.shape) == (T, R))
+        assert _dense(dcw_partials, (bptt_dcw_partials(E, N, two_chains), H, H))
+        assert _dense(c_weight, (H, H))
+    assert _f32(row_live, (T, R), none_ok=True) and _f32(row_keep, (T, R), none_ok=True)
 
     def ptrs(ms):
         if ms is None or all(m is None for m in ms):
             return None
         assert len(ms) >= T
-        for m in ms[:T]:
-            assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
+        assert all(_mask(m, R) for m in ms[:T])
         return (C.c_void_p * T)(*[None if m is None else m.data_ptr() for m in ms[:T]])
-    pa, pg = ptrs(alive), ptrs(gate)
-    b = _lib.Bptt()
-    b.struct_size = C.sizeof(b)
-    b.T, b.E, b.N, b.H, b.OT = T, E, N, H, OT
-    b.mode_avg, b.comm_zero, b.detach_gap, b.enc_first = int(bool(mode_avg)), int(bool(comm_zero)), int(detach_gap), int(bool(enc_first))
-    b.gates, b.hs, b.cs, b.dhead, b.snaps = gates.data_ptr(), hs.data_ptr(), cs.data_ptr(), dhead.data_ptr(), snaps.data_ptr()
+    pa, pg = ptrs(alive), ptrs(gate)                # (alive until the call has returned)
+    b = _lib.Bptt(T, E, N, H, OT, int(bool(mode_avg)), int(bool(comm_zero)), int(detach_gap), int(bool(enc_first)))
+    _set_ptrs(b, dict(gates=gates, hs=hs, cs=cs, dhead=dhead, snaps=snaps, lstm_wp3_bwd=lstm_wp3_bwd, w_heads=w_heads, dh=dh, dc=dc,
+                      dxh=dxh, dbias_partials=dbias_partials),
+              row_live=row_live, row_keep=row_keep, c_weight=c_weight, dcw_partials=dcw_partials)
     b.snap_words = snaps.stride(0)
     b.alive = C.cast(pa, C.POINTER(C.c_void_p)) if pa is not None else None
     b.gate = C.cast(pg, C.POINTER(C.c_void_p)) if pg is not None else None
-    b.row_live = row_live.data_ptr() if row_live is not None else None
-    b.row_keep = row_keep.data_ptr() if row_keep is not None else None
-    b.lstm_wp3_bwd, b.w_heads = lstm_wp3_bwd.data_ptr(), w_heads.data_ptr()
-    b.c_weight = c_weight.data_ptr() if c_weight is not None else None
-    b.dh, b.dc, b.dxh = dh.data_ptr(), dc.data_ptr(), dxh.data_ptr()
-    b.dbias_partials = dbias_partials.data_ptr()
-    b.dcw_partials = dcw_partials.data_ptr() if dcw_partials is not None else None
     b.two_chains = int(two_chains)
-    if dxh.dim() == 3:                     # a ring of per-step input gradients: the encoder's first stage once, over the window
+    if ring:                               # a ring of per-step input gradients: the encoder's first stage once, over the window
         b.dxh_step = dxh.stride(0)
-        b.enc_work = env.encode_window_work(H).data_ptr()
-    else:
-        b.enc_work = env._encb_work(H).data_ptr()
+    b.enc_work = _enc_work(env, H, ring)
     evs = None
     if gate_events is not None:
         from .envs import DispatchEvent
@@ -447,14 +458,13 @@ def rnn_tanh_backward_step(dh_in, h_t, dhead, w_heads, a2, dz, dh_out, dbias_par
     _need_cuda(h_t, "rnn_tanh_backward_step")
     R, H = h_t.shape
     OT = dhead.shape[-1]
-    for v in (h_t, dz, dh_out) + ((dh_in,) if dh_in is not None else ()):
-        assert v.is_contiguous() and tuple(v.shape) == (R, H) and v.dtype == torch.float32
-    assert dhead.is_contiguous() and tuple(dhead.shape) == (R, OT) and dhead.dtype == torch.float32
-    assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and a2.is_contiguous() and tuple(a2.shape) == (H, H)
-    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (rnn_backward_partials(R, H), H)
-    n = _lib.lib().ic3_rnn_tanh_backward_step_wide(ptr(dh_in), ptr(h_t), ptr(dhead), ptr(w_heads), OT, ptr(a2), _rowvec(out_scale, R),
-                                              ptr(dz), ptr(dh_out), ptr(dbias_partials), int(bool(accumulate)), R, H, stream())
-    return check(n)
+    assert _f32(h_t, (R, H)) and _f32(dz, (R, H)) and _f32(dh_out, (R, H)) and _f32(dh_in, (R, H), none_ok=True)
+    assert _f32(dhead, (R, OT))
+    assert _dense(w_heads, (OT, H)) and _dense(a2, (H, H))
+    assert _dense(dbias_partials, (rnn_backward_partials(R, H), H))
+    return check(_lib.lib().ic3_rnn_tanh_backward_step_wide(ptr(dh_in), ptr(h_t), ptr(dhead), ptr(w_heads), OT, ptr(a2),
+                                                            _rowvec(out_scale, R), ptr(dz), ptr(dh_out), ptr(dbias_partials),
+                                                            int(bool(accumulate)), R, H, stream()))
 
 
 def rnn_weight_grad(dz, h_prev, dA2, row_live=None, accumulate=True, work=None):
@@ -463,16 +473,14 @@ def rnn_weight_grad(dz, h_prev, dA2, row_live=None, accumulate=True, work=None):
     _need_cuda(dz, "rnn_weight_grad")
     H = dz.shape[-1]
     Q = dz.numel() // H
-    assert dz.is_contiguous() and dz.dtype == torch.float32 and h_prev.is_contiguous() and h_prev.numel() >= Q * H
-    assert h_prev.shape[-1] == H and h_prev.dtype == torch.float32
-    assert dA2.is_contiguous() and tuple(dA2.shape) == (H, H)
-    if row_live is not None:
-        assert row_live.is_contiguous() and row_live.dtype == torch.float32 and row_live.numel() == Q
+    assert _f32(dz) and _f32(h_prev) and h_prev.numel() >= Q * H and h_prev.shape[-1] == H
+    assert _dense(dA2, (H, H))
+    assert _f32(row_live, Q, none_ok=True)
     n = int(_lib.lib().ic3_rnn_weight_grad_wide_scratch_floats(Q, H))
     if n == 0:
         raise NotImplementedError("rnn_weight_grad: hid_size 64 / 128 / 256")
     check(_lib.lib().ic3_rnn_weight_grad_wide(ptr(dz), ptr(h_prev), ptr(row_live), Q, H, ptr(dA2), int(bool(accumulate)),
-                                         ptr(_scratch(work, 'rnn_wgrad', n, dz.device)), stream()))
+                                              ptr(_scratch(work, 'rnn_wgrad', n, dz.device)), stream()))
 
 
 def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_partials, h_last=None, detach_gap=0, row_live=None,
@@ -481,36 +489,22 @@ def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_p
     launch per step, the encoder's first stage over the dz ring — enc_window — or per step, and with a2_grad affine2's weight
     gradient over the window).  hs (>= T, R, H) the states entering the steps (slot T, or h_last, the state leaving the last one),
     dhead (T, R, OT), dz (T, R, H) the ring, dbias_partials (rnn_backward_partials(R, H), H) added to."""
-    import ctypes as C
     _need_cuda(hs, "rnn_backward")
     R = E * N
-    OT = dhead.shape[-1]
-    assert hs.is_contiguous() and hs.dtype == torch.float32 and tuple(hs.shape[1:]) == (R, H)
+    assert _f32(hs) and tuple(hs.shape[1:]) == (R, H)
     assert hs.shape[0] >= T + 1 or (hs.shape[0] >= T and h_last is not None)
-    assert h_last is None or (h_last.is_contiguous() and tuple(h_last.shape) == (R, H))
-    assert dhead.is_contiguous() and dhead.numel() == T * R * OT and dhead.dtype == torch.float32
-    assert snaps.is_contiguous() and snaps.dtype == torch.int32 and snaps.shape[0] >= T
-    assert dh.is_contiguous() and tuple(dh.shape) == (R, H) and dz.is_contiguous() and tuple(dz.shape) == (T, R, H)
-    assert a2.is_contiguous() and tuple(a2.shape) == (H, H) and w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H)
-    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (rnn_backward_partials(R, H), H)
-    for v in (row_live, row_keep):
-        assert v is None or (v.is_contiguous() and v.dtype == torch.float32 and tuple(v.shape) == (T, R))
-    b = _lib.RnnBptt()
-    b.struct_size = C.sizeof(b)
-    b.T, b.E, b.N, b.H, b.OT = T, E, N, H, OT
-    b.detach_gap, b.enc_first, b.enc_window = int(detach_gap), int(bool(enc_first)), int(bool(enc_window))
-    b.hs, b.dhead, b.snaps = hs.data_ptr(), dhead.data_ptr(), snaps.data_ptr()
-    b.h_last = h_last.data_ptr() if h_last is not None else None
+    assert _dense(h_last, (R, H), none_ok=True)
+    OT = _window_inputs(dhead, snaps, T, R)
+    assert _dense(dh, (R, H)) and _dense(dz, (T, R, H))
+    assert _dense(a2, (H, H)) and _dense(w_heads, (OT, H))
+    assert _dense(dbias_partials, (rnn_backward_partials(R, H), H))
+    assert _f32(row_live, (T, R), none_ok=True) and _f32(row_keep, (T, R), none_ok=True)
+    b = _lib.RnnBptt(T, E, N, H, OT, int(detach_gap), int(bool(enc_first)), int(bool(enc_window)))
+    _set_ptrs(b, dict(hs=hs, dhead=dhead, snaps=snaps, a2=a2, w_heads=w_heads, dh=dh, dz=dz, dbias_partials=dbias_partials),
+              h_last=h_last, row_live=row_live, row_keep=row_keep)
     b.snap_words = snaps.stride(0)
-    b.a2, b.w_heads = a2.data_ptr(), w_heads.data_ptr()
-    b.row_live = row_live.data_ptr() if row_live is not None else None
-    b.row_keep = row_keep.data_ptr() if row_keep is not None else None
-    b.dh, b.dz, b.dbias_partials = dh.data_ptr(), dz.data_ptr(), dbias_partials.data_ptr()
-    b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
-    if a2_grad is not None:
-        assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
-        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_wide_scratch_floats(T * R, H)), hs.device)
-        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), scratch.data_ptr()       # (`scratch`: alive until the call has returned)
+    b.enc_work = _enc_work(env, H, enc_window)
+    scratch = _a2_grad_fill(b, a2_grad, work, T * R, H, hs.device)       # (`scratch`: alive until the call has returned)
     check(_lib.lib().ic3_rnn_backward_wide(env._h, C.byref(b), stream()))
 
 
@@ -533,13 +527,12 @@ def mlp_backward_step(x1, h, dhead, w_heads, a2, dz, de, dbias_partials, accumul
     Q = h.numel() // H
     OT = dhead.shape[-1]
     for v in (x1, h, dz, de):
-        assert v.is_contiguous() and v.numel() == Q * H and v.shape[-1] == H and v.dtype == torch.float32
-    assert dhead.is_contiguous() and dhead.numel() == Q * OT and dhead.dtype == torch.float32
-    assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and a2.is_contiguous() and tuple(a2.shape) == (H, H)
-    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (mlp_backward_partials(Q, H), H)
-    n = _lib.lib().ic3_mlp_backward_step_wide(ptr(x1), ptr(h), ptr(dhead), ptr(w_heads), OT, ptr(a2), ptr(dz), ptr(de),
-                                         ptr(dbias_partials), int(bool(accumulate)), Q, H, stream())
-    return check(n)
+        assert _f32(v, Q * H) and v.shape[-1] == H
+    assert _f32(dhead, Q * OT)
+    assert _dense(w_heads, (OT, H)) and _dense(a2, (H, H))
+    assert _dense(dbias_partials, (mlp_backward_partials(Q, H), H))
+    return check(_lib.lib().ic3_mlp_backward_step_wide(ptr(x1), ptr(h), ptr(dhead), ptr(w_heads), OT, ptr(a2), ptr(dz), ptr(de),
+                                                       ptr(dbias_partials), int(bool(accumulate)), Q, H, stream()))
 
 
 def mlp_backward(env, T, E, N, H, h, dhead, snaps, enc_wt, enc_bias, a2, w_heads, x1, dz, de, dbias_partials, loc_table=None,
@@ -548,34 +541,21 @@ def mlp_backward(env, T, E, N, H, h, dhead, snaps, enc_wt, enc_bias, a2, w_heads
     T encoder launches into the x1 ring, ONE launch over all T x R rows, the encoder's first stage over the de ring (enc_window,
     or per step) and with a2_grad affine2's weight gradient over the window.  h (>= T, R, H) the state every step ended with,
     dhead (T, R, OT), x1 / dz / de (T, R, H) the rings, dbias_partials (mlp_backward_partials(T * R, H), H) written."""
-    import ctypes as C
     _need_cuda(h, "mlp_backward")
     R = E * N
-    OT = dhead.shape[-1]
-    assert h.is_contiguous() and h.dtype == torch.float32 and tuple(h.shape[1:]) == (R, H) and h.shape[0] >= T
-    assert dhead.is_contiguous() and dhead.numel() == T * R * OT and dhead.dtype == torch.float32
-    assert snaps.is_contiguous() and snaps.dtype == torch.int32 and snaps.shape[0] >= T
-    for v in (x1, dz, de):
-        assert v.is_contiguous() and tuple(v.shape) == (T, R, H) and v.dtype == torch.float32
-    assert enc_wt.is_contiguous() and enc_wt.dtype == torch.float32 and tuple(enc_wt.shape) == (env.obs_dim, H)
-    assert enc_bias.is_contiguous() and enc_bias.numel() == H
-    assert a2.is_contiguous() and tuple(a2.shape) == (H, H) and w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H)
-    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (mlp_backward_partials(T * R, H), H)
-    b = _lib.MlpBptt()
-    b.struct_size = C.sizeof(b)
-    b.T, b.E, b.N, b.H, b.OT = T, E, N, H, OT
-    b.enc_first, b.enc_window = int(bool(enc_first)), int(bool(enc_window))
-    b.h, b.dhead, b.snaps = h.data_ptr(), dhead.data_ptr(), snaps.data_ptr()
+    assert _f32(h) and tuple(h.shape[1:]) == (R, H) and h.shape[0] >= T
+    OT = _window_inputs(dhead, snaps, T, R)
+    assert _f32(x1, (T, R, H)) and _f32(dz, (T, R, H)) and _f32(de, (T, R, H))
+    assert _f32(enc_wt, (env.obs_dim, H))
+    assert _dense(enc_bias, H)
+    assert _dense(a2, (H, H)) and _dense(w_heads, (OT, H))
+    assert _dense(dbias_partials, (mlp_backward_partials(T * R, H), H))
+    b = _lib.MlpBptt(T, E, N, H, OT, int(bool(enc_first)), int(bool(enc_window)))
+    _set_ptrs(b, dict(h=h, dhead=dhead, snaps=snaps, enc_wt=enc_wt, enc_bias=enc_bias, a2=a2, w_heads=w_heads, x1=x1, dz=dz, de=de,
+                      dbias_partials=dbias_partials), loc_table=loc_table)
     b.snap_words = snaps.stride(0)
-    b.enc_wt, b.enc_bias = enc_wt.data_ptr(), enc_bias.data_ptr()
-    b.loc_table = loc_table.data_ptr() if loc_table is not None else None
-    b.a2, b.w_heads = a2.data_ptr(), w_heads.data_ptr()
-    b.x1, b.dz, b.de, b.dbias_partials = x1.data_ptr(), dz.data_ptr(), de.data_ptr(), dbias_partials.data_ptr()
-    b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
-    if a2_grad is not None:
-        assert a2_grad.is_contiguous() and tuple(a2_grad.shape) == (H, H) and a2_grad.dtype == torch.float32
-        scratch = _scratch(work, 'rnn_wgrad', int(_lib.lib().ic3_rnn_weight_grad_wide_scratch_floats(T * R, H)), h.device)
-        b.a2_grad, b.wgrad_scratch = a2_grad.data_ptr(), scratch.data_ptr()       # (`scratch`: alive until the call has returned)
+    b.enc_work = _enc_work(env, H, enc_window)
+    scratch = _a2_grad_fill(b, a2_grad, work, T * R, H, h.device)        # (`scratch`: alive until the call has returned)
     check(_lib.lib().ic3_mlp_backward_wide(env._h, C.byref(b), stream()))
 
 
@@ -607,18 +587,19 @@ def commnet_pass_backward(dh_in, h_next, dhead, w_heads, f_weight, dxh, dz, dx, 
     _need_cuda(h_next, "commnet_pass_backward")
     Q, H = h_next.shape
     for v in (dh_in, h_next, dz, dx):
-        assert v is None or (v.is_contiguous() and tuple(v.shape) == (Q, H) and v.dtype == torch.float32)
-    assert dxh.is_contiguous() and tuple(dxh.shape) == (Q, 2 * H) and dxh.dtype == torch.float32
+        assert _f32(v, (Q, H), none_ok=True)
+    assert _f32(dxh, (Q, 2 * H))
     OT = 0
     if dhead is not None:
         OT = dhead.shape[-1]
-        assert dhead.is_contiguous() and tuple(dhead.shape) == (Q, OT) and dhead.dtype == torch.float32
-        assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H) and w_heads.dtype == torch.float32
-    assert f_weight.is_contiguous() and tuple(f_weight.shape) == (H, H) and f_weight.dtype == torch.float32
-    assert dbias_partials.is_contiguous() and tuple(dbias_partials.shape) == (commnet_pass_backward_partials(Q, H), H)
-    return check(_lib.lib().ic3_commnet_pass_backward(ptr(dh_in), ptr(h_next), ptr(dhead), ptr(w_heads) if dhead is not None else None, OT,
-                                                      ptr(f_weight), ptr(dxh), ptr(dz), ptr(dx), int(bool(dx_add)), ptr(dbias_partials),
-                                                      int(bool(accumulate)), Q, H, stream()))
+        assert _f32(dhead, (Q, OT))
+        assert _f32(w_heads, (OT, H))
+    assert _f32(f_weight, (H, H))
+    assert _dense(dbias_partials, (commnet_pass_backward_partials(Q, H), H))
+    w_heads = w_heads if dhead is not None else None               # (dhead's weights: NULL without it)
+    return check(_lib.lib().ic3_commnet_pass_backward(ptr(dh_in), ptr(h_next), ptr(dhead), ptr(w_heads), OT, ptr(f_weight), ptr(dxh),
+                                                      ptr(dz), ptr(dx), int(bool(dx_add)), ptr(dbias_partials), int(bool(accumulate)),
+                                                      Q, H, stream()))
 
 
 def commnet_forward_record(enc, E, N, wp, bias, mode_avg, comm_zero, alive_in, comm_in, h_pass, wp3=None):
@@ -627,11 +608,10 @@ def commnet_forward_record(enc, E, N, wp, bias, mode_avg, comm_zero, alive_in, c
     _need_cuda(enc, "commnet_forward_record")
     R, H = enc.shape
     P = wp.shape[0]
-    assert R == E * N and enc.is_contiguous() and enc.dtype == torch.float32
-    assert h_pass.is_contiguous() and tuple(h_pass.shape) == (P + 1, R, H) and h_pass.dtype == torch.float32
-    for m in (alive_in, comm_in):
-        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
-    assert wp3 is None or (wp3.is_contiguous() and tuple(wp3.shape) == (P, 3 * H * H))
+    assert R == E * N and _f32(enc)
+    assert _f32(h_pass, (P + 1, R, H))
+    assert _mask(alive_in, R) and _mask(comm_in, R)
+    assert _dense(wp3, (P, 3 * H * H), none_ok=True)
     check(_lib.lib().ic3_commnet_forward_record(ptr(enc), E, N, H, P, ptr(wp), ptr(wp3), ptr(bias), None, None, None, 0,
                                                 int(bool(mode_avg)), int(bool(comm_zero)), ptr(alive_in), ptr(comm_in), None, None,
                                                 ptr(h_pass), stream()))
@@ -647,26 +627,20 @@ def commnet_backward(env, T, E, N, H, dhead, snaps, alive, gate, enc_wt, enc_bia
     (T, R, OT), alive / gate (T, E, N) int32 or None, f_weights / c_weights: lists of P (H, H) weights as stored, f_grads / c_grads
     (H, H) / bias_grads (H,): lists of P DISTINCT tensors, added to; heads_w_grad (OT, H) / heads_b_grad (OT,) added to.  The rings
     (commnet_backward_ring_floats) live in `work` between calls.  Returns (rings dict, chunks run)."""
-    import ctypes as C
     _need_cuda(dhead, "commnet_backward")
     R, P = E * N, len(f_weights)
-    OT = dhead.shape[-1]
     dev = dhead.device
-    assert dhead.is_contiguous() and dhead.numel() == T * R * OT and dhead.dtype == torch.float32
-    assert snaps.is_contiguous() and snaps.dtype == torch.int32 and snaps.shape[0] >= T
-    for m in (alive, gate):
-        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and tuple(m.shape) == (T, E, N))
-    assert enc_wt.is_contiguous() and enc_wt.dtype == torch.float32 and tuple(enc_wt.shape) == (env.obs_dim, H)
-    assert enc_bias.is_contiguous() and enc_bias.numel() == H
-    assert wp.is_contiguous() and tuple(wp.shape) == (P, 2 * H * H) and bias.is_contiguous() and tuple(bias.shape) == (P, H)
-    assert wp3 is None or (wp3.is_contiguous() and tuple(wp3.shape) == (P, 3 * H * H))
-    assert w_heads.is_contiguous() and tuple(w_heads.shape) == (OT, H)
+    OT = _window_inputs(dhead, snaps, T, R)
+    assert _i32(alive, (T, E, N), none_ok=True) and _i32(gate, (T, E, N), none_ok=True)
+    assert _f32(enc_wt, (env.obs_dim, H))
+    assert _dense(enc_bias, H)
+    assert _dense(wp, (P, 2 * H * H)) and _dense(bias, (P, H))
+    assert _dense(wp3, (P, 3 * H * H), none_ok=True)
+    assert _dense(w_heads, (OT, H))
     mats = list(f_weights) + list(f_grads) + ([] if comm_zero else list(c_weights) + list(c_grads))
     assert len(f_grads) == len(bias_grads) == P and (comm_zero or len(c_weights) == len(c_grads) == P)
-    for v in mats:
-        assert v.is_contiguous() and tuple(v.shape) == (H, H) and v.dtype == torch.float32
-    for v in bias_grads:
-        assert v.is_contiguous() and v.numel() == H and v.dtype == torch.float32
+    assert all(_f32(v, (H, H)) for v in mats)
+    assert all(_f32(v, H) for v in bias_grads)
     assert len(set(v.data_ptr() for v in f_grads)) == P and len(set(v.data_ptr() for v in bias_grads)) == P
     tc = commnet_backward_chunk_steps(env, T, H, max_chunk_steps)
     if tc < 1:
@@ -686,30 +660,20 @@ def commnet_backward(env, T, E, N, H, dhead, snaps, alive, gate, enc_wt, enc_bia
     rings = dict(h_pass=take(P + 1, Qc, H), dxh=take(Qc, 2 * H), dz=take(Qc, H), dx=take(Qc, H), de=take(Qc, H), dh=take(Qc, H))
     scratch = take(nscr)
     arr = lambda lst: (C.c_void_p * P)(*[v.data_ptr() for v in lst])
-    b = _lib.CommnetBptt()
-    b.struct_size = C.sizeof(b)
-    b.T, b.E, b.N, b.H, b.OT, b.passes = T, E, N, H, OT, P
-    b.mode_avg, b.comm_zero, b.enc_first, b.enc_window = int(bool(mode_avg)), int(bool(comm_zero)), int(bool(enc_first)), int(bool(enc_window))
-    b.max_chunk_steps = int(max_chunk_steps)
-    b.dhead, b.snaps, b.snap_words = dhead.data_ptr(), snaps.data_ptr(), snaps.stride(0)
-    b.alive = alive.data_ptr() if alive is not None else None
-    b.gate = gate.data_ptr() if gate is not None else None
-    b.enc_wt, b.enc_bias = enc_wt.data_ptr(), enc_bias.data_ptr()
-    b.loc_table = loc_table.data_ptr() if loc_table is not None else None
-    b.wp, b.bias, b.w_heads = wp.data_ptr(), bias.data_ptr(), w_heads.data_ptr()
-    b.wp3 = wp3.data_ptr() if wp3 is not None else None
+    b = _lib.CommnetBptt(T, E, N, H, OT, P, int(bool(mode_avg)), int(bool(comm_zero)), int(bool(enc_first)), int(bool(enc_window)),
+                         int(max_chunk_steps))
+    _set_ptrs(b, dict(rings, dhead=dhead, snaps=snaps, enc_wt=enc_wt, enc_bias=enc_bias, wp=wp, bias=bias, w_heads=w_heads,
+                      scratch=scratch), alive=alive, gate=gate, loc_table=loc_table, wp3=wp3)
+    b.snap_words = snaps.stride(0)
     keep = [arr(f_weights), arr(f_grads), arr(bias_grads)]      # (alive until the call has returned)
     b.f_weight, b.f_grad, b.bias_grad = keep
     if not comm_zero:
         keep += [arr(c_weights), arr(c_grads)]
         b.c_weight, b.c_grad = keep[3:]
     if heads_w_grad is not None:
-        assert heads_w_grad.is_contiguous() and tuple(heads_w_grad.shape) == (OT, H) and heads_b_grad.is_contiguous() and heads_b_grad.numel() == OT
-        b.heads_w_grad, b.heads_b_grad = heads_w_grad.data_ptr(), heads_b_grad.data_ptr()
-    for k, v in rings.items():
-        setattr(b, k, v.data_ptr())
-    b.scratch = scratch.data_ptr()
-    b.enc_work = (env.encode_window_work(H) if enc_window else env._encb_work(H)).data_ptr()
+        assert _dense(heads_w_grad, (OT, H)) and _dense(heads_b_grad, OT)
+        _set_ptrs(b, dict(heads_w_grad=heads_w_grad, heads_b_grad=heads_b_grad))
+    b.enc_work = _enc_work(env, H, enc_window)
     chunks = check(_lib.lib().ic3_commnet_backward(env._h, C.byref(b), stream()))
     return rings, chunks
 
@@ -723,25 +687,21 @@ def heads_grad(d, h, dW, db, work=None):
     _need_cuda(d, "heads_grad")
     M, OT = d.shape
     H = h.shape[1]
-    assert d.is_contiguous() and h.is_contiguous() and h.shape[0] == M and d.dtype == h.dtype == torch.float32
-    assert dW.is_contiguous() and tuple(dW.shape) == (OT, H) and db.is_contiguous() and db.numel() == OT
-    work = work if work is not None else dict()
-    key = ('heads_grad', H, str(d.device))
-    if key not in work:
-        work[key] = torch.empty((int(_lib.lib().ic3_heads_grad_scratch_floats(H)),), dtype=torch.float32, device=d.device)
-    check(_lib.lib().ic3_heads_grad(ptr(d), ptr(h), M, H, OT, ptr(dW), ptr(db), ptr(work[key]), stream()))
+    assert _f32(d) and _f32(h) and h.shape[0] == M
+    assert _dense(dW, (OT, H)) and _dense(db, OT)
+    scratch = _scratch(work, ('heads_grad', H), int(_lib.lib().ic3_heads_grad_scratch_floats(H)), d.device)
+    check(_lib.lib().ic3_heads_grad(ptr(d), ptr(h), M, H, OT, ptr(dW), ptr(db), ptr(scratch), stream()))
 
 
 def policy_heads(h, W, b, head_sizes, out=None):
     """h (R,H) rows (unit column stride), W (OT,H), b (OT,) -> out (R,OT) = [log_softmax heads | value]."""
-    import ctypes as C
     _need_cuda(h, "policy_heads")
     R, H = h.shape
     OT = W.shape[0]
-    assert h.stride(1) == 1 and W.is_contiguous() and OT == sum(head_sizes) + 1
+    assert h.stride(1) == 1 and _dense(W) and OT == sum(head_sizes) + 1
     if out is None:
         out = torch.empty((R, OT), dtype=torch.float32, device=h.device)
-    sizes = (C.c_int32 * len(head_sizes))(*[int(a) for a in head_sizes])
+    sizes = int32_array(head_sizes)
     check(_lib.lib().ic3_policy_heads(ptr(h), h.stride(0), ptr(W), ptr(b), sizes, len(head_sizes), ptr(out), R, H,
                                       stream()))
     return out
@@ -779,24 +739,23 @@ def policy_step_supported(env, H):
     return H in POLICY_STEP_SIZES and _lib.lib().ic3_policy_step_supported(env._h, int(H)) > 0
 
 
-def policy_pack_split(w_ih, w_hh):
-    """ic3_policy.gate_split (the default): [W_ih | W_hh] as three exact bf16 planes in MFMA fragment order."""
-    _need_cuda(w_ih, "policy_pack_split")
+def _pack_split(entry, name, w_ih, w_hh):
+    """[W_ih | W_hh] (4H, 2H) as three bf16 planes (24 H^2 words) in the fragment order `entry` writes."""
+    _need_cuda(w_ih, name)
     H = w_ih.shape[1]
     wp3 = torch.empty((3 * 2 * H * 4 * H,), dtype=torch.bfloat16, device=w_ih.device)
-    check(_lib.lib().ic3_policy_pack_split(ptr(w_ih.detach().contiguous().float()), ptr(w_hh.detach().contiguous().float()),
-                                           ptr(wp3), H, stream()))
+    check(entry(ptr(w_ih.detach().contiguous().float()), ptr(w_hh.detach().contiguous().float()), ptr(wp3), H, stream()))
     return wp3
+
+
+def policy_pack_split(w_ih, w_hh):
+    """ic3_policy.gate_split (the default): [W_ih | W_hh] as three exact bf16 planes in MFMA fragment order."""
+    return _pack_split(_lib.lib().ic3_policy_pack_split, "policy_pack_split", w_ih, w_hh)
 
 
 def policy_pack_split_bwd(w_ih, w_hh):
     """The split planes of [W_ih | W_hh] in the fragment order of the gate product's BACKWARD (ic3_lstm_gates_backward_dx)."""
-    _need_cuda(w_ih, "policy_pack_split_bwd")
-    H = w_ih.shape[1]
-    wp3 = torch.empty((3 * 4 * H * 2 * H,), dtype=torch.bfloat16, device=w_ih.device)
-    check(_lib.lib().ic3_policy_pack_split_bwd(ptr(w_ih.detach().contiguous().float()), ptr(w_hh.detach().contiguous().float()),
-                                               ptr(wp3), H, stream()))
-    return wp3
+    return _pack_split(_lib.lib().ic3_policy_pack_split_bwd, "policy_pack_split_bwd", w_ih, w_hh)
 
 
 def policy_step_passes_supported(fc, H, passes):
@@ -819,16 +778,13 @@ def _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, encoder=True, pass_in
             pol.c_wp_pass[i] = fc['ps_c_wp' + sf].data_ptr()
             pol.enc_bias_pass[i] = fc['enc_bias' + sf].data_ptr()
     pol.H, pol.nheads = int(H), len(head_sizes)
-    for i, a in enumerate(head_sizes):
-        pol.head_sizes[i] = int(a)
+    pol.head_sizes = int32_array(head_sizes, 4)
     pol.mode_avg, pol.comm_zero = int(bool(mode_avg)), int(bool(comm_zero))
     if encoder:
-        pol.enc_wt, pol.enc_bias = fc['wt'].data_ptr(), fc['enc_bias' + sfx].data_ptr()
-        pol.loc_table = fc['loc_table'].data_ptr() if fc.get('loc_table') is not None else None
-    pol.c_wp, pol.lstm_wp, pol.lstm_bias = fc['ps_c_wp' + sfx].data_ptr(), fc['ps_l_wp'].data_ptr(), fc['b_cat'].data_ptr()
-    pol.head_w, pol.head_b = fc['w_heads'].data_ptr(), fc['b_heads'].data_ptr()
-    if fc.get('ps_l_wp3') is not None:                           # gate_split: exact split products on the bf16 matrix cores
-        pol.gate_split, pol.lstm_wp3 = 1, fc['ps_l_wp3'].data_ptr()
+        _set_ptrs(pol, dict(enc_wt=fc['wt'], enc_bias=fc['enc_bias' + sfx]), loc_table=fc.get('loc_table'))
+    _set_ptrs(pol, dict(c_wp=fc['ps_c_wp' + sfx], lstm_wp=fc['ps_l_wp'], lstm_bias=fc['b_cat'], head_w=fc['w_heads'],
+                        head_b=fc['b_heads']), lstm_wp3=fc.get('ps_l_wp3'))
+    pol.gate_split = int(fc.get('ps_l_wp3') is not None)         # exact split products on the bf16 matrix cores
     return pol
 
 
@@ -837,12 +793,10 @@ def policy_forward(fc, H, head_sizes, mode_avg, comm_zero, enc, E, N, h, c, aliv
     """The policy half of policy_step for a caller-supplied encoder output enc (E*N, H) = encoder(x) + C.bias
     (ic3_policy_forward): communication block, C, LSTMCell, heads, log_softmax in one launch; h, c in place.
     inner=True: a non-final communication pass (comm_passes > 1) — h, c only, returns None."""
-    import ctypes as C
     _need_cuda(enc, "policy_forward")
     R = E * N
-    assert enc.is_contiguous() and enc.shape == (R, H) and h.is_contiguous() and c.is_contiguous()
-    for m in (alive_in, comm_in):
-        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
+    assert _dense(enc, (R, H)) and _dense(h) and _dense(c)
+    assert _mask(alive_in, R) and _mask(comm_in, R)
     if out is None and not inner:
         out = torch.empty((R, sum(head_sizes) + 1), dtype=torch.float32, device=enc.device)
     pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, encoder=False, pass_index=pass_index, inner=inner)
@@ -855,7 +809,6 @@ def policy_step_pass(env, fc, H, head_sizes, mode_avg, comm_zero, h, c, alive_in
     """A non-final communication pass of a comm_passes > 1 policy on the env's own state (ic3_policy_step with
     ic3_policy.inner_pass): sparse encoder, communication block, C_modules[pass_index], LSTMCell — h, c in place."""
     _need_cuda(h, "policy_step_pass")
-    import ctypes as C
     pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, pass_index=pass_index, inner=True)
     check(_lib.lib().ic3_policy_step(env._h, C.byref(pol), ptr(h), ptr(c), ptr(alive_in), ptr(comm_in), None, None, None,
                                      None, None, None, None, stream()))
@@ -868,13 +821,10 @@ def policy_step(env, fc, H, head_sizes, mode_avg, comm_zero, h, c, alive_in, com
     h, c (E*N, H) contiguous, updated in place; out (E*N, OT); action (heads, E, N) int32."""
     _need_cuda(h, "policy_step")
     R = h.shape[0]
-    assert h.is_contiguous() and c.is_contiguous() and h.shape == (R, H) and c.shape == (R, H)
-    assert out.is_contiguous() and action.is_contiguous() and action.dtype == torch.int32
-    assert action.numel() == len(head_sizes) * R and out.shape == (R, sum(head_sizes) + 1)
-    for m in (alive_in, comm_in):
-        assert m is None or (m.dtype == torch.int32 and m.is_contiguous() and m.numel() == R)
+    assert _dense(h, (R, H)) and _dense(c, (R, H))
+    assert _dense(out, (R, sum(head_sizes) + 1)) and _i32(action, len(head_sizes) * R)
+    assert _mask(alive_in, R) and _mask(comm_in, R)
     pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, pass_index=pass_index, passes=passes)
-    import ctypes as C
     check(_lib.lib().ic3_policy_step(env._h, C.byref(pol), ptr(h), ptr(c), ptr(alive_in), ptr(comm_in), ptr(out),
                                      ptr(action), ptr(obs), ptr(reward), ptr(done), ptr(alive), ptr(is_completed), stream()))
     return out
@@ -888,14 +838,12 @@ def episode_finalize(done, reward, alive=None, is_completed=None, gate=None, gat
     Returns dict(live (n,E), alive_mask, episode_mask (n,E), episode_mini_mask, live_after (E,), stats) where `stats`
     is a device fp64 tensor [num_steps, zero_len_envs, reward_sum[N], gate_sum[N]] (read it after a sync).
     `work`: dict reused between calls for the scratch buffers."""
-    import ctypes as C
     _need_cuda(reward, "episode_finalize")
     n, E, N = reward.shape
     dev = reward.device
-    assert done.dtype == torch.int32 and done.shape == (n, E) and done.is_contiguous()
-    assert reward.dtype == torch.float32 and reward.is_contiguous()
-    for m in (alive, is_completed):
-        assert m is None or (m.dtype == torch.int32 and m.shape == (n, E, N) and m.is_contiguous())
+    assert _i32(done, (n, E))
+    assert _f32(reward)
+    assert _i32(alive, (n, E, N), none_ok=True) and _i32(is_completed, (n, E, N), none_ok=True)
     gate_stride = 0
     if gate is not None:
         assert gate.dtype == torch.int32 and gate.shape == (n, E, N) and gate[0].is_contiguous()
@@ -936,7 +884,6 @@ def loss_gradients(out, action, returns, alive_mask, live, head_sizes, entr, val
     """compute_grad's losses and dL/d[logits | value] of every transition in one launch (ic3_loss_gradients): out (T, R, OT) the
     step launches' rows, action (T, heads, R) int32, returns / alive_mask (T, R), live (T, E).  Returns (d_out (T, R, OT),
     (action_loss, value_loss, entropy) as a float64 tensor of 3 on the device)."""
-    import ctypes as C
     _need_cuda(out, "loss_gradients")
     T, R, OT = out.shape
     E = live.shape[1]
@@ -944,11 +891,11 @@ def loss_gradients(out, action, returns, alive_mask, live, head_sizes, entr, val
     nh = len(head_sizes)
     assert OT == sum(int(a) for a in head_sizes) + 1 and tuple(action.shape) == (T, nh, R) and action.dtype == torch.int32
     for v in (out, action, returns, alive_mask, live):
-        assert v.is_contiguous()
+        assert _dense(v)
     assert returns.numel() == T * R == alive_mask.numel() and live.numel() == T * E and E * N == R
     d_out = torch.empty_like(out)
     sums = torch.empty((int(_lib.lib().ic3_loss_gradients_partials(T, R)), 3), dtype=torch.float64, device=out.device)
-    sizes = (C.c_int32 * nh)(*[int(a) for a in head_sizes])
+    sizes = int32_array(head_sizes)
     check(_lib.lib().ic3_loss_gradients(ptr(out), ptr(action), ptr(returns), ptr(alive_mask), ptr(live), sizes, nh,
                                         float(adv_shift), float(adv_scale), float(entr), float(value_coeff), ptr(d_out), ptr(sums),
                                         T, E, N, stream()))
@@ -963,18 +910,16 @@ def lstm_cell_heads_ok(H):
 def lstm_cell_heads_(gates, c, h_out, W, b, head_sizes, out=None, env=None, action=None):
     """lstm_cell_ + policy_heads (+ the action draws of every head into `action` (heads, E, N) int32 when `env`, the
     raw batched env, is given) in one launch.  Returns out (R, OT)."""
-    import ctypes as C
     _need_cuda(gates, "lstm_cell_heads_")
     R, H = c.shape
     OT = W.shape[0]
-    assert gates.is_contiguous() and c.is_contiguous() and h_out.stride(1) == 1 and W.is_contiguous()
+    assert _dense(gates) and _dense(c) and h_out.stride(1) == 1 and _dense(W)
     assert OT == sum(head_sizes) + 1
     if out is None:
         out = torch.empty((R, OT), dtype=torch.float32, device=c.device)
     if action is not None:
-        assert env is not None and action.is_contiguous() and action.dtype == torch.int32 \
-            and action.numel() == len(head_sizes) * R
-    sizes = (C.c_int32 * len(head_sizes))(*[int(a) for a in head_sizes])
+        assert env is not None and _i32(action, len(head_sizes) * R)
+    sizes = int32_array(head_sizes)
     check(_lib.lib().ic3_lstm_cell_heads(ptr(gates), ptr(c), ptr(h_out), h_out.stride(0), R, H, ptr(W), ptr(b), sizes,
                                          len(head_sizes), ptr(out), env._h if action is not None else None, ptr(action),
                                          stream()))
@@ -990,13 +935,20 @@ def comm_masked_mean(h, alive=None, comm_action=None, mode_avg=True, mask_self=T
     return _CommMaskedMean.apply(h, alive, comm_action, mode_avg, mask_self)
 
 
-def sample_actions(logp, head, seed, env_id_offset, episode, t, want_logp=False, out=None):
-    """logp (E,N,A) f32 -> action (E,N) int32 [, chosen log-prob (E,N) f32]; action_utils.py:32-36."""
-    _need_cuda(logp, "sample_actions")
+def _draw_buffers(logp, out, want_logp):
+    """(logp rows for the kernel, their stride, action (E,N) int32 = `out` or a new tensor, chosen log-prob (E,N) f32 or None)"""
     E, N, A = logp.shape
     logp, ld = _rows(logp.detach(), A)
     action = out if out is not None else torch.empty((E, N), dtype=torch.int32, device=logp.device)
     chosen = torch.empty((E, N), dtype=torch.float32, device=logp.device) if want_logp else None
+    return logp, ld, action, chosen
+
+
+def sample_actions(logp, head, seed, env_id_offset, episode, t, want_logp=False, out=None):
+    """logp (E,N,A) f32 -> action (E,N) int32 [, chosen log-prob (E,N) f32]; action_utils.py:32-36."""
+    _need_cuda(logp, "sample_actions")
+    E, N, A = logp.shape
+    logp, ld, action, chosen = _draw_buffers(logp, out, want_logp)
     check(_lib.lib().ic3_sample_actions(ptr(logp), ld, A, int(head), int(seed) & 0xffffffff, int(env_id_offset),
                                         int(episode), int(t), ptr(action), ptr(chosen), E, N, stream()))
     return (action, chosen) if want_logp else action
@@ -1007,9 +959,7 @@ def sample_actions_env(env, logp, head, out=None, want_logp=False):
     (ic3_env_sample_actions): identical draws, but every launch argument is constant -> hipGraph-capturable."""
     _need_cuda(logp, "sample_actions_env")
     E, N, A = logp.shape
-    logp, ld = _rows(logp.detach(), A)
-    action = out if out is not None else torch.empty((E, N), dtype=torch.int32, device=logp.device)
-    chosen = torch.empty((E, N), dtype=torch.float32, device=logp.device) if want_logp else None
+    logp, ld, action, chosen = _draw_buffers(logp, out, want_logp)
     check(_lib.lib().ic3_env_sample_actions(env._h, ptr(logp), ld, A, int(head), ptr(action), ptr(chosen), stream()))
     return (action, chosen) if want_logp else action
 
