@@ -58,6 +58,14 @@ class Policy(_SizedStruct):
                 ("npasses", C.c_int32), ("lstm_wp3", C.c_void_p), ("c_wp_pass", C.c_void_p * 4), ("enc_bias_pass", C.c_void_p * 4)]
 
 
+class PolicyRecord(_SizedStruct):
+    """ic3_policy_record (include/ic3_rollout.h): an ic3_policy followed by the operands of the recording inner pass; handed to
+    ic3_policy_forward in place of a Policy, with inner_pass = RECORD_PASS (the tag that selects this form) and its own struct_size."""
+    RECORD_PASS = 2                            # IC3_POLICY_RECORD_PASS
+    _fields_ = Policy._fields_ + [("enc_add", C.c_void_p), ("h_out", C.c_void_p), ("c_out", C.c_void_p), ("gates", C.c_void_p),
+                                  ("inp", C.c_void_p)]
+
+
 class Episode(_SizedStruct):
     """ic3_episode (include/ic3_rollout.h): episode buffers in, masks and reduced statistics out."""
     _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("E", C.c_int32), ("N", C.c_int32), ("auto_reset", C.c_int32),
@@ -78,6 +86,25 @@ class Bptt(_SizedStruct):
                 ("c_weight", C.c_void_p), ("dh", C.c_void_p), ("dc", C.c_void_p), ("dxh", C.c_void_p),
                 ("dbias_partials", C.c_void_p), ("dcw_partials", C.c_void_p), ("enc_work", C.c_void_p),
                 ("dxh_step", C.c_int64), ("two_chains", C.c_int32), ("gate_events", C.POINTER(C.c_void_p))]
+
+
+class BpttPasses(_SizedStruct):
+    """ic3_bptt_passes (include/ic3_rollout.h): one window (or chunk of one) of the comm_passes > 1 backward through time; handed to
+    ic3_bptt_backward in place of a Bptt (magic selects this form)."""
+    MAGIC = 0x53534150                         # IC3_BPTT_PASSES_MAGIC: the word that selects this form (an ic3_bptt holds T there)
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32)] + \
+               [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "passes", "mode_avg", "comm_zero", "detach_gap", "enc_first",
+                                         "t_first")] + \
+               [("gates", C.POINTER(C.c_void_p)), ("hs", C.POINTER(C.c_void_p)), ("cs", C.POINTER(C.c_void_p)), ("dhead", C.c_void_p),
+                ("snaps", C.c_void_p), ("snap_words", C.c_int64), ("alive", C.POINTER(C.c_void_p)), ("gate", C.POINTER(C.c_void_p)),
+                ("lstm_wp3_bwd", C.c_void_p), ("w_heads", C.c_void_p), ("c_weight", C.POINTER(C.c_void_p)), ("dh", C.c_void_p),
+                ("dc", C.c_void_p), ("dxh", C.POINTER(C.c_void_p)), ("dxh_step", C.c_int64), ("dbias_partials", C.POINTER(C.c_void_p)),
+                ("dcw_partials", C.POINTER(C.c_void_p)), ("enc_work", C.c_void_p)]
+
+
+    def __init__(self, *a, **kw):             # positional arguments start at T
+        super().__init__(*((self.MAGIC,) + a if a else a), **kw)
+        self.magic = self.MAGIC
 
 
 class RnnBptt(_SizedStruct):

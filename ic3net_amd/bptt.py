@@ -16,6 +16,11 @@ products are plain library GEMMs (hipBLASLt fp32 MFMA through torch.mm / addmm_:
 transposes — there is nothing to fuse into them that the HBM traffic of their operands would notice); everything
 pointwise or sparse is a HIP kernel of libic3rollout.
 
+comm_passes > 1 (round 18): a lock-step window of such a policy runs no library product — _backward_window_multipass re-evaluates the
+inner passes of all steps window-wide (ops.policy_forward_record) and differentiates them through ops.bptt_passes_backward, in chunks
+of whole steps; PP-hard with 2 passes at 8192 envs: 144-146 ms per update instead of 222-223 (profiles/r18/multipass_window.txt).
+Collection-mode windows of these policies keep the per-step loop above (_backward_episode_multipass).
+
 Cost per step (PP-hard): forward 0.30 GFLOP-equivalents of one gate GEMM, backward = recompute (1x) + input gradient (1x)
 + weight gradient (1x): fp32 arithmetic bounds the update at ~4x the rollout's matrix work.
 """
@@ -294,6 +299,9 @@ def backward_episode(args, net, raw, rec, d_out, acc, carry=None):
     if not rec.recurrent:
         return _backward_episode_commnet(args, net, raw, rec, d_out, acc)
     if net.comm_passes > 1:
+        if _multipass_window_ok(args, net, raw, rec, d_out):
+            return _backward_window_multipass(args, net, raw, rec, d_out, acc, carry)
+        net.multipass_loop_backwards = getattr(net, 'multipass_loop_backwards', 0) + 1
         return _backward_episode_multipass(args, net, raw, rec, d_out, acc, carry)
     fc = net._fused_cache()
     T, R, H = rec.n, rec.hs.shape[1], rec.hs.shape[2]
@@ -765,6 +773,133 @@ def _backward_episode_multipass(args, net, raw, rec, d_out, acc, carry=None):
         dwt, db = raw.encode_backward(denc, rec.snaps[t], want_bias=True)
         acc['wt'].add_(dwt)
         acc['enc_bias'].add_(db)
+    return (dh_rec, dc_rec)
+
+
+MULTIPASS_WINDOW_DEFAULT = True       # args.multipass_window_backward where the flag is absent (main.py carries the same default)
+
+
+def _multipass_ring_floats(H, P):
+    """Floats per row of one chunk step of _backward_window_multipass: per pass the gate record 4H, the inp rows, h and c H each and
+    the dxh ring 2H; slot 0 of the h ring and the encoder ring H each."""
+    return P * (8 * H + ops.record_xh_width(H)) + 2 * H
+
+
+def _multipass_chunk_steps(dev, T, R, H, P, most=0):
+    """Whole steps per chunk of _backward_window_multipass — the largest count for which every launch stays inside its 32-bit limits
+    (a chunk's rows x 4H floats below 4 GB: the recording forward and the gate launch's buffer offsets; rows below 2^31 - 2^16: the
+    encoder's window stage) and the chunk's rings inside what _ring_fits grants; at most `most` when that is > 0; 0: not even one."""
+    tc = min(T, (2 ** 32 - 1) // (R * 4 * H * 4), (2 ** 31 - 2 ** 16 - 1) // R)
+    if dev.type == 'cuda':
+        tc = min(tc, (device_room(dev) // 4) // (R * _multipass_ring_floats(H, P) * 4))
+    return max(min(tc, most) if most > 0 else tc, 0)
+
+
+def _multipass_window_ok(args, net, raw, rec, d_out):
+    """The recurrent LSTM policy with comm_passes > 1 on a lock-step window: hid_size 64 / 128 / 256 (a zero-padded twin at the twin's
+    size), at most 16 output columns, the split planes of both directions in the fused cache, the native loop and
+    args.multipass_window_backward on, the library's answer for this env (the encoder backward's window form) and room for at least
+    one step's rings: _backward_window_multipass."""
+    if rec.stream is not None or not rec.recurrent or rec.n < 1 or d_out.shape[-1] > 16 or not d_out.is_cuda:
+        return False
+    if not bool(getattr(args, 'bptt_native_loop', True)) or not bool(getattr(args, 'multipass_window_backward', MULTIPASS_WINDOW_DEFAULT)):
+        return False
+    H, N = rec.hs.shape[2], net.nagents
+    if H not in (64, 128, 256) or net.hid_size != H or N > 64 or not hasattr(net, 'f_module') or not hasattr(raw, '_h'):
+        return False
+    fc = net._fused_cache()
+    if fc.get('ps_l_wp3') is None or fc.get('ps_l_wp3_bwd') is None or fc.get('ps_c_wp') is None:
+        return False
+    if not _enc_window(args, raw, H) or not ops.bptt_passes_backward_supported(raw, H, net.comm_passes):
+        return False
+    return _multipass_chunk_steps(rec.hs.device, rec.n, rec.hs.shape[1], H, net.comm_passes) >= 1
+
+
+def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_chunk_steps=0, dgates_out=None):
+    """_backward_episode_multipass for a lock-step window on HIP launches alone.  (h, c) entering every step is recorded, so the inner
+    passes of all steps are independent of each other: the window is walked in chunks of whole steps, last chunk first, and per chunk
+      Tc x raw.encode_at              encoder(obs) + encoder.bias + C_0.bias of every snapshot into a ring
+      P x ops.policy_forward_record   pass i over the Tc x E stacked envs, slot i of the (h, c) ring -> slot i + 1 (slot 0: the record's
+                                      hs / cs), its activated gates and inp rows kept; C_i.bias - C_0.bias added inside the launch
+      ops.bptt_passes_backward        per (step, pass), last first: the cell's derivative in place on the gate record + the input
+                                      gradient, the communication backward; the encoder's window stage once per pass behind the loop
+      ops.lstm_weight_grad            [W_ih | W_hh]'s gradient over the chunk's P x Tc x R rows, added
+    dh / dc carry from chunk to chunk; the heads' gradient is one pass over the window beside the chain.  Behind the chunks: one
+    encoder finish, the bias partials of all passes, each pass's dC_i partials, and C_i.bias's gradient read off pass i's bias
+    partials — the column sum of pass i's d inp is (the column sum of its dgates) . W_ih.  max_chunk_steps > 0 bounds the chunk (tests); dgates_out (P, T, R, 4H) receives every chunk's dgates (tests)."""
+    fc = net._fused_cache()
+    P = net.comm_passes
+    T, R, H = rec.n, rec.hs.shape[1], rec.hs.shape[2]
+    N = net.nagents
+    E = R // N
+    dev = rec.hs.device
+    mode_avg = getattr(args, 'comm_mode', 'avg') == 'avg'
+    mask_zero = bool(args.comm_mask_zero)
+    heads = args.naction_heads
+    # (lock-step windows only — _multipass_window_ok: nothing arrives from a later window, dh / dc start at zero)
+    assert rec.stream is None and carry is None, "a carried gradient would be dropped: collection-mode windows keep the per-step loop"
+    Tc = _multipass_chunk_steps(dev, T, R, H, P, max_chunk_steps)
+    assert Tc >= 1, "no room for one step's rings (_multipass_window_ok answers first)"
+    xw = ops.record_xh_width(H)
+    empty = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+    zeros = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
+    enc, gates, inp = empty(Tc, R, H), empty(P, Tc, R, 4 * H), empty(P, Tc, R, xw)
+    hring, cring, dxh = empty(P + 1, Tc, R, H), empty(P, Tc, R, H), empty(P, Tc, R, 2 * H)     # cring[i]: c LEAVING pass i
+    dh_rec, dc_rec = zeros(R, H), zeros(R, H)
+    bias_parts = zeros(P, (R + 63) // 64, 4 * H)
+    dcw_parts = None if mask_zero else zeros(P, ops.comm_backward_partials(E, N), H, H)
+    c_weights = None if mask_zero else [m.weight.detach() for m in net.C_modules]
+    cuts = _Cuts(args, rec, T, E, N, dev)                         # (lock-step: the detach points; no row factors, no carry)
+    dhead = _dhead_rows(d_out, T)
+    work = acc.setdefault('_work', {})
+
+    def stacked(ms):                                              # Tn entries (E, N) or None -> (Tn x E, N), None: everyone
+        if all(m is None for m in ms):
+            return None
+        ones = next(m for m in ms if m is not None).new_ones((E, N))
+        return torch.stack([m if m is not None else ones for m in ms]).contiguous()
+    with _heads_grad_beside(args, rec, d_out, acc, T, R, H):
+        first = True
+        for t1 in range(T, 0, -Tc):
+            t0 = max(t1 - Tc, 0)
+            Tn = t1 - t0
+            for k in range(Tn):
+                raw.encode_at(rec.snaps[t0 + k], fc['wt'], fc['enc_bias'], out=enc[k], loc_table=fc['loc_table'])
+            alive, gate = rec.alive[t0:t1], rec.gate[t0:t1]
+            alive_st, gate_st = stacked(alive), stacked(gate)
+            hring[0, :Tn].copy_(rec.hs[t0:t1])
+            cs = [rec.cs[t0:t1]] + [cring[i, :Tn] for i in range(P - 1)]
+            for i in range(P):
+                ops.policy_forward_record(fc, H, heads, mode_avg, mask_zero, enc[:Tn].view(Tn * R, H), Tn * E, N,
+                                          hring[i, :Tn].view(Tn * R, H), cs[i].reshape(Tn * R, H), hring[i + 1, :Tn].view(Tn * R, H),
+                                          cring[i, :Tn].view(Tn * R, H), alive_st, gate_st, gates[i, :Tn].view(Tn * R, 4 * H),
+                                          inp[i, :Tn].view(Tn * R, xw), pass_index=i, enc_add=fc.get('enc_dbias_p%d' % i) if i else None)
+            ops.bptt_passes_backward(raw, Tn, E, N, H, [gates[i, :Tn] for i in range(P)], [hring[i, :Tn] for i in range(P)], cs,
+                                     dhead[t0:t1], rec.snaps[t0:t1], alive, gate, fc['ps_l_wp3_bwd'], fc['w_heads'], c_weights, dh_rec,
+                                     dc_rec, [dxh[i, :Tn] for i in range(P)], [bias_parts[i] for i in range(P)],
+                                     None if mask_zero else [dcw_parts[i] for i in range(P)], mode_avg=mode_avg, comm_zero=mask_zero,
+                                     detach_gap=cuts.gap, t_first=t0, enc_first=first)
+            first = False
+            if dgates_out is not None:
+                dgates_out[:, t0:t1].copy_(gates[:, :Tn])
+            split = bool(getattr(args, 'gate_split', True))
+            if Tn == Tc:                                          # the chunk's P x Tc x R rows in one launch
+                ops.lstm_weight_grad(inp, hring[:P], gates, acc['w_cat_t'], accumulate=True, work=work, split=split)
+            else:                                                 # (a short last chunk: the passes' rows are not one block)
+                for i in range(P):
+                    ops.lstm_weight_grad(inp[i, :Tn], hring[i, :Tn], gates[i, :Tn], acc['w_cat_t'], accumulate=True, work=work, split=split)
+        dwt, db = raw.encode_backward_window_finish(H, want_bias=True)
+        acc['wt'].add_(dwt)
+        acc['enc_bias'].add_(db)
+        bsum = bias_parts.sum(1)                                  # (P, 4H): the column sums of every pass's dgates
+        acc['b_cat'].add_(bsum.sum(0))
+        w_ih_t = fc['w_cat_t'][:H]                                # (H, 4H) = W_ih^T
+        for i in range(P):
+            acc['c_b'][i].add_(torch.mv(w_ih_t, bsum[i]))
+            if not mask_zero:
+                acc['c_w_p'][i].add_(dcw_parts[i].sum(0))
+    net.multipass_window_backwards = getattr(net, 'multipass_window_backwards', 0) + 1
+    net.multipass_window_chunk = Tc
     return (dh_rec, dc_rec)
 
 

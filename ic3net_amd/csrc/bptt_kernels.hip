@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <vector>
 
 #include "enc_bwd.hpp"
@@ -763,7 +764,112 @@ static int encoder_tail(ic3_env* env, const int32_t* snaps, int64_t snap_words, 
     }
     return 0;
 }
+
+// One LSTM cell of a window's backward on the rows of Ec envs — what ic3_bptt_backward issues per (step, chain) and
+// its passes form (an ic3_bptt_passes descriptor) per (step, pass): ic3_lstm_gates_backward_given in place on the cell's gate record (the heads' share where
+// dhead is given; `cut`: nothing arrives through dh / dc), then ic3_comm_backward, which leaves in dh what the cell in front receives.
+struct BpttCell {
+    float* gates;
+    const float* c_prev;
+    const float* h_prev;
+    float* dh;
+    float* dc;
+    bool cut;
+    float* dxh;
+    float* dbias;
+    const float* row_live;
+    const float* row_keep;
+    const float* dhead;
+    const float* w_heads;
+    int OT;
+    const void* lstm_wp3_bwd;
+    const int32_t* alive;
+    const int32_t* gate;
+    const float* c_weight;
+    const float* out_scale;
+    float* dcw;
+    hipEvent_t ev0, ev1;                                         // recorded in front of / behind the gate launch, or null
+};
+static int bptt_cell_backward(const char* fn, const BpttCell& q, int Ec, int N, int H, int mode_avg, int comm_zero, hipStream_t sc)
+{
+    ic3_stream scv = (ic3_stream)sc;
+    if (q.ev0 && hipEventRecord(q.ev0, sc) != hipSuccess) return fail(-5, std::string(fn) + ": hipEventRecord of a gate event failed");
+    int rc = ic3_lstm_gates_backward_given(q.gates, nullptr, 0, nullptr, q.lstm_wp3_bwd, q.c_prev, q.cut ? nullptr : q.dh,
+                                           q.cut ? nullptr : q.dc, q.gates, q.dc, q.dbias, 1, q.dxh, q.row_live, q.row_keep, q.dhead,
+                                           q.dhead ? q.w_heads : nullptr, q.OT, Ec * N, H, scv);
+    if (rc < 0) return rc;
+    if (q.ev1 && hipEventRecord(q.ev1, sc) != hipSuccess) return fail(-5, std::string(fn) + ": hipEventRecord of a gate event failed");
+    return ic3_comm_backward(q.dxh, 2 * H, q.h_prev, q.alive, q.gate, q.c_weight, q.out_scale, q.dh, q.dcw, 1, Ec, N, H, mode_avg,
+                             comm_zero, scv);
+}
 }  // namespace ic3
+
+// ---- ic3_bptt_backward on an ic3_bptt_passes descriptor ----------------------------------------------
+// comm_passes = P > 1 (comm.py:179-218): a step is P chained LSTM cells on one snapshot, one pair of masks and one encoder output;
+// pass i has its own C_i, only the last pass feeds the heads, only pass 0 touches the previous step.  The backward of a pass is the
+// cell ic3_bptt_backward issues per step (bptt_cell_backward), on the records the recording ic3_policy_forward left: for t = T - 1 .. 0,
+// i = P - 1 .. 0 — dhead on the last pass only, a detach point cuts what arrives at the last pass only, the communication backward
+// of pass i leaves in dh what pass i - 1 (step t - 1 for i = 0) receives.  The encoder is linear in its input gradient, which is the
+// sum of the passes' d inp: its window stage runs once per pass over that pass's ring and accumulates.
+static int bptt_passes_backward(ic3_env* env, const ic3_bptt_passes* b, ic3_stream stream)
+{
+    using namespace ic3;
+    if (const int rc = window_open("ic3_bptt_backward (ic3_bptt_passes)", "ic3_bptt_passes", env, b, ic3_bptt_backward_supported,
+                                   "hid_size 64 / 128 / 256, <= 64 agents, a grid whose encoder backward runs in its partial-sums form",
+                                   false);
+        rc < 0)
+        return rc;
+    const int T = b->T, E = b->E, N = b->N, H = b->H, P = b->passes;
+    if (P < 2) return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): passes >= 2 (one pass: ic3_bptt_backward)");
+    if (ic3_env_encode_backward_window_work(env, H) <= 0)
+        return fail(-38, "ic3_bptt_backward (ic3_bptt_passes): needs a configuration with ic3_env_encode_backward_window (the ring form)");
+    if (!b->gates || !b->hs || !b->cs || !b->dhead || !b->snaps || !b->lstm_wp3_bwd || !b->w_heads || !b->dh || !b->dc || !b->dxh ||
+        !b->dbias_partials || !b->enc_work || b->t_first < 0)
+        return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): null argument");
+    if (!b->comm_zero && (!b->c_weight || !b->dcw_partials)) return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): the passes' C.weight and partials");
+    const long long R = (long long)E * N;
+    if (b->dxh_step < R * 2 * H) return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): dxh_step >= E * N * 2 * hid_size (the ring form)");
+    for (int i = 0; i < P; ++i) {
+        if (!b->gates[i] || !b->hs[i] || !b->cs[i] || !b->dxh[i] || !b->dbias_partials[i] ||
+            (!b->comm_zero && (!b->c_weight[i] || !b->dcw_partials[i])))
+            return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): null argument of pass " + std::to_string(i));
+    }
+    // (the loop runs in place on the records: what a launch would refuse is refused here, before the first one)
+    if (R * 4 * H * 4 >= (1ll << 32))
+        return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): rows * 4 * hid_size floats must stay below 4 GB (the gate launch's 32-bit buffer "
+                         "offsets)");
+    hipStream_t s = (hipStream_t)stream;
+    for (int t = T - 1; t >= 0; --t) {
+        const bool detached = b->detach_gap > 0 && (b->t_first + t + 1) % b->detach_gap == 0;
+        for (int i = P - 1; i >= 0; --i) {
+            const bool last = i == P - 1;
+            BpttCell q{};
+            q.gates = b->gates[i] + (size_t)t * R * 4 * H;
+            q.c_prev = b->cs[i] + (size_t)t * R * H;
+            q.h_prev = b->hs[i] + (size_t)t * R * H;
+            q.dh = b->dh;
+            q.dc = b->dc;
+            q.cut = detached && last;
+            q.dxh = b->dxh[i] + (size_t)t * (size_t)b->dxh_step;
+            q.dbias = b->dbias_partials[i];
+            q.dhead = last ? b->dhead + (size_t)t * R * b->OT : nullptr;
+            q.w_heads = b->w_heads;
+            q.OT = b->OT;
+            q.lstm_wp3_bwd = b->lstm_wp3_bwd;
+            q.alive = (b->alive && b->alive[t]) ? b->alive[t] : nullptr;
+            q.gate = (b->gate && b->gate[t]) ? b->gate[t] : nullptr;
+            q.c_weight = b->comm_zero ? nullptr : b->c_weight[i];
+            q.dcw = b->comm_zero ? nullptr : b->dcw_partials[i];
+            if (const int rc = bptt_cell_backward("ic3_bptt_backward (ic3_bptt_passes)", q, E, N, H, b->mode_avg, b->comm_zero, s); rc < 0) return rc;
+        }
+    }
+    for (int i = 0; i < P; ++i) {
+        const int rc = ic3_env_encode_backward_window(env, b->snaps, b->snap_words, T, b->dxh[i], 2 * H, b->dxh_step, H, b->enc_work,
+                                                      (i == 0 && b->enc_first) ? 1 : 0, stream);
+        if (rc < 0) return rc;
+    }
+    return 0;
+}
 
 // envs [0, E1) run on the caller's stream, [E1, E) on the library's second stream (ic3_bptt.two_chains): E1 * N a multiple of 64,
 // so that the gate launch's row tiles — and with them its bias partials — do not straddle the border
@@ -776,6 +882,11 @@ extern "C" int ic3_bptt_first_chain_envs(int E, int N)
 extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream stream)
 {
     using namespace ic3;
+    // (both descriptors start with struct_size; the passes form carries its magic in the next word, where an ic3_bptt holds T.  A
+    //  tagged descriptor must have the passes struct's size exactly (window_open refuses it otherwise); an untagged one is an ic3_bptt)
+    static_assert(offsetof(ic3_bptt_passes, magic) == offsetof(ic3_bptt, T), "the tag sits where ic3_bptt holds T");
+    if (b && (uint32_t)b->T == IC3_BPTT_PASSES_MAGIC)
+        return bptt_passes_backward(env, reinterpret_cast<const ic3_bptt_passes*>(b), stream);
     if (const int rc = window_open("ic3_bptt_backward", "ic3_bptt", env, b, ic3_bptt_backward_supported,
                                    "hid_size 64 / 128 / 256, <= 64 agents, a grid whose encoder backward runs in its partial-sums form",
                                    false);
@@ -820,33 +931,37 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
     for (int t = T - 1; t >= 0; --t) {
         for (int ch = 0; ch < nch; ++ch) {
             const int e0 = ch ? E1 : 0, Ec = ch ? E - E1 : E1;
-            const size_t r0 = (size_t)e0 * N, Rc = (size_t)Ec * N;
+            const size_t r0 = (size_t)e0 * N;
             hipStream_t sc = ch ? side->stream : s;
-            ic3_stream scv = (ic3_stream)sc;
-            float* dh = b->dh + r0 * H;
-            float* dc = b->dc + r0 * H;
             // trainer.py:56-60: (h_t, c_t) were handed on detached — the gate launch reads zeros for dL/d(h_t, c_t) (null inputs: an
             // empty descriptor instead of two memsets and their reads)
             const bool detached = b->detach_gap > 0 && (t + 1) % b->detach_gap == 0;
-            float* g = b->gates + ((size_t)t * R + r0) * 4 * H;
-            float* dxh = b->dxh + (size_t)t * (size_t)b->dxh_step + r0 * 2 * H;
-            if (b->gate_events && ch == 0 && hipEventRecord((hipEvent_t)b->gate_events[2 * t], sc) != hipSuccess)
-                return join(fail(-5, "ic3_bptt_backward: hipEventRecord of a gate event failed"));
-            int rc = ic3_lstm_gates_backward_given(g, nullptr, 0, nullptr, b->lstm_wp3_bwd, b->cs + ((size_t)t * R + r0) * H,
-                                                   detached ? nullptr : dh, detached ? nullptr : dc, g,
-                                                   dc, b->dbias_partials + (r0 / 64) * 4 * H, 1, dxh,
-                                                   b->row_live ? b->row_live + (size_t)t * R + r0 : nullptr,
-                                                   b->row_keep ? b->row_keep + (size_t)t * R + r0 : nullptr,
-                                                   b->dhead + ((size_t)t * R + r0) * b->OT, b->w_heads, b->OT, (int)Rc, H, scv);
-            if (rc < 0) return join(rc);
-            if (b->gate_events && ch == 0 && hipEventRecord((hipEvent_t)b->gate_events[2 * t + 1], sc) != hipSuccess)
-                return join(fail(-5, "ic3_bptt_backward: hipEventRecord of a gate event failed"));
-            const float* out_scale = (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R + r0 : nullptr;
-            float* dcw = b->dcw_partials;
-            if (dcw && ch) dcw += (size_t)ic3_comm_backward_partials(E1, N) * H * H;
-            rc = ic3_comm_backward(dxh, 2 * H, b->hs + ((size_t)t * R + r0) * H, (b->alive && b->alive[t]) ? b->alive[t] + r0 : nullptr,
-                                   (b->gate && b->gate[t]) ? b->gate[t] + r0 : nullptr, b->c_weight, out_scale, dh, dcw, 1, Ec, N, H,
-                                   b->mode_avg, b->comm_zero, scv);
+            BpttCell q{};
+            q.gates = b->gates + ((size_t)t * R + r0) * 4 * H;
+            q.c_prev = b->cs + ((size_t)t * R + r0) * H;
+            q.h_prev = b->hs + ((size_t)t * R + r0) * H;
+            q.dh = b->dh + r0 * H;
+            q.dc = b->dc + r0 * H;
+            q.cut = detached;
+            q.dxh = b->dxh + (size_t)t * (size_t)b->dxh_step + r0 * 2 * H;
+            q.dbias = b->dbias_partials + (r0 / 64) * 4 * H;
+            q.row_live = b->row_live ? b->row_live + (size_t)t * R + r0 : nullptr;
+            q.row_keep = b->row_keep ? b->row_keep + (size_t)t * R + r0 : nullptr;
+            q.dhead = b->dhead + ((size_t)t * R + r0) * b->OT;
+            q.w_heads = b->w_heads;
+            q.OT = b->OT;
+            q.lstm_wp3_bwd = b->lstm_wp3_bwd;
+            q.alive = (b->alive && b->alive[t]) ? b->alive[t] + r0 : nullptr;
+            q.gate = (b->gate && b->gate[t]) ? b->gate[t] + r0 : nullptr;
+            q.c_weight = b->c_weight;
+            q.out_scale = (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R + r0 : nullptr;
+            q.dcw = b->dcw_partials;
+            if (q.dcw && ch) q.dcw += (size_t)ic3_comm_backward_partials(E1, N) * H * H;
+            if (b->gate_events && ch == 0) {
+                q.ev0 = (hipEvent_t)b->gate_events[2 * t];
+                q.ev1 = (hipEvent_t)b->gate_events[2 * t + 1];
+            }
+            const int rc = bptt_cell_backward("ic3_bptt_backward", q, Ec, N, H, b->mode_avg, b->comm_zero, sc);
             if (rc < 0) return join(rc);
         }
         if (b->dxh_step) continue;                               // (the encoder's first stage: once, behind the loop)

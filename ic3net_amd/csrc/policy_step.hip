@@ -163,10 +163,14 @@ __device__ __forceinline__ void reload_args(StepArgs& a)
 // kept copy would be 32 registers or 32 KB of LDS the kernel does not have), takes h from the h half of the A tile where the
 // previous pass's cell epilogue left it and c from the registers it was computed in, and only the LAST pass stores h', c',
 // issues the obs zero fill and runs the back half.  MP = 0 compiles to exactly the one-pass kernel.
-template <int H, int KIND, int SPLIT = 0, int MP = 0>
+// REC = 1 (ic3_policy_forward on an ic3_policy_record): the caller's-encoder-output kernel (KIND 0, split product) as a RECORDING inner pass — the
+// record stores of the env instantiations (inp rows behind S7, activated gates in the cell epilogue) and an optional [H] row
+// (`enc_bias`, which KIND 0 does not read otherwise) added to every enc row as it is read.  REC = 0 compiles to what it was.
+template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0>
 __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(const StepArgs a_in)
 {
     static_assert(!MP || (SPLIT && KIND != 0), "the in-launch pass loop exists for the split gate product on an env handle");
+    static_assert(!REC || (SPLIT && KIND == 0 && !MP), "the recording pass exists for the split gate product on a caller's encoder output");
     constexpr int K = 2 * H, LDA = K + 4, LDA4 = LDA / 4, BM = 64, NT = 2 * H, NW = H / 32, H4 = H / 4;
     IC3_DYNAMIC_LDS(float, smem);
     float* const As = smem;                                      // [BM][LDA]: cols [0,H) enc / comm / inp, [H,2H) h / h'
@@ -352,6 +356,12 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                 const int el = div_small(row, invN), aa = row - el * N;
                 if constexpr (KIND == 0) {
                     v = *reinterpret_cast<const ps_f32x4*>(a.enc_in + (r0 + row) * H + 4 * c4);
+                    if constexpr (REC != 0) {
+                        if (a.enc_bias) {   // (uniform) pass i > 0 of a step: C_i.bias - C_0.bias on top of the caller's rows
+                            const ps_f32x4 b = a.enc_bias[c4];
+                            v = ps_f32x4{ v[0] + b[0], v[1] + b[1], v[2] + b[2], v[3] + b[3] };
+                        }
+                    }
                 } else if constexpr (KIND == IC3_ENV_PP) {
                     v = pp_encode_row_t(sr + el * total, sc + el * total, ptab + el * nsegE, aa, c4, H4, WW,
                                         a.pp.dim * a.pp.dim + 4, a.pp.dim, encW, enc_bias_now, encL, rmask[row]);
@@ -510,7 +520,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                     As[lr * LDA + col] = accC[rt][reg];
                 }
             }
-            if constexpr (KIND != 0 && MP == 0) {
+            if constexpr ((KIND != 0 && MP == 0) || REC != 0) {
                 if (a.xh_out) {   // (uniform; ic3_env_set_record_out) the same values -> the inp half of the record's [inp | h] rows
                     // (hid 256: inp rows alone, row stride H — the window backward reads h from the (h, c) record, and the wide
                     //  layout would not fit beside the gate record at the shapes hid 256 is trained at)
@@ -857,7 +867,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
             const int ze = obs_here ? a.zepi : 0;
             // (the host arms gates_out for the SPLIT, one-pass, env instantiations only, and leaves the epilogue no zero-store
             //  slots then)
-            constexpr bool GS_BUILT = SPLIT == 1 && MP == 0 && KIND != 0;
+            constexpr bool GS_BUILT = SPLIT == 1 && MP == 0 && (KIND != 0 || REC != 0);
             if (GS_BUILT && a.gates_out) {
                 if constexpr (GS_BUILT) cell(std::integral_constant<int, 0>{}, std::true_type{});
             } else if (ze <= 0) cell(std::integral_constant<int, 0>{}, std::false_type{});
@@ -1073,7 +1083,7 @@ static double tiles_cost(const TileCosts& tc, int k_full, int k_half)
     return c + (k_half / 2) * tc.half_pair + (k_half & 1) * tc.lone_half;
 }
 
-template <int H, int KIND, int SPLIT = 0, int MP = 0>
+template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0>
 static int launch_step(const StepArgs& a, int tiles, size_t lds, hipStream_t s, hipEvent_t ev0 = nullptr,
                        hipEvent_t ev1 = nullptr);
 // words of the small LDS arrays behind the A tile: sm, sscale, sact, rmask [64 each], sfm [4], sep, sts [64 each], shb [16], slb [4H]
@@ -1231,14 +1241,14 @@ static int plan_tiles(StepArgs& a, int H, const ic3_policy* p, hipStream_t s)
     return a.ntiles;
 }
 
-template <int H, int KIND, int SPLIT, int MP>
+template <int H, int KIND, int SPLIT, int MP, int REC>
 static int launch_step(const StepArgs& a, int tiles, size_t lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     // one workgroup per tile, dispatched in tile order (full tiles first, see plan_tiles): the hardware dispatcher
     // balances them over the CUs (a fixed resident set walking a strided tile list was measured slower)
     const dim3 grid(tiles), block(2 * H);
-    if (ev0 || ev1) return launch_kernel_timed(policy_step_kernel<H, KIND, SPLIT, MP>, grid, block, lds, s, ev0, ev1, a);
-    return launch_kernel(policy_step_kernel<H, KIND, SPLIT, MP>, grid, block, lds, s, a);
+    if (ev0 || ev1) return launch_kernel_timed(policy_step_kernel<H, KIND, SPLIT, MP, REC>, grid, block, lds, s, ev0, ev1, a);
+    return launch_kernel(policy_step_kernel<H, KIND, SPLIT, MP, REC>, grid, block, lds, s, a);
 }
 // the env instantiation of the handle's kind
 template <int H, int SPLIT, int MP = 0>
@@ -1267,10 +1277,67 @@ static int policy_step_lds(const ic3_env* env, int H)
 extern "C" int ic3_policy_step_supported(const ic3_env* env, int H) { return policy_step_lds(env, H); }
 
 
+// ic3_policy_forward on an ic3_policy_record: a recording inner pass over a chunk of whole steps (the window backward of
+// comm_passes > 1 policies re-evaluates the passes the one-launch rollout keeps in LDS): (h, c) -> (h_out, c_out), the activated
+// gates and the inp rows.  
+static int policy_forward_record(const ic3_policy_record* r, const float* enc, int E, int N, const float* h_in, const float* c_in,
+                                 const int32_t* alive_in, const int32_t* comm_in, ic3_stream stream)
+{
+    ic3_policy base = r->policy;                                 // (the plain descriptor of an inner pass, for what checks its size)
+    base.struct_size = sizeof(ic3_policy);
+    base.inner_pass = 1;
+    const ic3_policy* const p = &base;
+    const float* const enc_add = r->enc_add;
+    float* const h_out = r->h_out;
+    float* const c_out = r->c_out;
+    float* const gates = r->gates;
+    float* const inp = r->inp;
+    if (!enc || !h_in || !c_in || !h_out || !c_out || !gates || !inp || E <= 0 || N <= 0)
+        return fail(-22, "ic3_policy_forward (ic3_policy_record): bad arguments");
+    const int H = p->H;
+    if ((H != 64 && H != 128 && H != 256) || N > 64)
+        return fail(-38, "ic3_policy_forward (ic3_policy_record): needs hid_size 64/128/256 and <= 64 agents per env");
+    if (!p->gate_split || !p->lstm_wp3) return fail(-38, "ic3_policy_forward (ic3_policy_record): needs gate_split with lstm_wp3");
+    if ((long long)E * N * 4 * H * 4 >= (1ll << 32))
+        return fail(-22, "ic3_policy_forward (ic3_policy_record): rows * 4 * hid_size floats must stay below 4 GB (the 32-bit buffer offsets of the "
+                         "launches that read the gate record)");
+    StepArgs a{};
+    int rc = fill_policy(a, p, "ic3_policy_forward (ic3_policy_record)");
+    if (rc) return rc;
+    if (a.npass > 1) return fail(-38, "ic3_policy_forward (ic3_policy_record): one call per pass (npasses < 2)");
+    a.inner = 1;                                                 // the launch ends behind the LSTM cell
+    a.enc_in = enc;
+    a.enc_bias = reinterpret_cast<const ps_f32x4*>(enc_add);
+    a.h = const_cast<float*>(h_in);
+    a.c = const_cast<float*>(c_in);
+    a.h_out = h_out;
+    a.c_out = c_out;
+    a.gates_out = gates;
+    a.xh_out = inp;
+    a.alive_in = alive_in;
+    a.comm_in = comm_in;
+    a.E = E;
+    a.N = N;
+    a.EPT = 64 / N;
+    a.G = 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int tiles = plan_tiles(a, H, p, s);
+    const size_t lds = ((size_t)64 * (2 * H + 4) + ps_lds_small(H)) * sizeof(float);
+    return with_hid(H, [&](auto hid) { return launch_step<decltype(hid)::value, 0, 1, 0, 1>(a, tiles, lds, s); });
+}
+
 extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, int N, float* h, float* c,
                                   const int32_t* alive_in, const int32_t* comm_in, float* out, ic3_stream stream)
 {
     ic3::Range range_("ic3_policy_forward");
+    // (the first words of both descriptors are an ic3_policy's: the tag says which one this is, and a tagged one must have the
+    //  record's size exactly — anything else falls to the size check of ic3_policy below or is refused here)
+    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_POLICY_RECORD_PASS) {
+        if (p->struct_size != sizeof(ic3_policy_record))
+            return fail(-22, "ic3_policy_forward (ic3_policy_record): struct_size is " + std::to_string(p->struct_size) +
+                                 ", this library's ic3_policy_record has " + std::to_string(sizeof(ic3_policy_record)) + " bytes");
+        return policy_forward_record(reinterpret_cast<const ic3_policy_record*>(p), enc, E, N, h, c, alive_in, comm_in, stream);
+    }
     if (int src = check_policy_struct(p, "ic3_policy_forward")) return src;   // before any other field is read
     if (!p || !enc || !h || !c || (!out && !p->inner_pass) || E <= 0 || N <= 0)
         return fail(-22, "ic3_policy_forward: bad arguments");

@@ -56,7 +56,10 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  ('dist_backend', str, 'nccl'),     # 'nccl' = RCCL over xGMI; 'gloo' for several ranks on one GPU (tests)
                  # 1: the non-recurrent CommNet module's update runs window-wide launches (bptt._backward_window_commnet);
                  # 0: the per-step loop (bptt._backward_episode_commnet)
-                 ('commnet_window_backward', int, 1)]
+                 ('commnet_window_backward', int, 1),
+                 # 1: the update of a recurrent policy with comm_passes > 1 runs window-wide HIP launches
+                 # (bptt._backward_window_multipass); 0: the per-step loop (bptt._backward_episode_multipass)
+                 ('multipass_window_backward', int, 1)]
 
 
 def build_parser(argv):

@@ -359,6 +359,51 @@ def bptt_backward_supported(env, H):
     return bool(_lib.lib().ic3_bptt_backward_supported(env._h, int(H)))
 
 
+def bptt_passes_backward_supported(env, H, passes):
+    """bptt_passes_backward can run: what ic3_bptt_backward needs, the encoder backward's window form, at least two passes."""
+    return passes >= 2 and bptt_backward_supported(env, H) and env.encode_window_work(H) is not None
+
+
+def bptt_passes_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lstm_wp3_bwd, w_heads, c_weights, dh, dc, dxh,
+                         dbias_partials, dcw_partials, mode_avg=True, comm_zero=False, detach_gap=0, t_first=0, enc_first=True):
+    """ic3_bptt_backward on an ic3_bptt_passes descriptor: the backward through T recorded steps of a comm_passes = P > 1 policy (a window, or a chunk of whole
+    steps of one starting at its step t_first) as one host call.  Per pass i, lists of P tensors: gates[i] (T, R, 4H) — the record
+    ops.policy_forward_record left, dgates on return —, hs[i] / cs[i] (T, R, H) the state entering the pass, dxh[i] (T, R, 2H) the
+    ring of input gradients (written), dbias_partials[i] (ceil(R / 64), 4H) and dcw_partials[i] (comm_backward_partials(E, N), H, H)
+    added to, c_weights[i] (H, H) (dcw_partials / c_weights: None with comm_zero).  alive / gate: lists of T (E, N) int32 tensors or
+    None entries, or None.  The encoder's window stage runs behind the loop (finish: env.encode_backward_window_finish)."""
+    _need_cuda(dh, "bptt_passes_backward")
+    R = E * N
+    P = len(gates)
+    assert P >= 2 and len(hs) == len(cs) == len(dxh) == len(dbias_partials) == P
+    OT = _window_inputs(dhead, snaps, T, R)
+    assert _f32(dh, (R, H)) and _f32(dc, (R, H))
+    for i in range(P):
+        assert _f32(gates[i], T * R * 4 * H) and _f32(hs[i], T * R * H) and _f32(cs[i], T * R * H)
+        assert _f32(dxh[i], (T, R, 2 * H)) and _f32(dbias_partials[i], ((R + 63) // 64, 4 * H))
+    if not comm_zero:
+        assert len(c_weights) == len(dcw_partials) == P
+        assert all(_f32(c_weights[i], (H, H)) and _f32(dcw_partials[i], (comm_backward_partials(E, N), H, H)) for i in range(P))
+
+    def ptrs(ms, n, masks=False):
+        if ms is None or (masks and all(m is None for m in ms)):
+            return None
+        assert len(ms) >= n and (not masks or all(_mask(m, R) for m in ms[:n]))
+        return (C.c_void_p * n)(*[None if m is None else m.data_ptr() for m in ms[:n]])
+    arrays = dict(gates=ptrs(gates, P), hs=ptrs(hs, P), cs=ptrs(cs, P), dxh=ptrs(dxh, P), dbias_partials=ptrs(dbias_partials, P),
+                  c_weight=None if comm_zero else ptrs(c_weights, P), dcw_partials=None if comm_zero else ptrs(dcw_partials, P),
+                  alive=ptrs(alive, T, True), gate=ptrs(gate, T, True))          # (alive until the call has returned)
+    b = _lib.BpttPasses(T, E, N, H, OT, P, int(bool(mode_avg)), int(bool(comm_zero)), int(detach_gap), int(bool(enc_first)), int(t_first))
+    for name, arr in arrays.items():
+        setattr(b, name, C.cast(arr, C.POINTER(C.c_void_p)) if arr is not None else None)
+    _set_ptrs(b, dict(dhead=dhead, snaps=snaps, lstm_wp3_bwd=lstm_wp3_bwd, w_heads=w_heads, dh=dh, dc=dc))
+    b.snap_words = snaps.stride(0)
+    b.dxh_step = dxh[0].stride(0)
+    assert all(d.stride(0) == b.dxh_step for d in dxh)
+    b.enc_work = _enc_work(env, H, True)
+    check(_lib.lib().ic3_bptt_backward(env._h, C.byref(b), stream()))      # (its magic says which descriptor this is)
+
+
 def record_xh_width(H):
     """Row width of the inp record ic3_env_set_record_out writes: 2H ([inp | h] rows, the h half left to the backward) at hid
     64 / 128, H (inp rows alone) at hid 256."""
@@ -803,6 +848,27 @@ def policy_forward(fc, H, head_sizes, mode_avg, comm_zero, enc, E, N, h, c, aliv
     check(_lib.lib().ic3_policy_forward(C.byref(pol), ptr(enc), E, N, ptr(h), ptr(c), ptr(alive_in), ptr(comm_in),
                                         None if inner else ptr(out), stream()))
     return None if inner else out
+
+
+def policy_forward_record(fc, H, head_sizes, mode_avg, comm_zero, enc, E, N, h_in, c_in, h_out, c_out, alive_in, comm_in, gates, inp,
+                          pass_index=0, enc_add=None):
+    """ic3_policy_forward on an ic3_policy_record: communication pass `pass_index` of a comm_passes > 1 step as a recording inner pass over E envs (a
+    chunk of whole steps: Tc x E envs, masks stacked) — (h_in, c_in) -> (h_out, c_out) (E*N, H), the activated gates (E*N, 4H) and the
+    inp rows (E*N, record_xh_width(H)); enc (E*N, H) = encoder(x) + encoder.bias + C_0.bias, enc_add (H,) = C_i.bias - C_0.bias or
+    None.  Needs the split planes (fc['ps_l_wp3'])."""
+    _need_cuda(enc, "policy_forward_record")
+    R = E * N
+    assert _dense(enc, (R, H)) and _f32(enc_add, H, none_ok=True)
+    assert _dense(h_in, (R, H)) and _dense(c_in, (R, H)) and _dense(h_out, (R, H)) and _dense(c_out, (R, H))
+    assert _dense(gates, (R, 4 * H)) and _dense(inp, (R, record_xh_width(H)))
+    assert _mask(alive_in, R) and _mask(comm_in, R)
+    pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, encoder=False, pass_index=pass_index, inner=True)
+    rec = _lib.PolicyRecord()
+    C.memmove(C.addressof(rec), C.addressof(pol), C.sizeof(pol))
+    rec.struct_size, rec.inner_pass = C.sizeof(rec), rec.RECORD_PASS
+    _set_ptrs(rec, dict(h_out=h_out, c_out=c_out, gates=gates, inp=inp), enc_add=enc_add)
+    check(_lib.lib().ic3_policy_forward(C.cast(C.byref(rec), C.POINTER(_lib.Policy)), ptr(enc), E, N, ptr(h_in), ptr(c_in), ptr(alive_in),
+                                        ptr(comm_in), None, stream()))
 
 
 def policy_step_pass(env, fc, H, head_sizes, mode_avg, comm_zero, h, c, alive_in, comm_in, pass_index):

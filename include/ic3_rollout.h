@@ -490,6 +490,60 @@ int ic3_bptt_backward_supported(const ic3_env* env, int H);
 int ic3_bptt_first_chain_envs(int E, int N);
 int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream stream);
 
+/* The same backward for comm_passes = P >= 2 — ic3_bptt_backward handed the descriptor below in place of an ic3_bptt.  The
+ * descriptor is selected by its second word, magic = IC3_BPTT_PASSES_MAGIC (where an ic3_bptt holds T: no window has 1.4e9 steps),
+ * AND struct_size = sizeof(ic3_bptt_passes): a tagged descriptor of another size is refused with -EINVAL, an untagged one is an
+ * ic3_bptt and refused unless it has exactly that struct's size.  (ABI 601 is closed, see ic3_policy_record: a descriptor, not a
+ * symbol.)  Error messages begin "ic3_bptt_backward (ic3_bptt_passes)".  (comm.py:179-218: a step is P chained LSTM cells on one snapshot, one pair of masks and
+ * one encoder output; pass i mixes through C_modules[i], only the last pass feeds the heads, only pass 0 touches the previous step)
+ * over a window (or a chunk of whole steps of one) of T steps whose passes the recording ic3_policy_forward left, as ONE host call —
+ * for t = T - 1 .. 0 and i = P - 1 .. 0 the two launches ic3_bptt_backward issues per step:
+ *   ic3_lstm_gates_backward_given in place on pass i's gate record with c_prev = c_{t,i}; dhead / w_heads on the last pass only;
+ *     dh / dc NULL at a detach point, (t_first + t + 1) % detach_gap == 0, and there on the last pass only; the input gradient to
+ *     the ring slot of (t, i); the bias partials ADDED to pass i's;
+ *   ic3_comm_backward with h_{t,i}, step t's masks and C_i.weight, ADDED to pass i's dcw_partials — it leaves in dh what pass i - 1
+ *     (step t - 1 when i = 0) receives;
+ * and behind the loop the encoder's window stage (ic3_env_encode_backward_window, which accumulates) once per pass over that pass's
+ * ring; only the first of them starts the accumulation, and only with enc_first.  Finish with
+ * ic3_env_encode_backward_window_finish[_ordered].  Afterwards the caller runs ic3_lstm_weight_grad_wide over the P x T x R rows.
+ *   gates, hs, cs, dxh, dbias_partials, dcw_partials, c_weight: HOST arrays of P device pointers (any P >= 2; with shared weights
+ *   the c_weight entries are equal, the partials stay per pass) — gates[i] [T][R][4H] in: pass i's activated gates, out: dgates;
+ *   hs[i], cs[i] [T][R][H]: the state ENTERING pass i of every step (i = 0: the recorded (h, c) of the steps);  dxh[i]: a ring of T
+ *   slots [R][2H], dxh_step floats apart (>= R * 2H; written);  dbias_partials[i] [ceil(R / 64)][4H],  dcw_partials[i]
+ *   [ic3_comm_backward_partials(E, N)][H][H] (unused with comm_zero, as c_weight);  dhead [T][R][OT], snaps, alive / gate (HOST arrays
+ *   of T device pointers or NULL), lstm_wp3_bwd, w_heads, dh / dc, enc_work (ic3_env_encode_backward_window_work floats): as ic3_bptt.
+ * The call can run where ic3_bptt_backward_supported(env, H) answers 1 and ic3_env_encode_backward_window_work(env, H) > 0 — ask before
+ * anything is overwritten.
+ * -ENOSYS: what ic3_bptt_backward_supported refuses, or a configuration without ic3_env_encode_backward_window.  -EINVAL BEFORE the
+ * first launch (the records are untouched): a struct_size mismatch, passes < 2, a null argument, dxh_step below R * 2H, rows * 4 *
+ * hid_size floats at 4 GB or more.  One stream. */
+#define IC3_BPTT_PASSES_MAGIC 0x53534150u /* "PASS" */
+typedef struct ic3_bptt_passes {
+    uint32_t struct_size;   /* sizeof(ic3_bptt_passes) of the caller's header (checked with the tag: -EINVAL on mismatch) */
+    uint32_t magic;         /* IC3_BPTT_PASSES_MAGIC */
+    int32_t T, E, N, H, OT, passes;
+    int32_t mode_avg, comm_zero, detach_gap, enc_first;
+    int32_t t_first;        /* index, within its window, of this call's first step (a chunk of a window: the detach points) */
+    float* const* gates;
+    const float* const* hs;
+    const float* const* cs;
+    const float* dhead;
+    const int32_t* snaps;
+    int64_t snap_words;
+    const int32_t* const* alive;
+    const int32_t* const* gate;
+    const void* lstm_wp3_bwd;
+    const float* w_heads;
+    const float* const* c_weight;
+    float* dh;
+    float* dc;
+    float* const* dxh;
+    int64_t dxh_step;
+    float* const* dbias_partials;
+    float* const* dcw_partials;
+    float* enc_work;
+} ic3_bptt_passes;
+
 /* The backward through a window of T recorded steps of the IC / IRIC baselines' tanh recurrence (models.py:68-92, rnn_type 'MLP':
  * h_t = tanh(affine1(obs_t) + affine2(h_{t-1})), heads and value on h_t), last step first, as ONE host call — per step ONE launch:
  *   dh_t = dh + d_t . W_heads;  dz_t = dh_t * (1 - h_t^2) -> dz slot t;  dh <- (dz_t . A2) * row_keep[t - 1];  column sums of dz_t
@@ -735,6 +789,21 @@ typedef struct {
     const float* c_wp_pass[4];
     const float* enc_bias_pass[4];
 } ic3_policy;
+/* ic3_policy followed by the operands of the RECORDING inner pass: handed to ic3_policy_forward in place of an ic3_policy, with
+ * policy.inner_pass = IC3_POLICY_RECORD_PASS — the tag that selects this form — AND policy.struct_size = sizeof(ic3_policy_record):
+ * a tagged descriptor of any other size is refused with -EINVAL, and an untagged one is an ic3_policy, refused unless it has
+ * exactly that struct's size (a caller built against another header is never read as the other struct).  Why not an entry point of
+ * its own: ABI 601 is closed — tests/test_binding_cpu.py holds the binding to its 110 entry points and to the sizes of ic3_policy /
+ * ic3_bptt — so version 601 can gain a descriptor, not a symbol.  Every other entry point refuses this struct by its size. */
+#define IC3_POLICY_RECORD_PASS 2
+typedef struct ic3_policy_record {
+    ic3_policy policy;
+    const float* enc_add;
+    float* h_out;
+    float* c_out;
+    float* gates;
+    float* inp;
+} ic3_policy_record;
 
 /* The NON-recurrent CommNet module after the encoder (comm.py:127-129,179-205,220-224,228-239), every communication pass
  * in ONE launch:  x = tanh(enc);  h_0 = x;  h_{i+1} = tanh(x + f_modules[i](h_i) + C_modules[i](comm(h_i)));
@@ -888,6 +957,22 @@ int ic3_policy_step_supported(const ic3_env* env, int H); /* 0, or the LDS bytes
  * updated in place; p->enc_wt / enc_bias / loc_table are not read.  No draws, no env step.  H in {64,128,256}, N <= 64. */
 int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, int N, float* h, float* c, const int32_t* alive_in,
                        const int32_t* comm_in, float* out, ic3_stream stream);
+/* ic3_policy_forward as a RECORDING inner pass — p points to an ic3_policy_record: policy.inner_pass = IC3_POLICY_RECORD_PASS,
+ * policy.struct_size = sizeof(ic3_policy_record); an instantiation of its own of the same kernel: the launches above are untouched;
+ * error messages begin "ic3_policy_forward (ic3_policy_record)".  In this form the prototype's h / c are INPUTS and `out` is not
+ * read; what the call writes is named by the record: one communication pass of a comm_passes > 1 step — the mix, C, the gate product
+ * and the LSTM cell on the caller's enc rows, no heads, no draws, `out` is not read — that
+ *   reads (h, c) from the call's h / c [E*N][H], which keep their bits, and writes the new state to h_out / c_out [E*N][H] (the
+ *   same bits the call with ic3_policy.inner_pass leaves in h / c; h_out == h / c_out == c is allowed);
+ *   stores gates [E*N][4H] = the activated gates sigmoid(i) | sigmoid(f) | tanh(g) | sigmoid(o) its cell update used, and inp
+ *   = the inp rows (enc + C(comm), the left operand of the gate product) as ic3_env_set_record_out lays them out: row stride 2H at
+ *   hid_size 64 / 128 (the h half is not touched), H at 256.
+ * enc [E*N][H] = encoder(x) + encoder.bias + C_0.bias (what ic3_env_encode_at writes with ic3_policy.enc_bias);  enc_add [H] or
+ * NULL is added to every enc row as it is read — pass i > 0 hands C_i.bias - C_0.bias, so one encoder ring serves every pass.
+ * p->c_wp = pass i's packed C weight.  The "E" of a call may be a chunk of whole steps, Tc x E envs with the steps' alive_in /
+ * comm_in masks stacked to [Tc*E][N] (a step's alive mask absent: ones).  Needs ic3_policy.gate_split with lstm_wp3 (-ENOSYS
+ * otherwise, as for hid_size other than 64 / 128 / 256 or N > 64); E*N * 4H floats must stay below 4 GB and every output must be
+ * given (-EINVAL, before any launch: the 32-bit buffer offsets of the launches that read the gate record). */
 int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, float* c, const int32_t* alive_in,
                     const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
                     int32_t* alive, int32_t* is_completed, ic3_stream stream);

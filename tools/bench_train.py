@@ -1,7 +1,9 @@
 """Throughput of the update path Trainer.train_batch (rollout + compute_grad + RMSprop), PP-hard by default:
 python tools/bench_train.py [nenvs] [updates] [native|autograd] [workload] [dense_obs 0|1] [gate_split 0|1] [collection 0|1]   (default native: no-grad
 one-launch rollout + the explicit backward through time of ic3net_amd.bptt; autograd: the rollout keeps the autograd
-graph, rounds 1-2; dense_obs 0: the training rollout does not assemble observation rows nothing reads)."""
+graph, rounds 1-2; dense_obs 0: the training rollout does not assemble observation rows nothing reads).
+COMM_PASSES=<P> (with SHARE_WEIGHTS=1: one C for every pass) overrides the workload's communication passes; MULTIPASS_WINDOW=0 sends
+the update of such a policy through the per-step loop instead of bptt._backward_window_multipass (the line then says which ran)."""
 import os
 import sys
 import time
@@ -19,7 +21,14 @@ def main():
     dense = int(sys.argv[5]) if len(sys.argv) > 5 else 1
     split = int(sys.argv[6]) if len(sys.argv) > 6 else 1      # gate product: 1 exact bf16 split products (default), 0 fp32 MFMA
     coll = int(sys.argv[7]) if len(sys.argv) > 7 else 0       # 1: collection mode (args.auto_reset): E streams of whole episodes
-    tr, a = bench.build_trainer(wl, E, 0, 0, 0)
+    over = {}
+    if os.environ.get('COMM_PASSES'):
+        over['comm_passes'] = int(os.environ['COMM_PASSES'])
+        if os.environ.get('SHARE_WEIGHTS', '0') == '1':
+            over['share_weights'] = True
+    tr, a = bench.build_trainer(wl, E, 0, 0, 0, **over)
+    if over and 'MULTIPASS_WINDOW' in os.environ:            # A/B: the window backward of comm_passes > 1 policies against the loop
+        a.multipass_window_backward = os.environ['MULTIPASS_WINDOW'] == '1'
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
@@ -50,7 +59,11 @@ def main():
         steps += st['num_steps']
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    label = wl + (" (obs rows assembled in the rollout)" if a.train_dense_obs else "") + ("" if split else " (fp32 MFMA gate product)") + \
+    knet = tr._kernel_net()
+    passes = "" if not over else " comm_passes=%d%s (window backwards %d, chunk of %s steps; loop backwards %d)" % (
+        over['comm_passes'], " shared" if over.get('share_weights') else "", getattr(knet, 'multipass_window_backwards', 0),
+        getattr(knet, 'multipass_window_chunk', '-'), getattr(knet, 'multipass_loop_backwards', 0))
+    label = wl + passes + (" (obs rows assembled in the rollout)" if a.train_dense_obs else "") + ("" if split else " (fp32 MFMA gate product)") + \
         (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "")
     print("train_batch [%s] %s E=%d: %.0f env-steps/s = %.2f M agent-steps/s (%.2f s per update of %d env-steps), "
           "peak mem %.1f GB, gemm %s" % (mode, label, E, steps / dt, a.nagents * steps / dt / 1e6, dt / updates,
