@@ -99,8 +99,8 @@ class BpttPasses(_SizedStruct):
                 ("snaps", C.c_void_p), ("snap_words", C.c_int64), ("alive", C.POINTER(C.c_void_p)), ("gate", C.POINTER(C.c_void_p)),
                 ("lstm_wp3_bwd", C.c_void_p), ("w_heads", C.c_void_p), ("c_weight", C.POINTER(C.c_void_p)), ("dh", C.c_void_p),
                 ("dc", C.c_void_p), ("dxh", C.POINTER(C.c_void_p)), ("dxh_step", C.c_int64), ("dbias_partials", C.POINTER(C.c_void_p)),
-                ("dcw_partials", C.POINTER(C.c_void_p)), ("enc_work", C.c_void_p)]
-
+                ("dcw_partials", C.POINTER(C.c_void_p)), ("enc_work", C.c_void_p), ("row_keep", C.c_void_p),
+                ("keep_before", C.c_void_p)]
 
     def __init__(self, *a, **kw):             # positional arguments start at T
         super().__init__(*((self.MAGIC,) + a if a else a), **kw)

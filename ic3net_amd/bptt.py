@@ -590,8 +590,10 @@ class _Cuts(object):
         return (torch.where(fr, ones, alive) if alive is not None else None,
                 torch.where(fr, zeros, gate) if gate is not None else None)
 
-    def masks_window(self, alive, gate):
-        """`masks` (fill_gate) for all T steps at once — one `where` per mask over (T, E, N); returns the two lists of T"""
+    def masks_window(self, alive, gate, fill_gate=True):
+        """`masks` for all T steps at once — one `where` per mask over (T, E, N); returns the two lists of T.  fill_gate (the
+        drivers that leave the entering state in the record): a missing gate counts as all ones first; without it a window that
+        has no gate at all keeps none, as `masks` does step by step"""
         alive, gate = list(alive), list(gate)
         if not self.on:
             return alive, gate
@@ -599,7 +601,8 @@ class _Cuts(object):
         fr = self.fresh.unsqueeze(2)
         if any(m is not None for m in alive):
             alive = list(torch.where(fr, ones, torch.stack([m if m is not None else ones for m in alive])).unbind(0))
-        gate = list(torch.where(fr, zeros, torch.stack([m if m is not None else ones for m in gate])).unbind(0))
+        if fill_gate or any(m is not None for m in gate):
+            gate = list(torch.where(fr, zeros, torch.stack([m if m is not None else ones for m in gate])).unbind(0))
         return alive, gate
 
     def entering(self, t, h, c=None):
@@ -777,30 +780,35 @@ def _backward_episode_multipass(args, net, raw, rec, d_out, acc, carry=None):
 
 
 MULTIPASS_WINDOW_DEFAULT = True       # args.multipass_window_backward where the flag is absent (main.py carries the same default)
+MULTIPASS_WINDOW_COLLECTION_DEFAULT = False     # args.multipass_window_collection likewise: collection-mode windows keep the loop
 
 
-def _multipass_ring_floats(H, P):
+def _multipass_ring_floats(H, P, collection=False):
     """Floats per row of one chunk step of _backward_window_multipass: per pass the gate record 4H, the inp rows, h and c H each and
-    the dxh ring 2H; slot 0 of the h ring and the encoder ring H each."""
-    return P * (8 * H + ops.record_xh_width(H)) + 2 * H
+    the dxh ring 2H; slot 0 of the h ring and the encoder ring H each; collection mode: slot 0 of a c ring too (the copy of the
+    entering c with the starting envs' rows zeroed)."""
+    return P * (8 * H + ops.record_xh_width(H)) + (3 if collection else 2) * H
 
 
-def _multipass_chunk_steps(dev, T, R, H, P, most=0):
+def _multipass_chunk_steps(dev, T, R, H, P, most=0, collection=False):
     """Whole steps per chunk of _backward_window_multipass — the largest count for which every launch stays inside its 32-bit limits
     (a chunk's rows x 4H floats below 4 GB: the recording forward and the gate launch's buffer offsets; rows below 2^31 - 2^16: the
     encoder's window stage) and the chunk's rings inside what _ring_fits grants; at most `most` when that is > 0; 0: not even one."""
     tc = min(T, (2 ** 32 - 1) // (R * 4 * H * 4), (2 ** 31 - 2 ** 16 - 1) // R)
     if dev.type == 'cuda':
-        tc = min(tc, (device_room(dev) // 4) // (R * _multipass_ring_floats(H, P) * 4))
+        tc = min(tc, (device_room(dev) // 4) // (R * _multipass_ring_floats(H, P, collection) * 4))
     return max(min(tc, most) if most > 0 else tc, 0)
 
 
 def _multipass_window_ok(args, net, raw, rec, d_out):
-    """The recurrent LSTM policy with comm_passes > 1 on a lock-step window: hid_size 64 / 128 / 256 (a zero-padded twin at the twin's
+    """The recurrent LSTM policy with comm_passes > 1 on a window: hid_size 64 / 128 / 256 (a zero-padded twin at the twin's
     size), at most 16 output columns, the split planes of both directions in the fused cache, the native loop and
     args.multipass_window_backward on, the library's answer for this env (the encoder backward's window form) and room for at least
-    one step's rings: _backward_window_multipass."""
-    if rec.stream is not None or not rec.recurrent or rec.n < 1 or d_out.shape[-1] > 16 or not d_out.is_cuda:
+    one step's rings: _backward_window_multipass.  A collection-mode window (rec.stream) needs args.multipass_window_collection as
+    well, which is off where the flag is absent: such a window then keeps the per-step loop."""
+    if not rec.recurrent or rec.n < 1 or d_out.shape[-1] > 16 or not d_out.is_cuda:
+        return False
+    if rec.stream is not None and not bool(getattr(args, 'multipass_window_collection', MULTIPASS_WINDOW_COLLECTION_DEFAULT)):
         return False
     if not bool(getattr(args, 'bptt_native_loop', True)) or not bool(getattr(args, 'multipass_window_backward', MULTIPASS_WINDOW_DEFAULT)):
         return False
@@ -812,11 +820,11 @@ def _multipass_window_ok(args, net, raw, rec, d_out):
         return False
     if not _enc_window(args, raw, H) or not ops.bptt_passes_backward_supported(raw, H, net.comm_passes):
         return False
-    return _multipass_chunk_steps(rec.hs.device, rec.n, rec.hs.shape[1], H, net.comm_passes) >= 1
+    return _multipass_chunk_steps(rec.hs.device, rec.n, rec.hs.shape[1], H, net.comm_passes, collection=rec.stream is not None) >= 1
 
 
 def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_chunk_steps=0, dgates_out=None):
-    """_backward_episode_multipass for a lock-step window on HIP launches alone.  (h, c) entering every step is recorded, so the inner
+    """_backward_episode_multipass for a window on HIP launches alone.  (h, c) entering every step is recorded, so the inner
     passes of all steps are independent of each other: the window is walked in chunks of whole steps, last chunk first, and per chunk
       Tc x raw.encode_at              encoder(obs) + encoder.bias + C_0.bias of every snapshot into a ring
       P x ops.policy_forward_record   pass i over the Tc x E stacked envs, slot i of the (h, c) ring -> slot i + 1 (slot 0: the record's
@@ -826,7 +834,13 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
       ops.lstm_weight_grad            [W_ih | W_hh]'s gradient over the chunk's P x Tc x R rows, added
     dh / dc carry from chunk to chunk; the heads' gradient is one pass over the window beside the chain.  Behind the chunks: one
     encoder finish, the bias partials of all passes, each pass's dC_i partials, and C_i.bias's gradient read off pass i's bias
-    partials — the column sum of pass i's d inp is (the column sum of its dgates) . W_ih.  max_chunk_steps > 0 bounds the chunk (tests); dgates_out (P, T, R, 4H) receives every chunk's dgates (tests)."""
+    partials — the column sum of pass i's d inp is (the column sum of its dgates) . W_ih.  max_chunk_steps > 0 bounds the chunk (tests); dgates_out (P, T, R, 4H) receives every chunk's dgates (tests).
+    Collection mode (rec.stream; `carry` = (dL/dh, dL/dc) from the later window, the pair leaving the first slot is returned): the
+    cuts of _Cuts ride inside the same launches.  keep[t] scales what leaves slot t — the chunk's rows go to the call as row_keep,
+    the row of the slot in front of the chunk as keep_before, and dh is scaled by keep[T - 1] where it enters the window.  An env
+    that starts an episode at slot t has nobody dead and everyone gated off in every pass of that step (masks_window) and zeros
+    entering pass 0: slot 0 of the h ring and of a c ring hold the recorded rows times `live`, once per chunk over all its steps
+    (the record itself is left alone: the heads' pass beside the chain reads it)."""
     fc = net._fused_cache()
     P = net.comm_passes
     T, R, H = rec.n, rec.hs.shape[1], rec.hs.shape[2]
@@ -836,20 +850,22 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
     mode_avg = getattr(args, 'comm_mode', 'avg') == 'avg'
     mask_zero = bool(args.comm_mask_zero)
     heads = args.naction_heads
-    # (lock-step windows only — _multipass_window_ok: nothing arrives from a later window, dh / dc start at zero)
-    assert rec.stream is None and carry is None, "a carried gradient would be dropped: collection-mode windows keep the per-step loop"
-    Tc = _multipass_chunk_steps(dev, T, R, H, P, max_chunk_steps)
+    cuts = _Cuts(args, rec, T, E, N, dev)                         # (lock-step: the detach points; collection: row factors, masks, carry)
+    assert cuts.on or carry is None, "a carried gradient would be dropped: only collection-mode windows (rec.stream) take a carry"
+    Tc = _multipass_chunk_steps(dev, T, R, H, P, max_chunk_steps, collection=cuts.on)
     assert Tc >= 1, "no room for one step's rings (_multipass_window_ok answers first)"
     xw = ops.record_xh_width(H)
     empty = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
     zeros = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
     enc, gates, inp = empty(Tc, R, H), empty(P, Tc, R, 4 * H), empty(P, Tc, R, xw)
     hring, cring, dxh = empty(P + 1, Tc, R, H), empty(P, Tc, R, H), empty(P, Tc, R, 2 * H)     # cring[i]: c LEAVING pass i
+    c_in = empty(Tc, R, H) if cuts.on else None                   # collection: c ENTERING pass 0, the starting envs' rows zeroed
     dh_rec, dc_rec = zeros(R, H), zeros(R, H)
+    cuts.carry_in(carry, dh_rec, dc_rec, at_border=True)
+    alive_w, gate_w = cuts.masks_window(rec.alive[:T], rec.gate[:T], fill_gate=False)
     bias_parts = zeros(P, (R + 63) // 64, 4 * H)
     dcw_parts = None if mask_zero else zeros(P, ops.comm_backward_partials(E, N), H, H)
     c_weights = None if mask_zero else [m.weight.detach() for m in net.C_modules]
-    cuts = _Cuts(args, rec, T, E, N, dev)                         # (lock-step: the detach points; no row factors, no carry)
     dhead = _dhead_rows(d_out, T)
     work = acc.setdefault('_work', {})
 
@@ -865,10 +881,14 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
             Tn = t1 - t0
             for k in range(Tn):
                 raw.encode_at(rec.snaps[t0 + k], fc['wt'], fc['enc_bias'], out=enc[k], loc_table=fc['loc_table'])
-            alive, gate = rec.alive[t0:t1], rec.gate[t0:t1]
+            alive, gate = alive_w[t0:t1], gate_w[t0:t1]
             alive_st, gate_st = stacked(alive), stacked(gate)
-            hring[0, :Tn].copy_(rec.hs[t0:t1])
-            cs = [rec.cs[t0:t1]] + [cring[i, :Tn] for i in range(P - 1)]
+            if cuts.on:
+                torch.mul(rec.hs[t0:t1], cuts.live_rows[t0:t1], out=hring[0, :Tn])
+                torch.mul(rec.cs[t0:t1], cuts.live_rows[t0:t1], out=c_in[:Tn])
+            else:
+                hring[0, :Tn].copy_(rec.hs[t0:t1])
+            cs = [c_in[:Tn] if cuts.on else rec.cs[t0:t1]] + [cring[i, :Tn] for i in range(P - 1)]
             for i in range(P):
                 ops.policy_forward_record(fc, H, heads, mode_avg, mask_zero, enc[:Tn].view(Tn * R, H), Tn * E, N,
                                           hring[i, :Tn].view(Tn * R, H), cs[i].reshape(Tn * R, H), hring[i + 1, :Tn].view(Tn * R, H),
@@ -878,7 +898,9 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
                                      dhead[t0:t1], rec.snaps[t0:t1], alive, gate, fc['ps_l_wp3_bwd'], fc['w_heads'], c_weights, dh_rec,
                                      dc_rec, [dxh[i, :Tn] for i in range(P)], [bias_parts[i] for i in range(P)],
                                      None if mask_zero else [dcw_parts[i] for i in range(P)], mode_avg=mode_avg, comm_zero=mask_zero,
-                                     detach_gap=cuts.gap, t_first=t0, enc_first=first)
+                                     detach_gap=cuts.gap, t_first=t0, enc_first=first,
+                                     row_keep=cuts.keep_flat[t0:t1] if cuts.on else None,
+                                     keep_before=cuts.keep_flat[t0 - 1] if cuts.on and t0 > 0 else None)
             first = False
             if dgates_out is not None:
                 dgates_out[:, t0:t1].copy_(gates[:, :Tn])

@@ -811,6 +811,8 @@ static int bptt_cell_backward(const char* fn, const BpttCell& q, int Ec, int N, 
 // i = P - 1 .. 0 — dhead on the last pass only, a detach point cuts what arrives at the last pass only, the communication backward
 // of pass i leaves in dh what pass i - 1 (step t - 1 for i = 0) receives.  The encoder is linear in its input gradient, which is the
 // sum of the passes' d inp: its window stage runs once per pass over that pass's ring and accumulates.
+// Collection mode (row_keep / keep_before): dc flows uncut between the passes of one step and dh between them unscaled — the cuts sit
+// on the slot's border alone.  The zero state entering a starting env is the caller's (zeroed copies as pass 0's hs / cs): no row_live.
 static int bptt_passes_backward(ic3_env* env, const ic3_bptt_passes* b, ic3_stream stream)
 {
     using namespace ic3;
@@ -838,9 +840,16 @@ static int bptt_passes_backward(ic3_env* env, const ic3_bptt_passes* b, ic3_stre
     if (R * 4 * H * 4 >= (1ll << 32))
         return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): rows * 4 * hid_size floats must stay below 4 GB (the gate launch's 32-bit buffer "
                          "offsets)");
+    if (b->detach_gap > 0 && (b->row_keep || b->keep_before))
+        return fail(-22, "ic3_bptt_backward (ic3_bptt_passes): detach_gap > 0 with row_keep / keep_before (a detached step has no dc for "
+                         "row_keep to scale: lock-step windows carry detach_gap, collection-mode windows the row factors)");
     hipStream_t s = (hipStream_t)stream;
     for (int t = T - 1; t >= 0; --t) {
         const bool detached = b->detach_gap > 0 && (b->t_first + t + 1) % b->detach_gap == 0;
+        // collection mode: what LEAVES slot t is cut by keep[t] — dc where it arrives, at the slot's last pass; dh where it is produced,
+        // by pass 0 of slot t + 1 (so this slot's pass 0 scales by the keep row of the slot in front: keep_before at the call's first)
+        const float* keep_here = b->row_keep ? b->row_keep + (size_t)t * R : nullptr;
+        const float* keep_front = t > 0 ? (b->row_keep ? b->row_keep + (size_t)(t - 1) * R : nullptr) : b->keep_before;
         for (int i = P - 1; i >= 0; --i) {
             const bool last = i == P - 1;
             BpttCell q{};
@@ -860,6 +869,8 @@ static int bptt_passes_backward(ic3_env* env, const ic3_bptt_passes* b, ic3_stre
             q.gate = (b->gate && b->gate[t]) ? b->gate[t] : nullptr;
             q.c_weight = b->comm_zero ? nullptr : b->c_weight[i];
             q.dcw = b->comm_zero ? nullptr : b->dcw_partials[i];
+            q.row_keep = last ? keep_here : nullptr;
+            q.out_scale = i == 0 ? keep_front : nullptr;
             if (const int rc = bptt_cell_backward("ic3_bptt_backward (ic3_bptt_passes)", q, E, N, H, b->mode_avg, b->comm_zero, s); rc < 0) return rc;
         }
     }

@@ -59,7 +59,9 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  ('commnet_window_backward', int, 1),
                  # 1: the update of a recurrent policy with comm_passes > 1 runs window-wide HIP launches
                  # (bptt._backward_window_multipass); 0: the per-step loop (bptt._backward_episode_multipass)
-                 ('multipass_window_backward', int, 1)]
+                 ('multipass_window_backward', int, 1),
+                 # 1: ... in collection mode (--auto_reset) too; 0 (default): collection-mode windows of such a policy keep the loop
+                 ('multipass_window_collection', int, 0)]
 
 
 def build_parser(argv):

@@ -365,14 +365,18 @@ def bptt_passes_backward_supported(env, H, passes):
 
 
 def bptt_passes_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lstm_wp3_bwd, w_heads, c_weights, dh, dc, dxh,
-                         dbias_partials, dcw_partials, mode_avg=True, comm_zero=False, detach_gap=0, t_first=0, enc_first=True):
+                         dbias_partials, dcw_partials, mode_avg=True, comm_zero=False, detach_gap=0, t_first=0, enc_first=True,
+                         row_keep=None, keep_before=None):
     """ic3_bptt_backward on an ic3_bptt_passes descriptor: the backward through T recorded steps of a comm_passes = P > 1 policy (a window, or a chunk of whole
     steps of one starting at its step t_first) as one host call.  Per pass i, lists of P tensors: gates[i] (T, R, 4H) — the record
     ops.policy_forward_record left, dgates on return —, hs[i] / cs[i] (T, R, H) the state entering the pass, dxh[i] (T, R, 2H) the
     ring of input gradients (written), dbias_partials[i] (ceil(R / 64), 4H) and dcw_partials[i] (comm_backward_partials(E, N), H, H)
     added to, c_weights[i] (H, H) (dcw_partials / c_weights: None with comm_zero).  alive / gate: lists of T (E, N) int32 tensors or
-    None entries, or None.  The encoder's window stage runs behind the loop (finish: env.encode_backward_window_finish)."""
+    None entries, or None.  The encoder's window stage runs behind the loop (finish: env.encode_backward_window_finish).
+    Collection mode: row_keep (T, R) = keep of the call's slots, keep_before (R,) = keep of the slot in front of the call's first one
+    (None at a window's first slot); hs[0] / cs[0] are then the caller's copies with the starting envs' rows zeroed."""
     _need_cuda(dh, "bptt_passes_backward")
+    assert _f32(row_keep, T * E * N, none_ok=True) and _f32(keep_before, E * N, none_ok=True)
     R = E * N
     P = len(gates)
     assert P >= 2 and len(hs) == len(cs) == len(dxh) == len(dbias_partials) == P
@@ -396,7 +400,8 @@ def bptt_passes_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, ga
     b = _lib.BpttPasses(T, E, N, H, OT, P, int(bool(mode_avg)), int(bool(comm_zero)), int(detach_gap), int(bool(enc_first)), int(t_first))
     for name, arr in arrays.items():
         setattr(b, name, C.cast(arr, C.POINTER(C.c_void_p)) if arr is not None else None)
-    _set_ptrs(b, dict(dhead=dhead, snaps=snaps, lstm_wp3_bwd=lstm_wp3_bwd, w_heads=w_heads, dh=dh, dc=dc))
+    _set_ptrs(b, dict(dhead=dhead, snaps=snaps, lstm_wp3_bwd=lstm_wp3_bwd, w_heads=w_heads, dh=dh, dc=dc),
+              row_keep=row_keep, keep_before=keep_before)
     b.snap_words = snaps.stride(0)
     b.dxh_step = dxh[0].stride(0)
     assert all(d.stride(0) == b.dxh_step for d in dxh)

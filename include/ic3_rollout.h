@@ -512,11 +512,23 @@ int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream stream);
  *   slots [R][2H], dxh_step floats apart (>= R * 2H; written);  dbias_partials[i] [ceil(R / 64)][4H],  dcw_partials[i]
  *   [ic3_comm_backward_partials(E, N)][H][H] (unused with comm_zero, as c_weight);  dhead [T][R][OT], snaps, alive / gate (HOST arrays
  *   of T device pointers or NULL), lstm_wp3_bwd, w_heads, dh / dc, enc_work (ic3_env_encode_backward_window_work floats): as ic3_bptt.
+ * Collection mode (a window of consecutive slots of E streams of episodes): row_keep [T][R] or NULL, keep[t] = 1 where the state
+ * leaving slot t reaches slot t + 1 with its gradient.  What LEAVES slot t is multiplied by keep[t], and only on the slot's border:
+ *   dc — the gate launch of cell (t, P - 1) takes row_keep = keep[t]; every other pass NULL (dc flows uncut between a step's passes);
+ *   dh — the communication backward of cell (t + 1, 0) takes out_scale = keep[t]; passes i > 0 NULL.
+ * So this call's step 0, pass 0, scales by the keep row of the slot IN FRONT of the call: keep_before [R], a pointer of its own (not
+ * row -1 of row_keep), NULL at a window's first slot — dh then leaves unscaled and the earlier window's caller cuts it at its border,
+ * as the caller scales dh by keep of the window's last slot on the way IN (nothing precedes that slot's last pass).  row_keep NULL
+ * with keep_before set scales the call's first cell alone.  The zero state ENTERING an env that starts an episode at slot t is the
+ * caller's business: the call takes no row_live — hand pass 0 copies of (h, c) with those rows zeroed as hs[0] / cs[0] (the same
+ * copies go to ic3_lstm_weight_grad_wide) and masks with those envs gated off; the recorded states stay as they are.  Both NULL:
+ * the lock-step call, bit for bit.
  * The call can run where ic3_bptt_backward_supported(env, H) answers 1 and ic3_env_encode_backward_window_work(env, H) > 0 — ask before
  * anything is overwritten.
  * -ENOSYS: what ic3_bptt_backward_supported refuses, or a configuration without ic3_env_encode_backward_window.  -EINVAL BEFORE the
  * first launch (the records are untouched): a struct_size mismatch, passes < 2, a null argument, dxh_step below R * 2H, rows * 4 *
- * hid_size floats at 4 GB or more.  One stream. */
+ * hid_size floats at 4 GB or more, detach_gap > 0 together with row_keep or keep_before (as ic3_bptt_backward: a detached step has no
+ * dc for row_keep to scale).  One stream. */
 #define IC3_BPTT_PASSES_MAGIC 0x53534150u /* "PASS" */
 typedef struct ic3_bptt_passes {
     uint32_t struct_size;   /* sizeof(ic3_bptt_passes) of the caller's header (checked with the tag: -EINVAL on mismatch) */
@@ -542,6 +554,8 @@ typedef struct ic3_bptt_passes {
     float* const* dbias_partials;
     float* const* dcw_partials;
     float* enc_work;
+    const float* row_keep;    /* [T][R] or NULL: keep[t] of this call's T slots (collection mode, see above) */
+    const float* keep_before; /* [R] or NULL: keep of the slot in front of this call's first one (a chunk with t_first > 0) */
 } ic3_bptt_passes;
 
 /* The backward through a window of T recorded steps of the IC / IRIC baselines' tanh recurrence (models.py:68-92, rnn_type 'MLP':

@@ -3,7 +3,9 @@ python tools/bench_train.py [nenvs] [updates] [native|autograd] [workload] [dens
 one-launch rollout + the explicit backward through time of ic3net_amd.bptt; autograd: the rollout keeps the autograd
 graph, rounds 1-2; dense_obs 0: the training rollout does not assemble observation rows nothing reads).
 COMM_PASSES=<P> (with SHARE_WEIGHTS=1: one C for every pass) overrides the workload's communication passes; MULTIPASS_WINDOW=0 sends
-the update of such a policy through the per-step loop instead of bptt._backward_window_multipass (the line then says which ran)."""
+the update of such a policy through the per-step loop instead of bptt._backward_window_multipass (the line then says which ran);
+MULTIPASS_COLLECTION=1 sends its collection-mode windows (argument 7 = 1) through the window path too (args.multipass_window_collection,
+off by default)."""
 import os
 import sys
 import time
@@ -29,6 +31,8 @@ def main():
     tr, a = bench.build_trainer(wl, E, 0, 0, 0, **over)
     if over and 'MULTIPASS_WINDOW' in os.environ:            # A/B: the window backward of comm_passes > 1 policies against the loop
         a.multipass_window_backward = os.environ['MULTIPASS_WINDOW'] == '1'
+    if over and 'MULTIPASS_COLLECTION' in os.environ:
+        a.multipass_window_collection = os.environ['MULTIPASS_COLLECTION'] == '1'
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
