@@ -19,22 +19,63 @@ from . import ops
 DEFAULT_GATE_SPLIT = True     # (tests run the policy parity set in both modes by flipping this)
 
 
-class _PaddedArgs(object):
-    """The args of a policy, read live, with another hid_size (CommNetMLP._twin)."""
+class _ArgsView(object):
+    """The args of a policy, read (and written) live, with a few names overridden: another hid_size for the zero-padded
+    twin (CommNetMLP._padded_twin), the communication block switched off for a baseline's stand-in (models.py)."""
 
-    def __init__(self, base, hid_size):
+    def __init__(self, base, **override):
         object.__setattr__(self, '_base', base)
-        object.__setattr__(self, '_hid_size', int(hid_size))
+        object.__setattr__(self, '_override', override)
 
-    def __getattr__(self, k):                                    # (only reached for names not set on the proxy itself)
-        return getattr(object.__getattribute__(self, '_base'), k)
+    def __getattr__(self, k):                                    # (only reached for names not set on the view itself)
+        override = object.__getattribute__(self, '_override')
+        return override[k] if k in override else getattr(object.__getattribute__(self, '_base'), k)
 
     def __setattr__(self, k, v):
         setattr(object.__getattribute__(self, '_base'), k, v)
 
-    @property
-    def hid_size(self):
-        return object.__getattribute__(self, '_hid_size')
+
+def _param_key(params, *switches):
+    """What a tensor derived from `params` (and the switches read with them) was built from: a parameter written in place
+    moves its version, a replaced one its address."""
+    return tuple((q._version, q.data_ptr()) for q in params) + switches
+
+
+class _DerivedPolicy(object):
+    """Holder of a CommNetMLP derived from an owner policy — the zero-padded twin of a CommNetMLP, the kernel stand-in of a
+    baseline (models.py): frozen, zeroed, on the owner's device and dtype, NOT a submodule of the owner (derived data, like
+    the packed weights of _fused_cache).  `fill(owner, net)` copies the owner's parameters into it whenever one of them has
+    a new version — in place: captured graphs hold the addresses."""
+    MIRRORED = ('mega_steps', 'mega_forwards', 'commnet_steps', 'commnet_forwards', 'cache_generation')
+
+    def __init__(self, owner, args, num_inputs, fill):
+        self.owner, self.args, self.num_inputs, self.fill, self.net, self.key = owner, args, num_inputs, fill, None, None
+
+    def get(self):
+        """The derived policy, its parameters up to date, with the owner's hooks (sparse encoder, table, action sink)."""
+        o, net = self.owner, self.net
+        like = next(o.parameters())
+        if net is None or net.encoder.weight.device != like.device or net.encoder.weight.dtype != like.dtype:
+            net = self.net = CommNetMLP(self.args, self.num_inputs).to(device=like.device, dtype=like.dtype)
+            for q in net.parameters():
+                q.requires_grad_(False)
+                q.zero_()
+            self.key = None
+        key = _param_key(o.parameters())
+        if key != self.key:
+            with torch.no_grad():
+                self.fill(o, net)
+            self.key = key
+        for k in ('obs_encoder', 'obs_table', 'obs_env', 'sample_into'):
+            setattr(net, k, getattr(o, k, None))
+        return net
+
+    def done(self):
+        """mirror what callers read off the owner after a call"""
+        for k in self.MIRRORED:
+            if k in self.net.__dict__:
+                self.owner.__dict__[k] = self.net.__dict__[k]
+        self.owner.sampled = self.net.sampled
 
 
 class CommNetMLP(nn.Module):
@@ -96,6 +137,25 @@ class CommNetMLP(nn.Module):
             m = m.unsqueeze(0).expand(batch, -1)
         return m.reshape(batch, self.nagents).contiguous()
 
+    def _call_inputs(self, info, batch, dev):
+        """What every path reads off `info` and the args per call: (alive mask, comm_action — only when args.hard_attn —,
+        mode_avg, comm_mask_zero)."""
+        a = self.args
+        return (self._mask(info, 'alive_mask', batch, dev),
+                self._mask(info, 'comm_action', batch, dev) if a.hard_attn else None,
+                hasattr(a, 'comm_mode') and a.comm_mode == 'avg', bool(a.comm_mask_zero))
+
+    def _step_out(self, out, R, dev):
+        """(integer head sizes, the (R, OT) [log-probs | value] rows of a step launch): a fresh tensor per call (a Transition
+        keeps its action_out), or the caller's buffer (hipGraph mode: nothing is allocated inside a captured step)."""
+        heads = [int(o) for o in self.args.naction_heads]
+        OT = sum(heads) + 1
+        if out is None:
+            out = torch.empty((R, OT), dtype=torch.float32, device=dev)
+        else:
+            assert out.is_contiguous() and tuple(out.shape) == (R, OT) and out.dtype == torch.float32
+        return heads, out
+
     def forward(self, x, info={}):
         n, H = self.nagents, self.hid_size
         tw = self._twin_for(x)
@@ -112,12 +172,10 @@ class CommNetMLP(nn.Module):
             x = self.tanh(self._encode(x))
             hidden_state, cell_state = x, None
         batch = x.size(0)
-        alive = self._mask(info, 'alive_mask', batch, x.device)
-        comm_action = self._mask(info, 'comm_action', batch, x.device) if self.args.hard_attn else None
-        mode_avg = hasattr(self.args, 'comm_mode') and self.args.comm_mode == 'avg'
+        alive, comm_action, mode_avg, mz = self._call_inputs(info, batch, x.device)
         for i in range(self.comm_passes):
             h = hidden_state.view(batch, n, H)
-            comm_sum = ops.comm_masked_mean(h, alive, comm_action, mode_avg, not self.args.comm_mask_zero)
+            comm_sum = ops.comm_masked_mean(h, alive, comm_action, mode_avg, not mz)
             c = self.C_modules[i](comm_sum)                       # comm.py:206 (bias even with zero comm, Q24)
             if self.args.recurrent:
                 inp = (x + c).view(batch * n, H)                  # comm.py:209-213
@@ -152,50 +210,37 @@ class CommNetMLP(nn.Module):
             return None
         if not self.encoder.weight.is_cuda or self.encoder.weight.dtype != torch.float32:
             return None
-        tw = self._padded_twin(Hp)
-        tw.obs_encoder, tw.obs_table, tw.obs_env, tw.sample_into = self.obs_encoder, self.obs_table, self.obs_env, self.sample_into
-        return tw
+        return self._padded_twin(Hp)
+
+    def _twin_region(self, name, t, Hp):
+        """The region of a twin's tensor `t` (parameter `name` at hidden size Hp, or its gradient) that holds this policy's
+        own entries, as a view; None for what forward never reads (hidd_encoder, quirk Q18)."""
+        H = self.hid_size
+        if name.startswith('hidd_encoder.'):
+            return None
+        if self.args.recurrent and name.startswith('f_module.'):      # LSTMCell: four gate blocks of H rows
+            return t.view(4, Hp, Hp)[:, :H, :H] if t.dim() == 2 else t.view(4, Hp)[:, :H]
+        if name.startswith('heads.') or name.startswith('value_head.'):
+            return t[:, :H] if t.dim() == 2 else t
+        if name.startswith('encoder.'):
+            return t[:H]
+        return t[:H, :H] if t.dim() == 2 else t[:H]                   # C_module(s), the non-recurrent f_module(s): H x H
 
     def _padded_twin(self, Hp):
         """The twin at hidden size Hp, its parameters up to date with this policy's (any device)."""
-        a = self.args
         box = self.__dict__.get('_twin_box')
-        dev, dt = self.encoder.weight.device, self.encoder.weight.dtype
-        if box is None or box[0].encoder.weight.device != dev or box[0].encoder.weight.dtype != dt or box[0].hid_size != Hp:
-            tw = CommNetMLP(_PaddedArgs(a, Hp), self.encoder.in_features).to(device=dev, dtype=dt)
-            for q in tw.parameters():
-                q.requires_grad_(False)
-                q.zero_()
-            box = self.__dict__['_twin_box'] = [tw, None]        # (a list: not registered as a submodule)
-        tw = box[0]
-        key = tuple((q._version, q.data_ptr()) for q in self.parameters())
-        if box[1] != key:
-            H = self.hid_size
-            with torch.no_grad():
-                mine, theirs = dict(self.named_parameters()), dict(tw.named_parameters())
-                assert mine.keys() == theirs.keys()
-                for name, src in mine.items():
-                    dst = theirs[name]
-                    if name.startswith('hidd_encoder.'):
-                        continue                                  # unused by forward (quirk Q18)
-                    if a.recurrent and name.startswith('f_module.'):       # LSTMCell: four gate blocks of H rows
-                        if src.dim() == 2:
-                            dst.view(4, Hp, Hp)[:, :H, :H].copy_(src.view(4, H, H))
-                        else:
-                            dst.view(4, Hp)[:, :H].copy_(src.view(4, H))
-                    elif name.startswith('heads.') or name.startswith('value_head.'):
-                        if src.dim() == 2:
-                            dst[:, :H].copy_(src)
-                        else:
-                            dst.copy_(src)
-                    elif name.startswith('encoder.'):
-                        dst[:H].copy_(src)
-                    elif src.dim() == 2:                          # C_module(s), the non-recurrent f_module(s): H x H
-                        dst[:H, :H].copy_(src)
-                    else:
-                        dst[:H].copy_(src)
-            box[1] = key
-        return tw
+        if box is None or box.args.hid_size != Hp:
+            box = self.__dict__['_twin_box'] = _DerivedPolicy(self, _ArgsView(self.args, hid_size=int(Hp)),
+                                                              self.encoder.in_features, CommNetMLP._fill_twin)
+        return box.get()
+
+    def _fill_twin(self, tw):
+        theirs = dict(tw.named_parameters())
+        assert dict(self.named_parameters()).keys() == theirs.keys()
+        for name, src in self.named_parameters():
+            region = self._twin_region(name, theirs[name], tw.hid_size)
+            if region is not None:
+                region.copy_(src.view(region.shape))
 
     def _twin_for(self, x):
         if torch.is_grad_enabled():
@@ -205,14 +250,20 @@ class CommNetMLP(nn.Module):
             return None
         return self._twin()
 
-    def _twin_done(self, tw):
-        """mirror what callers read off the policy after a call"""
-        for k in ('mega_steps', 'mega_forwards', 'commnet_steps', 'commnet_forwards', 'cache_generation'):
-            if k in tw.__dict__:
-                self.__dict__[k] = tw.__dict__[k]
-        self.sampled = tw.sampled
-        if getattr(tw, '_fc', None) is not None:
-            self.__dict__['_fc'] = tw._fc
+    def _state_buffers(self, R, dev):
+        """The persistent (h, c) pair of the one-launch paths, self._mb['h'] / ['c']: (R, hid_size) fp32, zeroed when (re)allocated
+        (once per shape, never inside a captured step)."""
+        mb = getattr(self, '_mb', None)
+        if mb is None or mb['h'].shape[0] != R or mb['h'].device != dev:
+            mb = self._mb = dict(h=torch.zeros((R, self.hid_size), dtype=torch.float32, device=dev),
+                                 c=torch.zeros((R, self.hid_size), dtype=torch.float32, device=dev))
+        return mb
+
+    @staticmethod
+    def _take_state(buf, state):
+        """fresh hidden state from the caller (t = 0) -> the path's own buffer, unless it already is that buffer"""
+        if state.data_ptr() != buf.data_ptr():
+            buf.copy_(state.detach().reshape(buf.shape))
 
     def _twin_hidden(self, tw, hidden_state, cell_state, R):
         """The caller's hidden state as the twin takes it: (h, c, wide).  A state that already has the twin's width (the
@@ -221,11 +272,7 @@ class CommNetMLP(nn.Module):
         H, Hp = self.hid_size, tw.hid_size
         if hidden_state.shape[-1] == Hp:
             return hidden_state, cell_state, True
-        mb = getattr(tw, '_mb', None)
-        dev = hidden_state.device
-        if mb is None or mb['h'].shape[0] != R or mb['h'].device != dev:
-            mb = tw._mb = dict(h=torch.zeros((R, Hp), dtype=torch.float32, device=dev),
-                               c=torch.zeros((R, Hp), dtype=torch.float32, device=dev))
+        mb = tw._state_buffers(R, hidden_state.device)
         for src, k in ((hidden_state, 'h'), (cell_state, 'c')):
             buf = mb[k]
             if src.data_ptr() == buf.data_ptr() and tuple(src.shape) == (R, H) and src.stride() == (Hp, 1):
@@ -246,24 +293,14 @@ class CommNetMLP(nn.Module):
         """After a native update on the twin: p.grad of every parameter <- its region of the twin's gradient (the padded
         rows / columns of the twin's gradients are exactly zero)."""
         box = self.__dict__.get('_twin_box')
-        if not box or box[0] is None:
+        if box is None or box.net is None:
             raise RuntimeError("unpad_grads(): this policy has no zero-padded twin (nothing ran on one: hid_size %d is a size "
                                "the kernels take as it is, or args.pad_hidden is off)" % self.hid_size)
-        tw = box[0]
-        H, Hp = self.hid_size, tw.hid_size
-        theirs = dict(tw.named_parameters())
+        theirs = dict(box.net.named_parameters())
         for name, p in self.named_parameters():
             g = theirs[name].grad
-            if g is None or name.startswith('hidd_encoder.'):
-                p.grad = None
-            elif self.args.recurrent and name.startswith('f_module.'):
-                p.grad = (g.view(4, Hp, Hp)[:, :H, :H] if g.dim() == 2 else g.view(4, Hp)[:, :H]).reshape(p.shape).clone()
-            elif name.startswith('heads.') or name.startswith('value_head.'):
-                p.grad = (g[:, :H] if g.dim() == 2 else g).clone()
-            elif name.startswith('encoder.'):
-                p.grad = g[:H].clone()
-            else:
-                p.grad = (g[:H, :H] if g.dim() == 2 else g[:H]).clone()
+            region = None if g is None else self._twin_region(name, g, box.net.hid_size)
+            p.grad = None if region is None else region.reshape(p.shape).clone()
             theirs[name].grad = None
 
     def _forward_twin(self, tw, x, info):
@@ -271,10 +308,10 @@ class CommNetMLP(nn.Module):
             x0, (hidden_state, cell_state) = x
             hp, cp, wide = self._twin_hidden(tw, hidden_state, cell_state, x0.size(0) * self.nagents)
             action, value, hc = tw([x0, (hp, cp)], info)
-            self._twin_done(tw)
+            self._twin_box.done()
             return action, value, self._twin_state_out(hc, wide)
         out = tw(x, info)
-        self._twin_done(tw)
+        self._twin_box.done()
         return out
 
     # ------------------------------------------------------------------------------------------
@@ -289,67 +326,134 @@ class CommNetMLP(nn.Module):
     # The returned (h, c) are views of internal buffers, valid until the next forward: one rollout at a time per
     # policy instance in this mode (set args.fused_policy = False to get fresh tensors from the generic path).
     # ------------------------------------------------------------------------------------------
+    # The launch preconditions, in three layers — what the args and parameters decide (_args_ok), what the env decides
+    # (_env_ok), what the tensors of one step decide (_obs_ok) — and the predicates composed of them: _fused_ok / _commnet_ok
+    # (forward), mega_ok / commnet_step_ok (one step), mega_supported (before an episode starts).
+    def _args_ok(self):
+        """What every fused path asks of args and parameters: args.fused_policy, at most 4 heads, [log-probs | value] rows of at
+        most 16 columns, fp32."""
+        a = self.args
+        return bool(getattr(a, 'fused_policy', True)) and len(self.heads) <= 4 \
+            and sum(int(o) for o in a.naction_heads) + 1 <= 16 and self.encoder.weight.dtype == torch.float32
+
+    def _env_ok(self, env):
+        """What every one-launch step asks of the env: a native handle, the sparse encoder bound to it, this policy's agents."""
+        return hasattr(env, '_h') and getattr(self.obs_encoder, '__self__', None) is env and self.nagents == env.nagents_env
+
+    def _obs_ok(self, env, obs):
+        """... and of a step's observation: the env's own buffer, every env of it."""
+        return self._x_is_env_obs(obs) and obs.shape[0] == env.nenvs
+
+    def _step_supported(self, env):
+        """ops.policy_step_supported(env, hid_size), asked once per env"""
+        ok = getattr(self, '_mega_sup', None)
+        if ok is None or ok[0] is not env:
+            ok = self._mega_sup = (env, ops.policy_step_supported(env, self.hid_size))
+        return ok[1]
+
     def _fused_ok(self, x):
         a = self.args
-        if torch.is_grad_enabled() or not getattr(a, 'fused_policy', True):
-            return False
-        if not (a.recurrent and self.hid_size % 4 == 0 and len(self.heads) <= 4):
+        if torch.is_grad_enabled() or not self._args_ok() or not (a.recurrent and self.hid_size % 4 == 0):
             return False
         if self.comm_passes != 1 and not self._multi_pass_ok():   # comm_passes > 1: the one-launch kernels, once per pass
             return False
-        if sum(int(o) for o in a.naction_heads) + 1 > 16:
-            return False
-        return isinstance(x, (list, tuple)) and x[0].is_cuda and self.encoder.weight.dtype == torch.float32
+        return isinstance(x, (list, tuple)) and x[0].is_cuda
 
     def _commnet_ok(self, x):
         """The non-recurrent module on the fused path: every communication pass in one ic3_commnet_forward launch."""
         a = self.args
-        if torch.is_grad_enabled() or not getattr(a, 'fused_policy', True) or not getattr(a, 'mega_policy', True):
+        if torch.is_grad_enabled() or not self._args_ok() or not getattr(a, 'mega_policy', True):
             return False
-        if a.recurrent or getattr(self, 'continuous', False) or len(self.heads) > 4:
+        if a.recurrent or getattr(self, 'continuous', False) or not torch.is_tensor(x) or not x.is_cuda:
             return False
-        if sum(int(o) for o in a.naction_heads) + 1 > 16 or not torch.is_tensor(x) or not x.is_cuda:
-            return False
-        return self.encoder.weight.dtype == torch.float32 and ops.commnet_forward_supported(self.hid_size, self.nagents)
+        return ops.commnet_forward_supported(self.hid_size, self.nagents)
+
+    def _derived(self, name, params, switches, build):
+        """The one mechanism of the derived-weights caches (self._fc, self._cn): the dict `name`, built by build() from `params`
+        and `switches`.  When one of those has changed, build() runs again; a result with the old dict's keys, shapes and devices
+        is copied INTO the old tensors — captured step graphs hold their addresses (a re-allocation would leave the graphs reading
+        freed / stale memory) —, any other replaces the dict and moves cache_generation on: the graphs are stale."""
+        key = _param_key(params, *switches)
+        if getattr(self, name + '_key', None) != key:
+            with torch.no_grad():
+                new, old = build(), getattr(self, name, None)
+                # the cache owns its tensors: an alias of a parameter (.contiguous() of one that already is) would be written
+                # by the copies below, which moves that parameter's version on — and with it the key, at every call
+                theirs = set(q.untyped_storage().data_ptr() for q in params)
+                new = {k: v.clone() if v is not None and v.untyped_storage().data_ptr() in theirs else v for k, v in new.items()}
+                same = old is not None and old.keys() == new.keys() and all(
+                    (old[k] is None) == (new[k] is None) and (new[k] is None or (old[k].shape == new[k].shape
+                                                                                 and old[k].device == new[k].device))
+                    for k in new)
+                if same:
+                    for k, v in new.items():
+                        if v is not None:
+                            old[k].copy_(v)
+                else:
+                    setattr(self, name, new)
+                    self.cache_generation = getattr(self, 'cache_generation', 0) + 1
+            setattr(self, name + '_key', key)
+        return getattr(self, name)
+
+    def refresh_derived(self):
+        """Bring every derived cache that has been built up to date with the parameters, in place — Trainer.begin_episode in
+        front of graph replays, which never run this module's Python.  A policy that runs as its twin: the twin's copies of
+        the parameters, then the twin's caches."""
+        tw = self._twin() if '_twin_box' in self.__dict__ else None
+        if tw is not None:
+            tw.refresh_derived()
+            return self._twin_box.done()
+        with torch.no_grad():
+            if '_fc' in self.__dict__:
+                self._fused_cache()
+            if '_cn' in self.__dict__:
+                self._commnet_cache()
+
+    def _heads_cat(self):
+        return dict(w_heads=torch.cat([hd.weight for hd in self.heads] + [self.value_head.weight], 0).contiguous(),
+                    b_heads=torch.cat([hd.bias for hd in self.heads] + [self.value_head.bias], 0).contiguous())
 
     def _commnet_cache(self):
-        ps = [self.encoder.weight, self.encoder.bias, self.value_head.weight, self.value_head.bias] + \
-            [q for m in list(self.C_modules) + list(self.f_modules) for q in (m.weight, m.bias)] + \
-            [q for hd in self.heads for q in (hd.weight, hd.bias)]
-        key = tuple((q._version, q.data_ptr()) for q in ps) + (bool(getattr(self.args, 'gate_split', True)),)
-        if getattr(self, '_cn_key', None) != key:
-            with torch.no_grad():
-                wt = self.encoder.weight.t().contiguous()
-                wp, bias = ops.commnet_pack([m.weight for m in self.C_modules], [m.weight for m in self.f_modules],
-                                            [m.bias for m in self.C_modules], [m.bias for m in self.f_modules])
-                # args.gate_split (the default): the [comm | h] . [C_i | F_i]^T product as exact bf16 split products too
-                wp3 = ops.commnet_pack_split([m.weight for m in self.C_modules], [m.weight for m in self.f_modules]) \
-                    if getattr(self.args, 'gate_split', True) else None
-                self._cn = dict(wt=wt, enc_bias=self.encoder.bias.detach().contiguous(), wp=wp, wp3=wp3, bias=bias,
-                                loc_table=self.obs_table(wt) if self.obs_table is not None else None,
-                                w_heads=torch.cat([hd.weight for hd in self.heads] + [self.value_head.weight], 0).contiguous(),
-                                b_heads=torch.cat([hd.bias for hd in self.heads] + [self.value_head.bias], 0).contiguous())
-            self._cn_key = key
-        return self._cn
+        C, Fm = list(self.C_modules), list(self.f_modules)
+        split = bool(getattr(self.args, 'gate_split', True))
+
+        def build():
+            wt = self.encoder.weight.t().contiguous()
+            wp, bias = ops.commnet_pack([m.weight for m in C], [m.weight for m in Fm], [m.bias for m in C], [m.bias for m in Fm])
+            # args.gate_split (the default): the [comm | h] . [C_i | F_i]^T product as exact bf16 split products too
+            wp3 = ops.commnet_pack_split([m.weight for m in C], [m.weight for m in Fm]) if split else None
+            return dict(wt=wt, enc_bias=self.encoder.bias.detach().clone(), wp=wp, wp3=wp3, bias=bias,
+                        loc_table=self.obs_table(wt) if self.obs_table is not None else None, **self._heads_cat())
+        return self._derived('_cn', [self.encoder.weight, self.encoder.bias, self.value_head.weight, self.value_head.bias]
+                             + [q for m in C + Fm for q in (m.weight, m.bias)]
+                             + [q for hd in self.heads for q in (hd.weight, hd.bias)], (split,), build)
+
+    def _encode_into(self, cache, x, dst, hold=None):
+        """encoder(x) + cache['enc_bias'] -> dst (R, H): the env's sparse gather when x is the env's own obs, else a dense GEMM
+        (through a contiguous buffer kept in `hold` when dst is a strided view)."""
+        if self._x_is_env_obs(x):
+            return self.obs_encoder(cache['wt'], cache['enc_bias'], out=dst, loc_table=cache['loc_table'])
+        enc = dst
+        if not dst.is_contiguous():
+            enc = hold.get('enc')
+            if enc is None:
+                enc = hold['enc'] = torch.empty(dst.shape, dtype=torch.float32, device=dst.device)
+        torch.addmm(cache['enc_bias'], x.reshape(dst.shape[0], -1), cache['wt'], out=enc)
+        if enc is not dst:
+            dst.copy_(enc)
 
     def _forward_commnet(self, x, info):
         n, H = self.nagents, self.hid_size
         batch = x.size(0)
         R, dev = batch * n, x.device
         cn = self._commnet_cache()
-        alive = self._mask(info, 'alive_mask', batch, dev)
-        comm_action = self._mask(info, 'comm_action', batch, dev) if self.args.hard_attn else None
-        mode_avg = hasattr(self.args, 'comm_mode') and self.args.comm_mode == 'avg'
+        alive, comm_action, mode_avg, mz = self._call_inputs(info, batch, dev)
         buf = getattr(self, '_cnb', None)
         if buf is None or buf.shape[0] != R or buf.device != dev:
             buf = self._cnb = torch.empty((R, H), dtype=torch.float32, device=dev)
-        if self._x_is_env_obs(x):
-            self.obs_encoder(cn['wt'], cn['enc_bias'], out=buf, loc_table=cn['loc_table'])
-        else:
-            torch.addmm(cn['enc_bias'], x.reshape(R, -1), cn['wt'], out=buf)             # dense encoder GEMM
+        self._encode_into(cn, x, buf)
         out = ops.commnet_forward(buf, batch, n, cn['wp'], cn['bias'], cn['w_heads'], cn['b_heads'],
-                                  self.args.naction_heads, mode_avg, bool(self.args.comm_mask_zero), alive, comm_action,
-                                  wp3=cn.get('wp3'))
+                                  self.args.naction_heads, mode_avg, mz, alive, comm_action, wp3=cn.get('wp3'))
         self.commnet_forwards = getattr(self, 'commnet_forwards', 0) + 1
         self.sampled = False
         action, value = self._split_out(out, batch, n)
@@ -361,13 +465,8 @@ class CommNetMLP(nn.Module):
         tw = self._twin_for(x)
         if tw is not None:
             return tw.commnet_step_ok(env, x)
-        if not self._commnet_ok(x) or not hasattr(env, '_h'):
-            return False
-        if getattr(self.obs_encoder, '__self__', None) is not env or not self._x_is_env_obs(x):
-            return False
-        if x.shape[0] != env.nenvs or self.nagents != env.nagents_env:
-            return False
-        return ops.commnet_step_supported(env, self.hid_size)
+        return self._commnet_ok(x) and self._env_ok(env) and self._obs_ok(env, x) \
+            and ops.commnet_step_supported(env, self.hid_size)
 
     def step_env_commnet(self, env, x, info, action, reward, done, alive=None, is_completed=None, obs=None, out=None, h_in=None,
                          h_out=None):
@@ -379,19 +478,15 @@ class CommNetMLP(nn.Module):
         if tw is not None:
             assert h_in is None, "the tanh recurrence runs at the kernels' own hidden sizes"
             r = tw.step_env_commnet(env, x, info, action, reward, done, alive, is_completed, obs, out)
-            self._twin_done(tw)
+            self._twin_box.done()
             return r
         n, H = self.nagents, self.hid_size
         batch = x.size(0)
         R, dev = batch * n, x.device
         cn = self._commnet_cache()
-        alive_in = self._mask(info, 'alive_mask', batch, dev)
-        comm_in = self._mask(info, 'comm_action', batch, dev) if self.args.hard_attn else None
-        mode_avg = hasattr(self.args, 'comm_mode') and self.args.comm_mode == 'avg'
-        heads = [int(a) for a in self.args.naction_heads]
-        if out is None:
-            out = torch.empty((R, sum(heads) + 1), dtype=torch.float32, device=dev)
-        ops.commnet_step(env, cn, H, heads, mode_avg, bool(self.args.comm_mask_zero), alive_in, comm_in, out, action, reward,
+        alive_in, comm_in, mode_avg, mz = self._call_inputs(info, batch, dev)
+        heads, out = self._step_out(out, R, dev)
+        ops.commnet_step(env, cn, H, heads, mode_avg, mz, alive_in, comm_in, out, action, reward,
                          done, alive, is_completed, obs, h_in=h_in, h_out=h_out)
         self.commnet_steps = getattr(self, 'commnet_steps', 0) + 1
         action_out, value = self._split_out(out, batch, n)
@@ -429,53 +524,35 @@ class CommNetMLP(nn.Module):
         tw = self._twin() if not torch.is_grad_enabled() else None
         if tw is not None:                                       # (the Trainer refreshes derived weights before replays)
             fc = tw._fused_cache()
-            self._twin_done(tw)
+            self._twin_box.done()
             return fc
-        ps = [self.encoder.weight, self.encoder.bias] + [q for m in self.C_modules for q in (m.weight, m.bias)] + [
-              self.f_module.weight_ih, self.f_module.weight_hh, self.f_module.bias_ih, self.f_module.bias_hh,
-              self.value_head.weight, self.value_head.bias] + [p for hd in self.heads for p in (hd.weight, hd.bias)]
+        f, C0 = self.f_module, self.C_modules[0]
         split = self._gate_split()
-        key = tuple((p._version, p.data_ptr()) for p in ps) + (split,)
-        if getattr(self, '_fc_key', None) != key:
-            with torch.no_grad():
-                new = dict(
-                    wt=self.encoder.weight.t().contiguous(),
-                    enc_bias=(self.encoder.bias + self.C_modules[0].bias).contiguous(),    # comm.py:206 bias, Q24
-                    c_wt=self.C_modules[0].weight.t().contiguous(),
-                    w_cat_t=torch.cat([self.f_module.weight_ih, self.f_module.weight_hh], 1).t().contiguous(),
-                    b_cat=(self.f_module.bias_ih + self.f_module.bias_hh).contiguous(),
-                    w_heads=torch.cat([hd.weight for hd in self.heads] + [self.value_head.weight], 0).contiguous(),
-                    b_heads=torch.cat([hd.bias for hd in self.heads] + [self.value_head.bias], 0).contiguous())
-                new['loc_table'] = self.obs_table(new['wt']) if self.obs_table is not None else None
-                if self._mega_wanted():
-                    new.update(ops.policy_step_pack(self.C_modules[0].weight, self.f_module.weight_ih,
-                                                    self.f_module.weight_hh))
-                    if split:   # the gate product as exact bf16 split products (ruling of round 3's verdict)
-                        new['ps_l_wp3'] = ops.policy_pack_split(self.f_module.weight_ih, self.f_module.weight_hh)
-                        if self.hid_size in (64, 128, 256):        # the update half's fused input gradient (bptt)
-                            new['ps_l_wp3_bwd'] = ops.policy_pack_split_bwd(self.f_module.weight_ih, self.f_module.weight_hh)
-                    for i in range(1, self.comm_passes):         # comm_passes > 1: what pass i swaps in (C_modules[i])
-                        ci = self.C_modules[i]
-                        new['enc_bias_p%d' % i] = (self.encoder.bias + ci.bias).contiguous()
-                        new['enc_dbias_p%d' % i] = (ci.bias - self.C_modules[0].bias).contiguous()
-                        new['ps_c_wp_p%d' % i] = ops.policy_step_pack(ci.weight, self.f_module.weight_ih,
-                                                                     self.f_module.weight_hh)['ps_c_wp']
-                old = getattr(self, '_fc', None)
-                same = old is not None and old.keys() == new.keys() and all(
-                    (old[k] is None) == (new[k] is None) and (new[k] is None or (old[k].shape == new[k].shape
-                                                                                 and old[k].device == new[k].device))
-                    for k in new)
-                if same:
-                    # a new weight version: refresh the derived tensors IN PLACE — captured step graphs hold their
-                    # addresses (a re-allocation would leave the graphs reading freed / stale memory)
-                    for k, v in new.items():
-                        if v is not None:
-                            old[k].copy_(v)
-                else:
-                    self._fc = new
-                    self.cache_generation = getattr(self, 'cache_generation', 0) + 1   # addresses changed: graphs stale
-            self._fc_key = key
-        return self._fc
+
+        def build():
+            new = dict(
+                wt=self.encoder.weight.t().contiguous(),
+                enc_bias=(self.encoder.bias + C0.bias).contiguous(),                       # comm.py:206 bias, Q24
+                c_wt=C0.weight.t().contiguous(),
+                w_cat_t=torch.cat([f.weight_ih, f.weight_hh], 1).t().contiguous(),
+                b_cat=(f.bias_ih + f.bias_hh).contiguous(), **self._heads_cat())
+            new['loc_table'] = self.obs_table(new['wt']) if self.obs_table is not None else None
+            if self._mega_wanted():
+                new.update(ops.policy_step_pack(C0.weight, f.weight_ih, f.weight_hh))
+                if split:   # the gate product as exact bf16 split products (ruling of round 3's verdict)
+                    new['ps_l_wp3'] = ops.policy_pack_split(f.weight_ih, f.weight_hh)
+                    if self.hid_size in (64, 128, 256):            # the update half's fused input gradient (bptt)
+                        new['ps_l_wp3_bwd'] = ops.policy_pack_split_bwd(f.weight_ih, f.weight_hh)
+                for i in range(1, self.comm_passes):             # comm_passes > 1: what pass i swaps in (C_modules[i])
+                    ci = self.C_modules[i]
+                    new['enc_bias_p%d' % i] = (self.encoder.bias + ci.bias).contiguous()
+                    new['enc_dbias_p%d' % i] = (ci.bias - C0.bias).contiguous()
+                    new['ps_c_wp_p%d' % i] = ops.policy_step_pack(ci.weight, f.weight_ih, f.weight_hh)['ps_c_wp']
+            return new
+        return self._derived('_fc', [self.encoder.weight, self.encoder.bias]
+                             + [q for m in self.C_modules for q in (m.weight, m.bias)]
+                             + [f.weight_ih, f.weight_hh, f.bias_ih, f.bias_hh, self.value_head.weight, self.value_head.bias]
+                             + [q for hd in self.heads for q in (hd.weight, hd.bias)], (split,), build)
 
     def _forward_fused(self, x, info):
         n, H = self.nagents, self.hid_size
@@ -484,30 +561,19 @@ class CommNetMLP(nn.Module):
         R = batch * n
         dev = x.device
         fc = self._fused_cache()
-        alive = self._mask(info, 'alive_mask', batch, dev)
-        comm_action = self._mask(info, 'comm_action', batch, dev) if self.args.hard_attn else None
-        mode_avg = hasattr(self.args, 'comm_mode') and self.args.comm_mode == 'avg'
+        alive, comm_action, mode_avg, mz = self._call_inputs(info, batch, dev)
         self.sampled = False
         if 'ps_l_wp' in fc and n <= 64:
             # everything after the encoder in ONE launch (ic3_policy_forward: communication block, C, LSTMCell, heads,
             # log_softmax; comm / inp / gates stay in LDS and registers)
-            mb = getattr(self, '_mb', None)
-            if mb is None or mb['h'].shape[0] != R or mb['h'].device != dev:
-                mb = self._mb = dict(h=torch.empty((R, H), dtype=torch.float32, device=dev),
-                                     c=torch.empty((R, H), dtype=torch.float32, device=dev))
+            mb = self._state_buffers(R, dev)
             h, c = mb['h'], mb['c']
-            if hidden_state.data_ptr() != h.data_ptr():            # fresh hidden state from the caller (t = 0)
-                h.copy_(hidden_state.detach().reshape(R, H))
-            if cell_state.data_ptr() != c.data_ptr():
-                c.copy_(cell_state.detach().reshape(R, H))
+            self._take_state(h, hidden_state)
+            self._take_state(c, cell_state)
             enc = mb.get('enc')
             if enc is None:
                 enc = mb['enc'] = torch.empty((R, H), dtype=torch.float32, device=dev)
-            if self._x_is_env_obs(x):
-                self.obs_encoder(fc['wt'], fc['enc_bias'], out=enc, loc_table=fc['loc_table'])
-            else:
-                torch.addmm(fc['enc_bias'], x.reshape(R, -1), fc['wt'], out=enc)       # dense encoder GEMM
-            mz = bool(self.args.comm_mask_zero)
+            self._encode_into(fc, x, enc)
             self.mega_forwards = getattr(self, 'mega_forwards', 0) + 1
             for i in range(self.comm_passes - 1):                 # comm.py:179: every pass but the last updates h, c only
                 ops.policy_forward(fc, H, self.args.naction_heads, mode_avg, mz, self._enc_of_pass(fc, mb, enc, i), batch, n,
@@ -524,20 +590,10 @@ class CommNetMLP(nn.Module):
                                   gates=torch.empty((R, 4 * H), dtype=torch.float32, device=dev))
         xh, c = buf['xh'], buf['c']
         h_view = xh[:, H:]
-        if hidden_state.data_ptr() != h_view.data_ptr():       # fresh hidden state from the caller (t = 0)
-            h_view.copy_(hidden_state.detach().reshape(R, H))
-        if cell_state.data_ptr() != c.data_ptr():
-            c.copy_(cell_state.detach().reshape(R, H))
-        # encoder(x) + C.bias -> XH[:, :H]
-        if self._x_is_env_obs(x):
-            self.obs_encoder(fc['wt'], fc['enc_bias'], out=xh[:, :H], loc_table=fc['loc_table'])
-        else:
-            enc = buf.get('enc')
-            if enc is None:
-                enc = buf['enc'] = torch.empty((R, H), dtype=torch.float32, device=dev)
-            torch.addmm(fc['enc_bias'], x.reshape(R, -1), fc['wt'], out=enc)           # dense encoder GEMM
-            xh[:, :H].copy_(enc)
-        if self.args.comm_mask_zero:
+        self._take_state(h_view, hidden_state)
+        self._take_state(c, cell_state)
+        self._encode_into(fc, x, xh[:, :H], buf)                  # encoder(x) + C.bias -> XH[:, :H]
+        if mz:
             pass                                                                       # comm.py:40-41: C(0) = bias only
         else:
             ops.comm_masked_mean_raw(xh.view(batch, n, 2 * H)[:, :, H:], alive, comm_action, mode_avg, True,
@@ -589,36 +645,20 @@ class CommNetMLP(nn.Module):
         if tw is not None:
             hp, cp, _ = self._twin_hidden(tw, x[1][0], x[1][1], x[0].size(0) * self.nagents)
             return tw.mega_ok(env, [x[0], (hp, cp)])
-        if not (self._mega_wanted() and self._fused_ok(x) and hasattr(env, '_h')):
-            return False
-        if getattr(self.obs_encoder, '__self__', None) is not env or not self._x_is_env_obs(x[0]):
-            return False
-        if x[0].shape[0] != env.nenvs or self.nagents != env.nagents_env:
-            return False
-        ok = getattr(self, '_mega_sup', None)
-        if ok is None or ok[0] is not env:
-            ok = self._mega_sup = (env, ops.policy_step_supported(env, self.hid_size))
-        return ok[1]
+        return bool(self._mega_wanted() and self._fused_ok(x) and self._env_ok(env) and self._obs_ok(env, x[0])
+                    and self._step_supported(env))
 
     def mega_supported(self, env):
         """mega_ok() without an input: the conditions that do not depend on the tensors of a step (the Trainer asks
-        before an episode starts whether that episode will run on the one-launch path)."""
+        before an episode starts whether that episode will run on the one-launch path).  (Not _fused_ok without its input:
+        this one asks for the LSTM cell where mega_ok with one pass does not, and neither for the grad mode, hid_size % 4
+        nor _multi_pass_ok.)"""
         a = self.args
         tw = self._twin()
         if tw is not None:
             return tw.mega_supported(env)
-        if not (self._mega_wanted() and getattr(a, 'fused_policy', True) and hasattr(env, '_h')):
-            return False
-        if not (a.recurrent and getattr(a, 'rnn_type', '') == 'LSTM' and len(self.heads) <= 4):
-            return False
-        if sum(int(o) for o in a.naction_heads) + 1 > 16 or self.encoder.weight.dtype != torch.float32:
-            return False
-        if getattr(self.obs_encoder, '__self__', None) is not env or self.nagents != env.nagents_env:
-            return False
-        ok = getattr(self, '_mega_sup', None)
-        if ok is None or ok[0] is not env:
-            ok = self._mega_sup = (env, ops.policy_step_supported(env, self.hid_size))
-        return ok[1]
+        return bool(self._mega_wanted() and self._args_ok() and a.recurrent and getattr(a, 'rnn_type', '') == 'LSTM'
+                    and self._env_ok(env) and self._step_supported(env))
 
     def zero_hidden(self, batch_size, device):
         """init_hidden() for the one-launch rollout path: the persistent (h, c) buffers step_env() updates in place,
@@ -628,10 +668,7 @@ class CommNetMLP(nn.Module):
         if tw is not None:
             h, c = tw.zero_hidden(batch_size, device)
             return (h[:, :H], c[:, :H])
-        mb = getattr(self, '_mb', None)
-        if mb is None or mb['h'].shape[0] != R or mb['h'].device != device:
-            mb = self._mb = dict(h=torch.empty((R, H), dtype=torch.float32, device=device),
-                                 c=torch.empty((R, H), dtype=torch.float32, device=device))
+        mb = self._state_buffers(R, device)
         mb['h'].zero_()
         mb['c'].zero_()
         return (mb['h'], mb['c'])
@@ -650,17 +687,14 @@ class CommNetMLP(nn.Module):
             assert hidden_out is None or wide, "an in-place episode record has the twin's width (Trainer._kernel_net)"
             action_out, value, hc = tw.step_env(env, [x[0], (hp, cp)], info, action, reward, done, alive,
                                                 is_completed, obs, hidden_out, out, record_out)
-            self._twin_done(tw)
+            self._twin_box.done()
             return action_out, value, self._twin_state_out(hc, wide)
         x, (hidden_state, cell_state) = x
         batch = x.size(0)
         R = batch * n
         dev = x.device
         fc = self._fused_cache()
-        mb = getattr(self, '_mb', None)
-        if mb is None or mb['h'].shape[0] != R or mb['h'].device != dev:
-            mb = self._mb = dict(h=torch.empty((R, H), dtype=torch.float32, device=dev),
-                                 c=torch.empty((R, H), dtype=torch.float32, device=dev))
+        mb = self._state_buffers(R, dev)
         h, c = mb['h'], mb['c']
         if hidden_out is not None and self.comm_passes == 1:
             # the caller keeps the state ENTERING every step (the update half's episode record): read it where it is, write
@@ -677,20 +711,10 @@ class CommNetMLP(nn.Module):
         else:
             assert record_out is None, "the gate record comes with the in-place episode record (one pass)"
             hidden_out = None
-            if hidden_state.data_ptr() != h.data_ptr():        # fresh hidden state from the caller (t = 0)
-                h.copy_(hidden_state.detach().reshape(R, H))
-            if cell_state.data_ptr() != c.data_ptr():
-                c.copy_(cell_state.detach().reshape(R, H))
-        alive_in = self._mask(info, 'alive_mask', batch, dev)
-        comm_in = self._mask(info, 'comm_action', batch, dev) if self.args.hard_attn else None
-        mode_avg = hasattr(self.args, 'comm_mode') and self.args.comm_mode == 'avg'
-        heads = [int(a) for a in self.args.naction_heads]
-        OT = sum(heads) + 1
-        if out is None:
-            out = torch.empty((R, OT), dtype=torch.float32, device=dev)   # per call: a Transition keeps its action_out
-        else:                        # the caller's buffer (hipGraph mode: nothing is allocated inside a captured step)
-            assert out.is_contiguous() and tuple(out.shape) == (R, OT) and out.dtype == torch.float32
-        mz = bool(self.args.comm_mask_zero)
+            self._take_state(h, hidden_state)
+            self._take_state(c, cell_state)
+        alive_in, comm_in, mode_avg, mz = self._call_inputs(info, batch, dev)
+        heads, out = self._step_out(out, R, dev)
         if ops.policy_step_passes_supported(fc, H, self.comm_passes) and getattr(self.args, 'passes_in_launch', True):
             # comm.py:179-218 as a loop inside ONE launch (round 5): the hidden state stays on chip between the passes
             ops.policy_step(env, fc, H, heads, mode_avg, mz, h, c, alive_in, comm_in, out, action, reward, done, alive,
@@ -707,7 +731,7 @@ class CommNetMLP(nn.Module):
         """self.encoder(x) (comm.py:51,119); during no-grad rollouts optionally via the env's sparse gather."""
         if self.hid_size % 4 == 0 and self._x_is_env_obs(x):
             w = self.encoder.weight
-            key = (w._version, w.data_ptr())
+            key = _param_key([w])
             if self._wt_cache[0] != key:
                 wt = w.detach().t().contiguous()
                 self._wt_cache = (key, wt, self.obs_table(wt) if self.obs_table is not None else None)

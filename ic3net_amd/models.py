@@ -10,91 +10,45 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-
-class _StandInArgs(object):
-    """The args of a baseline, read live, as the communicating module's constructor and kernels read them: one pass, the
-    communication block switched off (comm_mask_zero: C sees zeros, comm.py:40-41), no gate head."""
-    _FIXED = dict(comm_passes=1, comm_mask_zero=True, hard_attn=False, share_weights=False, comm_init='uniform', commnet=True,
-                  comm_mode='avg', comm_action_one=False)
-
-    def __init__(self, base, recurrent):
-        object.__setattr__(self, '_base', base)
-        object.__setattr__(self, '_rec', bool(recurrent))
-
-    def __getattr__(self, k):
-        if k in _StandInArgs._FIXED:
-            return _StandInArgs._FIXED[k]
-        if k == 'recurrent':
-            return object.__getattribute__(self, '_rec')
-        if k == 'rnn_type':
-            return 'LSTM' if object.__getattribute__(self, '_rec') else 'MLP'
-        return getattr(object.__getattribute__(self, '_base'), k)
-
-    def __setattr__(self, k, v):
-        setattr(object.__getattribute__(self, '_base'), k, v)
+from .comm import _ArgsView, _DerivedPolicy, _param_key
 
 
-class _KernelStandIn(object):
-    """The ONE-LAUNCH rollout of a baseline (round 5).  models.MLP is the non-recurrent CommNet module with one pass and the
-    communication block off — h = tanh(x + f(x) + C(0)), x = tanh(encoder(obs)) (comm.py:119-129,220-224 against
-    models.py:23-34: encoder = affine1, f = affine2, C.bias = 0) — and models.RNN with the LSTM cell is the recurrent CommNet
-    policy with the block off — LSTMCell(encoder(obs) + C.bias, (h, c)) (comm.py:209-215 against models.py:75-84).  So a
-    baseline keeps a CommNetMLP of that shape whose parameters are COPIES of its own (C: zeros), refreshed when a parameter's
-    version changes (like the zero-padded twin of comm.CommNetMLP), and its rollout steps run ic3_commnet_step /
-    ic3_policy_step on that stand-in: sparse encoder, layer(s), heads, Philox draws, env.step and the obs rows in one launch.
-    The tanh recurrence of models.RNN (rnn_type 'MLP'), h_t = tanh(affine1(obs) + affine2(h_{t-1})), is the non-recurrent stand-in's
-    layer with x = enc (no tanh) and h_0 = h_{t-1}: it runs ic3_commnet_step with `h_in` on a stand-in of that shape (RNN.__init__)."""
+# The args of a baseline as the communicating module's constructor and kernels read them (comm._ArgsView, live): one pass, the
+# communication block switched off (comm_mask_zero: C sees zeros, comm.py:40-41), no gate head.
+_STAND_IN_ARGS = dict(comm_passes=1, comm_mask_zero=True, hard_attn=False, share_weights=False, comm_init='uniform', commnet=True,
+                      comm_mode='avg', comm_action_one=False)
+
+
+class _KernelStandIn(_DerivedPolicy):
+    """The ONE-LAUNCH rollout of a baseline.  models.MLP is the non-recurrent CommNet module with one pass and the communication
+    block off — h = tanh(x + f(x) + C(0)), x = tanh(encoder(obs)) (comm.py:119-129,220-224 against models.py:23-34: encoder =
+    affine1, f = affine2, C.bias = 0) — and models.RNN with the LSTM cell is the recurrent CommNet policy with the block off —
+    LSTMCell(encoder(obs) + C.bias, (h, c)) (comm.py:209-215 against models.py:75-84).  So a baseline holds a CommNetMLP of that
+    shape whose parameters are COPIES of its own (C: zeros) — comm._DerivedPolicy, the holder of the zero-padded twin too:
+    refilled in place when a parameter's version changes — and its rollout steps run ic3_commnet_step / ic3_policy_step on that
+    stand-in: sparse encoder, layer(s), heads, Philox draws, env.step and the obs rows in one launch.  The tanh recurrence of
+    models.RNN (rnn_type 'MLP'), h_t = tanh(affine1(obs) + affine2(h_{t-1})), is the non-recurrent stand-in's layer with x = enc
+    (no tanh) and h_0 = h_{t-1}: it runs ic3_commnet_step with `h_in` on a stand-in of that shape (RNN.__init__).  Replayed
+    graphs never run Python: MLP.refresh_derived() brings the copies and the stand-in's packed weights up to date, in place."""
 
     def __init__(self, owner, recurrent):
-        self.owner, self.recurrent, self.net, self.key = owner, recurrent, None, None
+        view = _ArgsView(owner.args, recurrent=bool(recurrent), rnn_type='LSTM' if recurrent else 'MLP', **_STAND_IN_ARGS)
+        super(_KernelStandIn, self).__init__(owner, view, owner.affine1.in_features, self._fill)
+        self.recurrent = recurrent
+
+    def _fill(self, o, n):
+        pairs = [(o.affine1, n.encoder), (o.lstm_unit, n.f_module) if self.recurrent else (o.affine2, n.f_modules[0])]
+        for mine, theirs in pairs + list(zip(list(o.heads) + [o.value_head], list(n.heads) + [n.value_head])):
+            for (k, src), (k2, dst) in zip(mine.named_parameters(), theirs.named_parameters()):
+                assert k == k2 and src.shape == dst.shape, (k, k2)
+                dst.copy_(src)
 
     def get(self):
-        from .comm import CommNetMLP
-        o = self.owner
-        w = o.affine1.weight
-        if not w.is_cuda or w.dtype != torch.float32 or not getattr(o.args, 'mega_policy', True):
+        """The stand-in, up to date — or None: it exists for fp32 on the device under args.mega_policy."""
+        w = self.owner.affine1.weight
+        if not w.is_cuda or w.dtype != torch.float32 or not getattr(self.owner.args, 'mega_policy', True):
             return None
-        if self.net is None or self.net.encoder.weight.device != w.device:
-            self.net = CommNetMLP(_StandInArgs(o.args, self.recurrent), o.affine1.in_features).to(device=w.device, dtype=w.dtype)
-            for q in self.net.parameters():
-                q.requires_grad_(False)
-                q.zero_()
-            self.key = None
-        key = tuple((q._version, q.data_ptr()) for q in o.parameters())
-        if key != self.key:
-            with torch.no_grad():
-                n = self.net
-                n.encoder.weight.copy_(o.affine1.weight)
-                n.encoder.bias.copy_(o.affine1.bias)
-                if self.recurrent:
-                    for k in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh'):
-                        getattr(n.f_module, k).copy_(getattr(o.lstm_unit, k))
-                else:
-                    n.f_modules[0].weight.copy_(o.affine2.weight)
-                    n.f_modules[0].bias.copy_(o.affine2.bias)
-                for mine, theirs in zip(list(o.heads) + [o.value_head], list(n.heads) + [n.value_head]):
-                    theirs.weight.copy_(mine.weight)
-                    theirs.bias.copy_(mine.bias)
-            self.key = key
-        n = self.net
-        n.obs_encoder, n.obs_table, n.sample_into = o.obs_encoder, getattr(o, 'obs_table', None), getattr(o, 'sample_into', None)
-        return n
-
-    def done(self):
-        """mirror what the Trainer reads off the policy after a call"""
-        for k in ('mega_steps', 'commnet_steps', 'cache_generation'):
-            if k in self.net.__dict__:
-                self.owner.__dict__[k] = self.net.__dict__[k]
-        self.owner.sampled = self.net.sampled
-        self.owner.__dict__['_fc'] = True          # (Trainer.begin_episode: derived weights exist -> refresh them before replays)
-
-    def refresh(self):
-        """Trainer.begin_episode in hipGraph mode: replays never run Python, so the copies and the packed weights derived from
-        them are brought up to date here (in place: the graphs hold their addresses)."""
-        n = self.get()
-        if n is not None:
-            n._fused_cache() if self.recurrent else n._commnet_cache()
-            self.done()
+        return super(_KernelStandIn, self).get()
 
 
 class MLP(nn.Module):
@@ -128,14 +82,19 @@ class MLP(nn.Module):
         self._stand_in.done()
         return out
 
-    def _fused_cache(self):
-        if self.__dict__.get('_stand_in') is not None:
-            self._stand_in.refresh()
+    def refresh_derived(self):
+        """Trainer.begin_episode in front of graph replays (comm.CommNetMLP.refresh_derived): the stand-in's copies of the
+        parameters and the caches it has built, in place."""
+        si = self.__dict__.get('_stand_in')
+        n = si.get() if si is not None and si.net is not None else None
+        if n is not None:
+            n.refresh_derived()
+            si.done()
 
     def _affine1(self, x):
         if self.obs_encoder is not None and not torch.is_grad_enabled() and self.args.hid_size % 4 == 0:
             w = self.affine1.weight
-            key = (w._version, w.data_ptr())
+            key = _param_key([w])
             if self._wt_cache[0] != key:
                 self._wt_cache = (key, w.detach().t().contiguous())
             return self.obs_encoder(self._wt_cache[1], self.affine1.bias.detach())
@@ -227,9 +186,8 @@ class RNN(MLP):
         from . import ops
         if self.args.rnn_type == 'LSTM' or torch.is_grad_enabled() or ops.padded_hidden(self.hid_size) is not None:
             return False
-        n = self._stand_in.get()
-        return n is not None and hasattr(env, '_h') and getattr(self.obs_encoder, '__self__', None) is env \
-            and self.nagents == env.nagents_env and ops.commnet_step_supported(env, self.hid_size)
+        n = self._stand_in.get()                             # (the stand-in has this policy's agents and sparse encoder)
+        return n is not None and n._env_ok(env) and ops.commnet_step_supported(env, self.hid_size)
 
     def rnn_step_ok(self, env, x):
         """True when step_env_rnn() may replace forward + select_action + env.step for this input: the env's own observation, a

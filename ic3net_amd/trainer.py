@@ -272,12 +272,12 @@ class Trainer(object):
                     self._rec.h_fin = None
         self._ones_comm = self._static['ones'] if args.comm_action_one else None
         self._zeros_comm = self._static['zeros']
-        if self._use_graph() and self._graphs and getattr(self.policy_net, '_fc', None) is not None:
+        if self._use_graph() and self._graphs and hasattr(self.policy_net, 'refresh_derived'):
             # weights may have changed since the capture (optimizer.step, checkpoint.load): replays never call
             # forward(), so refresh the derived weight tensors here — in place, the graphs hold their addresses; if
             # they had to be re-allocated the captured graphs are stale and are dropped
             with torch.no_grad():
-                self.policy_net._fused_cache()
+                self.policy_net.refresh_derived()
             gen = getattr(self.policy_net, 'cache_generation', 0)
             if gen != self._graph_gen:
                 self._graphs.clear()

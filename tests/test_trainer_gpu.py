@@ -200,31 +200,47 @@ def test_hip_graph_replay_equals_eager(env_name, flags):
                 np.testing.assert_array_equal(e[4][k], g[4][k], err_msg=k)
 
 
+# id -> (policy class, flags, the family's one-launch counter); "64" / "32": the recurrent IC3Net LSTM policy and its twin
+REPLAY_POLICIES = {
+    "64": ("comm", dict(hid_size=64, ic3net=True, recurrent=True, rnn_type='LSTM'), 'mega_steps'),
+    "32": ("comm", dict(hid_size=32, ic3net=True, recurrent=True, rnn_type='LSTM'), 'mega_steps'),
+    "mlp2-64": ("comm", dict(hid_size=64, commnet=True, comm_passes=2), 'commnet_steps'),     # non-recurrent module, 2 passes
+    "mlp2-32": ("comm", dict(hid_size=32, commnet=True, comm_passes=2), 'commnet_steps'),     # ... as its zero-padded twin
+    "ic-64": ("mlp", dict(hid_size=64), 'commnet_steps'),                                     # models.MLP on its stand-in
+    "iric_tanh-64": ("rnn", dict(hid_size=64, recurrent=True, rnn_type='MLP'), 'commnet_steps'),
+    "iric_lstm-64": ("rnn", dict(hid_size=64, recurrent=True, rnn_type='LSTM'), 'mega_steps'),
+}
+
+
 @pytest.mark.parametrize("mode", [True, 'step'], ids=["episode-graph", "step-graphs"])
-@pytest.mark.parametrize("hid", [64, 32])
-def test_graph_replay_follows_weight_updates(hid, mode):
+@pytest.mark.parametrize("policy", list(REPLAY_POLICIES))
+def test_graph_replay_follows_weight_updates(policy, mode):
     """Replayed step graphs hold the ADDRESSES of the derived weight tensors (packed layouts; for hid 32 the zero-padded
-    twin's parameters and ITS packed layouts): after the parameters change in place (optimizer.step, checkpoint load) the
-    next episode must play the new weights — begin_episode refreshes the derived tensors in place."""
-    from ic3net_amd import data, trainer as trmod
+    twin's parameters and ITS packed layouts; for a baseline its stand-in's): after the parameters change in place
+    (optimizer.step, checkpoint load) the next episode must play the new weights — begin_episode refreshes every derived
+    tensor in place, for every policy family.  Between the episodes a NaN-filled block is allocated and released, so a replay
+    that read a released block would not pass by luck."""
+    from ic3net_amd import data, models, trainer as trmod
     from ic3net_amd.action_utils import parse_action_args
     from ic3net_amd.comm import CommNetMLP
-    flags = dict(nagents=5, dim=10, vision=1, hid_size=hid, ic3net=True, recurrent=True, detach_gap=10)
+    kind, pflags, counter = REPLAY_POLICIES[policy]
+    flags = dict(nagents=5, dim=10, vision=1, detach_gap=10, **pflags)
 
     def run(graph):
         a = build_args("predator_prey", dict(flags), 5, 12, 64, 5)
         a.env_id_offset = 0
         a.hip_graph = graph
         env = data.init("predator_prey", a, False)
-        a.num_actions = [env.num_actions, 2]
-        a.dim_actions = env.dim_actions + 1
+        a.num_actions, a.dim_actions = [env.num_actions], env.dim_actions
+        if a.hard_attn and a.commnet:
+            a.num_actions, a.dim_actions = [env.num_actions, 2], env.dim_actions + 1
         a.num_inputs = env.observation_dim
-        a.recurrent, a.rnn_type = True, 'LSTM'
+        a.continuous = False
         parse_action_args(a)
         torch.manual_seed(11)
-        net = CommNetMLP(a, a.num_inputs).cuda()
+        net = {'comm': CommNetMLP, 'mlp': models.MLP, 'rnn': models.RNN}[kind](a, a.num_inputs).cuda()
         tr = trmod.Trainer(a, net, env)
-        out = []
+        out, junk = [], []
         for ep in range(6):
             if ep == 3:
                 with torch.no_grad():
@@ -232,11 +248,21 @@ def test_graph_replay_follows_weight_updates(hid, mode):
                         q.mul_(0.5).add_(0.01)
             episode, _ = tr.get_episode(ep)
             out.append(([t.action.clone() for t in episode], [t.value.clone() for t in episode]))
+            junk.append(torch.full((64 * 5 * 64 * (ep + 1),), float('nan'), device='cuda'))   # (a freed block would be reused here)
+            if ep % 2:
+                junk.clear()
+            # ... and, every episode, at the sizes of the derived tensors (transposes, concatenations, packed and split layouts of
+            # the parameters: 1 to 6 times a parameter's size), so that a block one of them released is written over at once
+            fill = [torch.full((q.numel() * k,), float('nan'), device='cuda') for q in net.parameters() for k in (1, 2, 3, 4, 6)]
+            del fill
+            if ep >= 4:                                    # a replayed episode at an unchanged weight version rebuilds nothing
+                assert [q._version for q in net.parameters()] == versions, "refreshing the derived weights wrote a parameter"
+            versions = [q._version for q in net.parameters()]
         return out, tr
 
     eager, _ = run(False)
     graphed, tr = run(mode)
-    assert len(tr._graphs) == (12 if mode == 'step' else 1) and getattr(tr.policy_net, 'mega_steps', 0) > 0
+    assert len(tr._graphs) == (12 if mode == 'step' else 1) and getattr(tr.policy_net, counter, 0) > 0
     assert not all(torch.equal(x, y) for x, y in zip(eager[2][1], eager[3][1]))     # the update does change the episode
     for ep, (e, g) in enumerate(zip(eager, graphed)):
         for i in range(2):
