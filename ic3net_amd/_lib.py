@@ -66,6 +66,16 @@ class PolicyRecord(_SizedStruct):
                                   ("inp", C.c_void_p)]
 
 
+class PolicyWindow(_SizedStruct):
+    """ic3_policy_window (include/ic3_rollout.h): an ic3_policy followed by the operands of a window of T lock-steps; handed to
+    ic3_policy_step in place of a Policy, with inner_pass = WINDOW (the tag that selects this form) and its own struct_size."""
+    WINDOW = 3                                 # IC3_POLICY_WINDOW
+    ALIVE_ALL, ALIVE_PREV = 0, 1               # IC3_WINDOW_ALIVE_*: the alive mask of step t >= 1
+    COMM_ALL, COMM_LAST_HEAD, COMM_ONES = 0, 1, 2   # IC3_WINDOW_COMM_*: the gate of step t >= 1
+    _fields_ = Policy._fields_ + [("T", C.c_int32), ("alive_mode", C.c_int32), ("comm_mode", C.c_int32), ("reserved", C.c_int32),
+                                  ("gates", C.c_void_p), ("inp", C.c_void_p), ("snaps", C.c_void_p), ("snap_words", C.c_int64)]
+
+
 class Episode(_SizedStruct):
     """ic3_episode (include/ic3_rollout.h): episode buffers in, masks and reduced statistics out."""
     _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("E", C.c_int32), ("N", C.c_int32), ("auto_reset", C.c_int32),

@@ -22,6 +22,20 @@
 #define IC3_WAIT_VMEM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define IC3_WAIT_VMEM_N(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")   // at most n vector-memory operations in flight
 #endif
+// Agent-scope acquire of a hand-off through global memory (policy_step.hip's window form): `s_waitcnt vmcnt(0); buffer_inv sc1`, the
+// CU's vector L1 is invalidated.  The producer side of such a hand-off is IC3_WAIT_VMEM() in front of the barrier.  Where the compiler
+// has no such builtin (the sources compiled for a CPU, tests/host: the emulated lanes of a workgroup run one at a time on one thread,
+// every store is visible to the lane that runs next) it is a compiler fence.
+#ifndef IC3_ACQUIRE_AGENT
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_fence)
+#define IC3_ACQUIRE_AGENT() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
+#endif
+#endif
+#ifndef IC3_ACQUIRE_AGENT
+#define IC3_ACQUIRE_AGENT() asm volatile("" ::: "memory")
+#endif
+#endif
 
 namespace ic3 {
 

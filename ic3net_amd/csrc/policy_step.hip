@@ -100,6 +100,16 @@ struct StepArgs {
     StepOut so;
     PPState pp;
     TJState tj;
+    // WIN instantiation (ic3_policy_window): T lock-steps in one launch.  The pointers above are those of step 0 (h, c: slot 0 of the
+    // record); window_step_args() moves them to step t.  (At the END of the block: the argument offsets of the other instantiations
+    // stay what they were.)
+    int win_T;                  // steps of the window
+    int win_alive, win_comm;    // where the masks of step t >= 1 come from (IC3_WINDOW_ALIVE_* / IC3_WINDOW_COMM_*)
+    int win_nfld;               // fields of the handle's state block
+    const int32_t* win_state;   // the state block; field f: words [win_off[f], win_off[f] + E * win_per[f]), env-major
+    int32_t* win_snaps;         // [T][win_snap_words] or null: the state entering step t, stored by the tiles that own it
+    long long win_snap_words;
+    int win_off[16], win_per[16];
 };
 
 // zero-store slots of one K block: 16 slots (one behind every pair of MFMAs of a full tile), S of them in use, evenly
@@ -158,6 +168,32 @@ __device__ __forceinline__ void reload_args(StepArgs& a)
     for (int i = 0; i < (int)(sizeof(StepArgs) / 4); ++i) dst[i] = kp[i];
 }
 
+// The arguments of step t of a window (WIN): every per-step pointer moved by t steps, offsets in 64 bits; the masks of a step
+// t >= 1 are what step t - 1 wrote (Trainer._after_launch / _commit_step hand over the same tensors between two per-step calls).
+template <int H>
+__device__ __forceinline__ void window_step_args(StepArgs& a, int t)
+{
+    const long long R = (long long)a.E * a.N;
+    const int32_t* const alive0 = a.so.alive_out;
+    const int32_t* const action0 = a.action;
+    a.h += t * R * H;
+    a.c += t * R * H;
+    a.h_out = a.h + R * H;
+    a.c_out = a.c + R * H;
+    a.out += t * R * a.OT;
+    a.action += (long long)t * a.nheads * R;
+    a.so.reward += t * R;
+    a.so.done += (long long)t * a.E;
+    if (a.so.alive_out) a.so.alive_out += t * R;
+    if (a.so.comp_out) a.so.comp_out += t * R;
+    if (a.gates_out) a.gates_out += t * R * 4 * H;
+    if (a.xh_out) a.xh_out += t * R * 2 * H;
+    if (t > 0) {
+        a.alive_in = a.win_alive == IC3_WINDOW_ALIVE_PREV ? alive0 + (t - 1) * R : nullptr;
+        a.comm_in = a.win_comm == IC3_WINDOW_COMM_LAST_HEAD ? action0 + ((long long)(t - 1) * a.nheads + a.nheads - 1) * R : nullptr;
+    }
+}
+
 // MP = 1 (round 5): comm_passes > 1 (comm.py:179-218) as a loop INSIDE the launch — masks, positions and window descriptors
 // are built once; every pass gathers the encoder output again (its bias differs per pass: encoder.bias + C_i.bias, and a
 // kept copy would be 32 registers or 32 KB of LDS the kernel does not have), takes h from the h half of the A tile where the
@@ -166,11 +202,18 @@ __device__ __forceinline__ void reload_args(StepArgs& a)
 // REC = 1 (ic3_policy_forward on an ic3_policy_record): the caller's-encoder-output kernel (KIND 0, split product) as a RECORDING inner pass — the
 // record stores of the env instantiations (inp rows behind S7, activated gates in the cell epilogue) and an optional [H] row
 // (`enc_bias`, which KIND 0 does not read otherwise) added to every enc row as it is read.  REC = 0 compiles to what it was.
-template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0>
+// WIN = 1 (ic3_policy_step on an ic3_policy_window): the step body inside a loop over the T steps of a window — the `pass` loop is
+// the step loop.  Every step reads the arguments again and moves them to its step (window_step_args), stores the tile's share of the
+// env snapshot in front of env.step, and ends with the hand-off to the next step: what step t + 1 reads back (the env's integer
+// state, slot t + 1 of (h, c), the alive slice, the last head's draws) was written by OTHER lanes and waves of this workgroup, so
+// behind the step's stores come the drain of every wave's stores, the workgroup barrier and an agent-scope acquire (the vector L1
+// is invalidated; see the hand-off itself for the pairing and what the full agent-scope release cost).  WIN = 0 compiles to what it was.
+template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0, int WIN = 0>
 __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(const StepArgs a_in)
 {
     static_assert(!MP || (SPLIT && KIND != 0), "the in-launch pass loop exists for the split gate product on an env handle");
     static_assert(!REC || (SPLIT && KIND == 0 && !MP), "the recording pass exists for the split gate product on a caller's encoder output");
+    static_assert(!WIN || (SPLIT && KIND != 0 && !MP && !REC && H <= 128), "the window form exists for the one-pass split gate product on an env handle");
     constexpr int K = 2 * H, LDA = K + 4, LDA4 = LDA / 4, BM = 64, NT = 2 * H, NW = H / 32, H4 = H / 4;
     IC3_DYNAMIC_LDS(float, smem);
     float* const As = smem;                                      // [BM][LDA]: cols [0,H) enc / comm / inp, [H,2H) h / h'
@@ -200,16 +243,17 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
         zso += NW * 1024;
     };
 
-    for (int pass = 0;; ++pass) {   // (one iteration unless MP)
+    for (int pass = 0;; ++pass) {   // (one iteration unless MP; WIN: the step of the window)
     // =====================================================================================================================
     // FRONT: masks, descriptors, encoder, comm, C product, gate GEMM
     // =====================================================================================================================
     {
         StepArgs a_re;                                               // MP: the arguments again for every pass (kernarg segment),
-        if constexpr (MP != 0) reload_args(a_re);                    // nothing of them lives across a pass
-        const StepArgs& a = MP ? a_re : a_in;
+        if constexpr (MP != 0 || WIN != 0) reload_args(a_re);        // nothing of them lives across a pass
+        if constexpr (WIN != 0) window_step_args<H>(a_re, pass);
+        const StepArgs& a = (MP || WIN) ? a_re : a_in;
         int tid_v = threadIdx.x;
-        if constexpr (MP != 0) IC3_OPAQUE_VGPR(tid_v);               // (per pass: nothing derived from it is hoisted out of the pass loop)
+        if constexpr (MP != 0 || WIN != 0) IC3_OPAQUE_VGPR(tid_v);               // (per pass: nothing derived from it is hoisted out of the pass loop)
         const int tid = tid_v;
         const bool first = !MP || pass == 0, last = !MP || pass + 1 == a.npass;
         // (the pass's C weights / bias by scalar selects: indexing the arrays with `pass` would put the argument block in scratch)
@@ -773,6 +817,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
     {
         StepArgs a;
         reload_args(a);
+        if constexpr (WIN != 0) window_step_args<H>(a, pass);
         int tid = threadIdx.x;
         IC3_OPAQUE_VGPR(tid);
         const bool first = !MP || pass == 0, last = !MP || pass + 1 == a.npass;
@@ -895,6 +940,26 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
         IC3_PRIO_AT(4);
         if (MP && !last) continue;          // (uniform) the next communication pass of the step
         if (a.inner) return;   // (uniform)
+
+        // ---- WIN: the integer state ENTERING this step -> the step's snapshot, the tile's envs' words of every field (what
+        //      ic3_env_snapshot copies in front of a per-step call).  env.step (S12) is the state's only writer and sits behind two
+        //      barriers from here.  A tile's share of a field is at most EPT * (N + 1) <= 2H words (checked by the host): every load
+        //      is issued before the first store.
+        if constexpr (WIN != 0) {
+            if (a.win_snaps) {   // (uniform)
+                const int32_t* __restrict__ const st = a.win_state;
+                int32_t* __restrict__ const sn = a.win_snaps + (long long)pass * a.win_snap_words;
+                int32_t sv[16];
+#pragma unroll
+                for (int f = 0; f < 16; ++f) {
+                    sv[f] = 0;
+                    if (f < a.win_nfld && tid < nenv * a.win_per[f]) sv[f] = st[(long long)a.win_off[f] + (long long)e0 * a.win_per[f] + tid];
+                }
+#pragma unroll
+                for (int f = 0; f < 16; ++f)
+                    if (f < a.win_nfld && tid < nenv * a.win_per[f]) sn[(long long)a.win_off[f] + (long long)e0 * a.win_per[f] + tid] = sv[f];
+            }
+        }
 
         // ---- S10: heads + value head (comm.py:228,239) as a 64 x 16 x H product on v_mfma_f32_16x16x4_f32: row tile of
         //      16 rows per wave, the OT <= 16 output columns are the weight rows [0, 16) of the inp half (rows >= OT hold
@@ -1047,6 +1112,20 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                 }
             }
         }
+        if constexpr (WIN != 0) {
+            if (pass + 1 < a.win_T) {   // (uniform) the hand-off to the next step, see above
+                // Producer and consumer are waves of ONE workgroup: one CU, one XCD, one L2.  Every wave waits for its own stores
+                // (`s_waitcnt vmcnt(0)`: the write-through stores have been acknowledged by the L2; a barrier alone does not drain
+                // them), the barrier, and every wave invalidates the CU's vector L1 (agent-scope acquire: `s_waitcnt vmcnt(0);
+                // buffer_inv sc1`) before its first load of the next step.  No agent-scope RELEASE: it would also write the XCD's
+                // dirty L2 lines back — the gate / inp / (h, c) records of every resident tile, for nobody (measured:
+                // profiles/r20/window_launch.txt; the emitted sequence: profiles/r20/window_launch_codegen.txt).
+                IC3_WAIT_VMEM();
+                __syncthreads();
+                IC3_ACQUIRE_AGENT();
+                continue;
+            }
+        }
     }
     break;
     }   // pass
@@ -1083,7 +1162,7 @@ static double tiles_cost(const TileCosts& tc, int k_full, int k_half)
     return c + (k_half / 2) * tc.half_pair + (k_half & 1) * tc.lone_half;
 }
 
-template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0>
+template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0, int WIN = 0>
 static int launch_step(const StepArgs& a, int tiles, size_t lds, hipStream_t s, hipEvent_t ev0 = nullptr,
                        hipEvent_t ev1 = nullptr);
 // words of the small LDS arrays behind the A tile: sm, sscale, sact, rmask [64 each], sfm [4], sep, sts [64 each], shb [16], slb [4H]
@@ -1241,14 +1320,14 @@ static int plan_tiles(StepArgs& a, int H, const ic3_policy* p, hipStream_t s)
     return a.ntiles;
 }
 
-template <int H, int KIND, int SPLIT, int MP, int REC>
+template <int H, int KIND, int SPLIT, int MP, int REC, int WIN>
 static int launch_step(const StepArgs& a, int tiles, size_t lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     // one workgroup per tile, dispatched in tile order (full tiles first, see plan_tiles): the hardware dispatcher
     // balances them over the CUs (a fixed resident set walking a strided tile list was measured slower)
     const dim3 grid(tiles), block(2 * H);
-    if (ev0 || ev1) return launch_kernel_timed(policy_step_kernel<H, KIND, SPLIT, MP, REC>, grid, block, lds, s, ev0, ev1, a);
-    return launch_kernel(policy_step_kernel<H, KIND, SPLIT, MP, REC>, grid, block, lds, s, a);
+    if (ev0 || ev1) return launch_kernel_timed(policy_step_kernel<H, KIND, SPLIT, MP, REC, WIN>, grid, block, lds, s, ev0, ev1, a);
+    return launch_kernel(policy_step_kernel<H, KIND, SPLIT, MP, REC, WIN>, grid, block, lds, s, a);
 }
 // the env instantiation of the handle's kind
 template <int H, int SPLIT, int MP = 0>
@@ -1368,11 +1447,90 @@ extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, 
     });
 }
 
+// ic3_policy_step on an ic3_policy_window: T lock-steps of the recorded training rollout in one launch (the WIN instantiations).
+static int policy_step_window(ic3_env* env, const ic3_policy_window* w, float* h, float* c, const int32_t* alive_in,
+                              const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
+                              int32_t* alive, int32_t* is_completed, ic3_stream stream)
+{
+    const std::string who = "ic3_policy_step (ic3_policy_window)";
+    if (!env) return fail(-22, who + ": null handle");
+    // the one-shots of the per-step call have no meaning here (the descriptor names the record): disarmed, and the call refused
+    const bool armed = env->h_out || env->c_out || env->gates_out || env->xh_out || env->ev_start || env->ev_stop;
+    env->h_out = env->c_out = env->gates_out = env->xh_out = nullptr;
+    env->ev_start = env->ev_stop = nullptr;
+    if (armed)
+        return fail(-22, who + ": ic3_env_set_hidden_out / ic3_env_set_record_out / ic3_env_set_step_events armed on the handle (disarmed; the "
+                               "window's record is named by the descriptor)");
+    ic3_policy base = w->policy;                                 // (the plain descriptor, for what checks its size)
+    base.struct_size = sizeof(ic3_policy);
+    base.inner_pass = 0;
+    const ic3_policy* const p = &base;
+    if (!h || !c || !out || !action || !reward || !done) return fail(-22, who + ": null argument");
+    if (obs) return fail(-22, who + ": obs must be NULL (the window form assembles no dense observation rows)");
+    if (w->T < 1 || w->reserved) return fail(-22, who + ": T >= 1, reserved = 0");
+    if ((w->gates == nullptr) != (w->inp == nullptr)) return fail(-22, who + ": gates and inp come together");
+    if (w->snaps && w->snap_words < env->dims.state_words) return fail(-22, who + ": snap_words >= dims.state_words");
+    if (w->alive_mode != IC3_WINDOW_ALIVE_ALL && w->alive_mode != IC3_WINDOW_ALIVE_PREV) return fail(-22, who + ": alive_mode");
+    if (w->comm_mode != IC3_WINDOW_COMM_ALL && w->comm_mode != IC3_WINDOW_COMM_LAST_HEAD && w->comm_mode != IC3_WINDOW_COMM_ONES)
+        return fail(-22, who + ": comm_mode");
+    if (w->alive_mode == IC3_WINDOW_ALIVE_PREV && !alive) return fail(-22, who + ": IC3_WINDOW_ALIVE_PREV needs the alive output");
+    if (env->resets == 0) return fail(-22, who + ": reset() has not been called");
+    if (!p->enc_wt || !p->enc_bias) return fail(-22, who + ": incomplete ic3_policy (encoder)");
+    const int H = p->H;
+    const int lds = policy_step_lds(env, H);
+    if (!lds || (H != 64 && H != 128))
+        return fail(-38, who + ": needs hid_size 64 / 128, <= 64 agents per env and an env tile that fits in LDS (use one call per step)");
+    if (!p->gate_split || !p->lstm_wp3) return fail(-38, who + ": needs gate_split with lstm_wp3 (use one call per step)");
+    if (p->npasses >= 2 || p->pass_index) return fail(-38, who + ": one communication pass per step (use one call per step)");
+    StepArgs a{};
+    if (int frc = fill_policy(a, p, who.c_str())) return frc;
+    a.h = a.h_out = h;
+    a.c = a.c_out = c;
+    a.gates_out = w->gates;
+    a.xh_out = w->inp;
+    a.alive_in = alive_in;
+    a.comm_in = comm_in;
+    a.out = out;
+    a.action = action;
+    hipEvent_t ev0, ev1;
+    fill_env_args(a, env, reward, done, alive, is_completed, false, ev0, ev1);
+    a.win_T = w->T;
+    a.win_alive = w->alive_mode;
+    a.win_comm = w->comm_mode;
+    a.win_state = env->state;
+    a.win_snaps = w->snaps;
+    a.win_snap_words = w->snap_words;
+    // the handle's field table: the state is one block, a field is env-major and a tile owns its envs' words of it
+    if (env->fields.size() > 16) return fail(-38, who + ": more than 16 state fields");
+    for (const Field& f : env->fields) {
+        const int64_t per = f.count / a.E;
+        if (per * a.E != f.count || per * a.EPT > 2 * H) return fail(-38, who + ": an env tile's share of a state field does not fit");
+        a.win_off[a.win_nfld] = (int)f.off;
+        a.win_per[a.win_nfld] = (int)per;
+        a.win_nfld += 1;
+    }
+    const bool pp = env->kind == IC3_ENV_PP;
+    hipStream_t s = (hipStream_t)stream;
+    const int tiles = plan_tiles(a, H, p, s);
+    if (H == 128)
+        return pp ? launch_step<128, IC3_ENV_PP, 1, 0, 0, 1>(a, tiles, lds, s) : launch_step<128, IC3_ENV_TJ, 1, 0, 0, 1>(a, tiles, lds, s);
+    return pp ? launch_step<64, IC3_ENV_PP, 1, 0, 0, 1>(a, tiles, lds, s) : launch_step<64, IC3_ENV_TJ, 1, 0, 0, 1>(a, tiles, lds, s);
+}
+
 extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, float* c, const int32_t* alive_in,
                                const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward,
                                int32_t* done, int32_t* alive, int32_t* is_completed, ic3_stream stream)
 {
     ic3::Range range_("ic3_policy_step");
+    // (the first words of both descriptors are an ic3_policy's, as for ic3_policy_record: the tag says which one this is, and a
+    //  tagged one must have the window's size exactly)
+    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_POLICY_WINDOW) {
+        if (p->struct_size != sizeof(ic3_policy_window))
+            return fail(-22, "ic3_policy_step (ic3_policy_window): struct_size is " + std::to_string(p->struct_size) +
+                                 ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
+        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), h, c, alive_in, comm_in, out, action, obs, reward,
+                                  done, alive, is_completed, stream);
+    }
     if (int src = check_policy_struct(p, "ic3_policy_step")) return src;      // before any other field is read
     if (!env || !p || !h || !c) return fail(-22, "ic3_policy_step: null argument");
     const bool inner = p->inner_pass != 0;                       // a non-final communication pass: h, c only

@@ -239,6 +239,18 @@ class RNN(MLP):
         self._stand_in.done()
         return out
 
+    def window_supported(self, env):
+        n = self._kernel()
+        return n is not None and self.record_inplace_ok() and n.window_supported(env)
+
+    def step_env_window(self, env, info, T, *bufs):
+        """A recorded training window of T steps in ONE launch (CommNetMLP.step_env_window on the stand-in)."""
+        n = self._stand_in.get()
+        out = n.step_env_window(env, info, T, *bufs)
+        self._stand_in.done()
+        self.window_launches = getattr(self, 'window_launches', 0) + 1
+        return out
+
     def forward(self, x, info={}):
         obs, state = x
         feat, state = self._recur.step(self._affine1(obs), state)

@@ -108,6 +108,8 @@ class Trainer(object):
         """trainer.py:26-126 for E envs in lock-step: begin_episode + max_steps x step_episode + end_episode."""
         self.begin_episode(epoch)
         check_every = int(getattr(self.args, 'done_check_every', 0))
+        if self._window_launch_ok(check_every) and self._play_window():
+            return self.end_episode()                               # the T step launches as ONE launch (args.window_launch)
         if self._episode_graph_ok(check_every):
             self._play_episode_graph()                              # the T step launches as ONE hipGraph replay
             return self.end_episode()
@@ -118,6 +120,70 @@ class Trainer(object):
                     bool(self._buf['done'][:t + 1].to(torch.bool).any(0).all().item()):
                 break                                               # trainer.py:107-108 (every env is done)
         return self.end_episode()
+
+    def _window_launch_ok(self, check_every=0):
+        """args.window_launch: get_episode plays the recorded rollout of a native update — max_steps lock-steps — as ONE launch
+        (CommNetMLP.step_env_window: ic3_policy_step on an ic3_policy_window) where every step of it would be the same one-launch
+        step writing into the episode record: the in-place (h, c) record with its gate / inp rows, no dense observation rows, nothing
+        that looks at a single step (store_states, display, the step timer, done_check_every), a lock-step handle (collection
+        windows — args.auto_reset — keep the per-step path) and a policy that answers window_supported.  A window the library
+        refused (-38) is not asked for again."""
+        a, rec, raw = self.args, self._rec, getattr(self.env, 'env', None)
+        if not getattr(a, 'window_launch', False) or getattr(self, '_window_refused', False) or rec is None or raw is None:
+            return False
+        if check_every or self._auto_reset() or getattr(raw, 'auto_max_steps', 0) or getattr(a, 'store_states', False) \
+                or getattr(a, 'rollout_grad', False) or getattr(self, '_should_display', False) \
+                or getattr(raw, 'step_timer', None) is not None or self._dense_obs():
+            return False
+        if not (a.recurrent and a.rnn_type == 'LSTM') or not rec.recurrent or rec.gates is None or rec.xh is None \
+                or rec.xh.shape[2] != 2 * rec.hs.shape[2]:
+            return False
+        ok = getattr(self.policy_net, 'window_supported', None)
+        with torch.no_grad():                                      # (the grad mode the steps of this rollout run in)
+            return ok is not None and self._rec_inplace() and bool(ok(raw))
+
+    def _play_window(self):
+        """The max_steps step bodies of get_episode as one launch, and what they leave behind: the record's counters and mask views,
+        the per-step outputs, the state the window ends with.  False (nothing played, nothing changed that step 0 would not set
+        again) when the library refuses the window."""
+        args, net, rec, buf = self.args, self.policy_net, self._rec, self._buf
+        raw = self.env.env
+        T = args.max_steps
+        E, dev = self._state.shape[0], self._state.device
+        with torch.no_grad():
+            info = self._info
+            if args.hard_attn and args.commnet:                    # trainer.py:45-46 (quirk Q22)
+                info['comm_action'] = self._zeros_comm
+            self._prev_hid = self._first_hidden(self._state, False)
+            if self._prev_hid[0].data_ptr() != rec.hs[0].data_ptr():
+                return False
+            if rec.out is None:
+                rec.out = torch.empty((T, E * args.nagents, sum(int(o) for o in args.naction_heads) + 1), dtype=torch.float32, device=dev)
+            try:
+                outs = net.step_env_window(raw, info, T, rec.hs, rec.cs, rec.out, buf['action'], buf['reward'], buf['done'],
+                                           buf['alive'], buf['is_completed'], rec.gates, rec.xh, rec.snaps)
+            except NotImplementedError:
+                self._window_refused = True
+                return False
+        self.clock.t = T - 1
+        for t in range(T):                                         # what record() / _after_launch / _commit_step do per step
+            if hasattr(net, '_mask'):
+                rec.alive[t] = net._mask(info, 'alive_mask', E, dev)
+                rec.gate[t] = net._mask(info, 'comm_action', E, dev) if net.args.hard_attn else None
+            if raw.dims.kind == 2:                                 # TJ:244-247
+                info = {'alive_mask': buf['alive'][t], 'is_completed': buf['is_completed'][t]}
+            else:
+                info = {'alive_mask_device': buf['alive'][t]}
+            if args.hard_attn and args.commnet:                    # trainer.py:70-71
+                info['comm_action'] = buf['action'][t][-1] if not args.comm_action_one else self._ones_comm
+            self._step_out[t] = (None, outs[t][0], outs[t][1], None)
+        rec.n = rec.gates_n = rec.out_n = T
+        self._prev_hid = rec.slot(T)
+        self._state = self.env._flatten_obs(raw._obs) if hasattr(self.env, '_flatten_obs') else raw._obs
+        self._info = info
+        self._nsteps = T
+        self._mega_last = True
+        return True
 
     def _episode_graph_ok(self, check_every=0):
         """args.hip_graph (True / 'episode'; 'step' keeps one graph per step index): get_episode replays the whole episode —

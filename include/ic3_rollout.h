@@ -818,6 +818,51 @@ typedef struct ic3_policy_record {
     float* gates;
     float* inp;
 } ic3_policy_record;
+/* ic3_policy followed by the operands of a WINDOW of T lock-steps: handed to ic3_policy_step in place of an ic3_policy, with
+ * policy.inner_pass = IC3_POLICY_WINDOW — the tag that selects this form — AND policy.struct_size = sizeof(ic3_policy_window): a
+ * tagged descriptor of any other size is refused with -EINVAL before anything else is read or launched, and every other entry point
+ * refuses this struct by its size (the same rule as ic3_policy_record, and for the same reason: ABI 601 gains a descriptor, not a
+ * symbol).  ONE launch plays T consecutive ic3_policy_step calls of the recorded training rollout: a workgroup walks its tile of
+ * whole envs through t = 0 .. T-1 (nobody else's envs enter a tile's arithmetic), writes every per-step output at its step offset
+ * and stores its envs' share of the env snapshot in front of every step.  Everything the launch writes — and the state it leaves in
+ * the handle — is the SAME BITS as T per-step calls on the same handle (the per-step body's arithmetic, the env's own t / episode as
+ * Philox counters, no atomics).  Meaning of the call's arguments in this form:
+ *   h, c          base of the record [T+1][E*N][H]: step t reads slot t and writes slot t+1 (nothing is copied)
+ *   alive_in, comm_in   the masks of step 0 only (NULL as in the per-step call); for t >= 1 they follow from step t-1:
+ *                 alive_mode IC3_WINDOW_ALIVE_ALL: everyone (Predator-Prey), IC3_WINDOW_ALIVE_PREV: the `alive` slice of step t-1
+ *                 (Traffic-Junction; needs `alive`);  comm_mode IC3_WINDOW_COMM_ALL / IC3_WINDOW_COMM_ONES: everyone talks (no mask /
+ *                 a mask of ones: the same arithmetic), IC3_WINDOW_COMM_LAST_HEAD: the draws of the last head at step t-1 (hard_attn)
+ *   out [T][E*N][OT];  action [T][nheads][E*N];  reward, alive, is_completed [T][E][N];  done [T][E]
+ *   obs           must be NULL (the window form assembles no dense rows): anything else is -EINVAL
+ * and of the descriptor's:
+ *   gates [T][E*N][4H], inp [T][E*N][2H]   what ic3_env_set_record_out lays out per step; both NULL: no gate record
+ *   snaps, snap_words   the integer state ENTERING step t goes to snaps + t * snap_words (snap_words >= dims.state_words), byte for
+ *                 byte what ic3_env_snapshot would have copied in front of step t; snaps NULL: no snapshots
+ * All step offsets are formed in 64 bits; one step's block keeps the per-step call's 32-bit limits.  Needs gate_split with lstm_wp3,
+ * one communication pass (npasses <= 1, pass_index 0), hid_size 64 / 128 (-ENOSYS before any launch otherwise, as for an env tile
+ * that does not fit); Predator-Prey and Traffic-Junction handles, lock-step and auto-reset.  A call that finds ic3_env_set_hidden_out,
+ * ic3_env_set_record_out or ic3_env_set_step_events armed on the handle disarms them and is refused with -EINVAL.  Error messages
+ * begin "ic3_policy_step (ic3_policy_window)".
+ * (A change for callers of the per-step form: ic3_policy.inner_pass used to mean "inner pass" for ANY non-zero value.  The value
+ * IC3_POLICY_WINDOW is now this tag in ic3_policy_step — a plain ic3_policy that carries it is refused with -EINVAL as a window
+ * descriptor of the wrong size, as IC3_POLICY_RECORD_PASS already is in ic3_policy_forward.  Pass 1 for an inner pass.) */
+#define IC3_POLICY_WINDOW 3
+#define IC3_WINDOW_ALIVE_ALL 0
+#define IC3_WINDOW_ALIVE_PREV 1
+#define IC3_WINDOW_COMM_ALL 0
+#define IC3_WINDOW_COMM_LAST_HEAD 1
+#define IC3_WINDOW_COMM_ONES 2
+typedef struct ic3_policy_window {
+    ic3_policy policy;
+    int32_t T;
+    int32_t alive_mode;
+    int32_t comm_mode;
+    int32_t reserved;       /* 0 */
+    float* gates;
+    float* inp;
+    int32_t* snaps;
+    int64_t snap_words;
+} ic3_policy_window;
 
 /* The NON-recurrent CommNet module after the encoder (comm.py:127-129,179-205,220-224,228-239), every communication pass
  * in ONE launch:  x = tanh(enc);  h_0 = x;  h_{i+1} = tanh(x + f_modules[i](h_i) + C_modules[i](comm(h_i)));

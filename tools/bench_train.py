@@ -5,7 +5,8 @@ graph, rounds 1-2; dense_obs 0: the training rollout does not assemble observati
 COMM_PASSES=<P> (with SHARE_WEIGHTS=1: one C for every pass) overrides the workload's communication passes; MULTIPASS_WINDOW=0 sends
 the update of such a policy through the per-step loop instead of bptt._backward_window_multipass (the line then says which ran);
 MULTIPASS_COLLECTION=1 sends its collection-mode windows (argument 7 = 1) through the window path too (args.multipass_window_collection,
-off by default)."""
+off by default).  WINDOW_LAUNCH=1 sets args.window_launch: the recorded rollout of an update as one launch per window (the line says how
+many windows went through it)."""
 import os
 import sys
 import time
@@ -33,6 +34,7 @@ def main():
         a.multipass_window_backward = os.environ['MULTIPASS_WINDOW'] == '1'
     if over and 'MULTIPASS_COLLECTION' in os.environ:
         a.multipass_window_collection = os.environ['MULTIPASS_COLLECTION'] == '1'
+    a.window_launch = os.environ.get('WINDOW_LAUNCH', '0') == '1'
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
@@ -68,7 +70,8 @@ def main():
         over['comm_passes'], " shared" if over.get('share_weights') else "", getattr(knet, 'multipass_window_backwards', 0),
         getattr(knet, 'multipass_window_chunk', '-'), getattr(knet, 'multipass_loop_backwards', 0))
     label = wl + passes + (" (obs rows assembled in the rollout)" if a.train_dense_obs else "") + ("" if split else " (fp32 MFMA gate product)") + \
-        (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "")
+        (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "") + \
+        (" (window_launch: %d windows in one launch each)" % getattr(knet, 'window_launches', 0) if a.window_launch else "")
     print("train_batch [%s] %s E=%d: %.0f env-steps/s = %.2f M agent-steps/s (%.2f s per update of %d env-steps), "
           "peak mem %.1f GB, gemm %s" % (mode, label, E, steps / dt, a.nagents * steps / dt / 1e6, dt / updates,
                                          steps // updates, torch.cuda.max_memory_allocated() / 2 ** 30,
