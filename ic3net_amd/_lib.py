@@ -76,6 +76,16 @@ class PolicyWindow(_SizedStruct):
                                   ("gates", C.c_void_p), ("inp", C.c_void_p), ("snaps", C.c_void_p), ("snap_words", C.c_int64)]
 
 
+class CommnetWindow(_SizedStruct):
+    """ic3_commnet_window (include/ic3_rollout.h): an ic3_policy header followed by the operands of a window of T ic3_commnet_step
+    calls; handed to ic3_policy_step in place of a Policy, with inner_pass = WINDOW (the tag that selects this form) and its own
+    struct_size.  The masks' modes are PolicyWindow's."""
+    WINDOW = 4                                 # IC3_COMMNET_WINDOW
+    _fields_ = Policy._fields_ + [("T", C.c_int32), ("alive_mode", C.c_int32), ("comm_mode", C.c_int32), ("recurrence", C.c_int32),
+                                  ("wp", C.c_void_p), ("wp3", C.c_void_p), ("bias", C.c_void_p), ("h_fin", C.c_void_p),
+                                  ("snaps", C.c_void_p), ("snap_words", C.c_int64)]
+
+
 class Episode(_SizedStruct):
     """ic3_episode (include/ic3_rollout.h): episode buffers in, masks and reduced statistics out."""
     _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("E", C.c_int32), ("N", C.c_int32), ("auto_reset", C.c_int32),

@@ -492,6 +492,36 @@ class CommNetMLP(nn.Module):
         action_out, value = self._split_out(out, batch, n)
         return action_out, value.reshape(batch, n, 1)
 
+    def commnet_window_supported(self, env):
+        """step_env_commnet_window() may play a recorded training window on this env: the non-recurrent module's one-launch step at
+        this hidden size itself (a zero-padded twin answers no), no autograd, the split products, hid 64 / 128."""
+        a = self.args
+        if torch.is_grad_enabled() or self._twin() is not None or a.recurrent or not self._args_ok() \
+                or not getattr(a, 'mega_policy', True) or not self._env_ok(env):
+            return False
+        return ops.commnet_step_window_supported(env, self._commnet_cache(), self.hid_size)
+
+    def step_env_commnet_window(self, env, info, T, out, action, reward, done, alive, is_completed, snaps, hs=None, h_fin=None):
+        """T consecutive step_env_commnet() calls of the recorded training rollout in ONE launch (ic3_policy_step on an
+        ic3_commnet_window): out (T, R, OT), action (T, heads, E, N), reward / alive / is_completed (T, E, N), done (T, E), snaps
+        (T, words) the env state entering every step; hs (T+1, R, H): the tanh recurrence of models.RNN on this module as its
+        stand-in — step t reads slot t, writes slot t+1 —, h_fin (T, R, H): the hidden state every step ends with (models.MLP's
+        record); `info`: step 0's.  The masks of a step t >= 1 are what the Trainer hands over between two step_env_commnet()
+        calls (step_env_window).  No dense observation rows.  Returns [(action_out, value)] per step, views of `out`.  -38 from the
+        library surfaces as NotImplementedError before anything was launched."""
+        n, H, a = self.nagents, self.hid_size, self.args
+        assert self._twin() is None, "commnet_window_supported() answers first"
+        batch = reward.shape[1]
+        cn = self._commnet_cache()
+        alive_in, comm_in, mode_avg, mz = self._call_inputs(info, batch, out.device)
+        heads = [int(o) for o in a.naction_heads]
+        comm_mode = 'all' if not a.hard_attn else 'ones' if getattr(a, 'comm_action_one', False) else 'last_head'
+        ops.commnet_step_window(env, cn, H, heads, mode_avg, mz, T, alive_in, comm_in, out, action, reward, done, alive, is_completed,
+                                hs=hs, h_fin=h_fin, snaps=snaps, alive_prev=env.dims.kind == 2, comm_mode=comm_mode)
+        self.window_launches = getattr(self, 'window_launches', 0) + 1
+        steps = [self._split_out(out[t], batch, n) for t in range(T)]
+        return [(action_out, value.reshape(batch, n, 1)) for action_out, value in steps]
+
     def _x_is_env_obs(self, x):
         """The sparse encoder evaluates encoder(obs(env's CURRENT integer state)) without reading x; that is only
         the answer when x IS that observation, i.e. the env's own obs buffer (which env.reset/step keep in sync with

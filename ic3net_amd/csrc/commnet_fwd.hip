@@ -65,7 +65,46 @@ struct CommnetArgs {
     // other field: the offsets the other instantiations read their arguments at stay where they were.
     float* h_pass;             // [passes + 1][R][H]
     long long h_pass_stride;
+    // WIN instantiations (ic3_policy_step on an ic3_commnet_window): T steps in one launch.  The pointers above are those of step 0
+    // (h_in: slot 0 of the tanh recurrence's record); window_step_args() moves them to step t.  (Behind every other field, as above.)
+    int win_T;                  // steps of the window
+    int win_alive, win_comm;    // where the masks of step t >= 1 come from (IC3_WINDOW_ALIVE_* / IC3_WINDOW_COMM_*)
+    int win_nfld;               // fields of the handle's state block
+    const int32_t* win_state;   // the state block; field f: words [win_off[f], win_off[f] + E * win_per[f]), env-major
+    int32_t* win_snaps;         // [T][win_snap_words] or null: the state entering step t, stored by the tiles that own it
+    long long win_snap_words;
+    float* win_h_fin;           // [T][R][H] or null: the final hidden state of every step
+    int win_off[16], win_per[16];
 };
+
+// The arguments of step t of a window (WIN), as policy_step.hip's window_step_args: every per-step pointer moved by t steps, offsets
+// in 64 bits; the masks of a step t >= 1 are what step t - 1 wrote.  The tanh recurrence reads slot t of its record and writes slot
+// t + 1; without it h_out is the step's slot of h_fin.
+template <int H>
+__device__ __forceinline__ void window_step_args(CommnetArgs& a, int t)
+{
+    const long long R = (long long)a.E * a.N;
+    const int32_t* const alive0 = a.so.alive_out;
+    const int32_t* const action0 = a.action;
+    if (a.win_h_fin) a.win_h_fin += t * R * H;
+    if (a.h_in) {
+        a.h_in += t * R * H;
+        a.h_out = const_cast<float*>(a.h_in) + R * H;
+    } else {
+        a.h_out = a.win_h_fin;
+        a.win_h_fin = nullptr;
+    }
+    a.out += t * R * a.OT;
+    a.action += (long long)t * a.nheads * R;
+    a.so.reward += t * R;
+    a.so.done += (long long)t * a.E;
+    if (a.so.alive_out) a.so.alive_out += t * R;
+    if (a.so.comp_out) a.so.comp_out += t * R;
+    if (t > 0) {
+        a.alive_in = a.win_alive == IC3_WINDOW_ALIVE_PREV ? alive0 + (t - 1) * R : nullptr;
+        a.comm_in = a.win_comm == IC3_WINDOW_COMM_LAST_HEAD ? action0 + ((long long)(t - 1) * a.nheads + a.nheads - 1) * R : nullptr;
+    }
+}
 
 // Wave priority (policy_step.hip: the phases around a matrix product are dependent chains on the tile's critical path, the
 // product is throughput work): 3 outside the [comm | h] product, 0 inside.
@@ -78,10 +117,21 @@ struct CommnetArgs {
 // RECORD (ic3_commnet_forward_record, KIND 0, the wide tile): the tile's h rows also go to the h_pass ring behind x and behind every
 // pass — what the window backward of the module differentiates (ic3_commnet_backward); `out` may be null there (no heads).  A
 // template flag: the other instantiations carry no trace of it.
-template <int H, int KIND = 0, bool NARROW = false, bool RECORD = false>
-__global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void commnet_forward_kernel(const CommnetArgs a)
+// WIN (ic3_policy_step on an ic3_commnet_window): the step body inside a loop over the T steps of a window, built as
+// policy_step_kernel's WIN.  The tile plan is fixed for the launch; every step reads the arguments again and moves them to its step
+// (window_step_args), reads the masks step t - 1 left and its envs' counters from the state block, stores the tile's share of the env
+// snapshot in front of env.step, and ends with the hand-off to the next step.  No dense obs rows in this form: the PP run-based
+// store and the TJ zero fill / patches are compiled out.  WIN = 0 compiles to what it was.
+template <int H, int KIND = 0, bool NARROW = false, bool RECORD = false, int WIN = 0>
+__global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void commnet_forward_kernel(CommnetArgs a)
 {
     static_assert(!RECORD || (KIND == 0 && !NARROW), "the recording instantiation is the plain forward's");
+    static_assert(!WIN || (KIND != 0 && !RECORD && H <= 128), "the window form exists for the env instantiations at hid 64 / 128");
+    for (int step = 0;; ++step) {   // (one iteration unless WIN: the step of the window)
+    if constexpr (WIN != 0) {                                    // WIN: the arguments again for every step (kernarg segment),
+        reload_args(a);                                          // nothing of them lives across a step.  The parameter itself is
+        window_step_args<H>(a, step);                            // overwritten: a local copy behind a reference changed the code of
+    }                                                            // the other instantiations (profiles/r21/commnet_window_codegen.txt)
     CN_PRIO(3);
     constexpr int K = 2 * H, LDA = (NARROW ? H : K) + 4, LDA4 = LDA / 4, NT = 2 * H, H4 = H / 4, KB = K / 8, BM = 64;
     constexpr int HO = NARROW ? 0 : H, HO4 = HO / 4;             // column of the h half inside the tile
@@ -97,7 +147,9 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
     int32_t* const sep = reinterpret_cast<int32_t*>(rmask + BM); // [BM] episode counters of the tile's envs (Philox key)
     int32_t* const sts = sep + BM;                               // [BM] step counters
     int32_t* const tile = sts + BM;                              // env descriptors of the tile's envs
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
+    int tid_v = threadIdx.x;
+    if constexpr (WIN != 0) IC3_OPAQUE_VGPR(tid_v);              // (per step: nothing derived from it is hoisted out of the step loop)
+    const int tid = tid_v, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int col = 32 * w + li, N = a.N;
     const int bid = blockIdx.x;
     const bool short_tile = bid >= a.n_full;                      // (plan_commnet_tiles: full tiles first, short ones behind)
@@ -147,7 +199,9 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
         // per-element evaluation (it was a quarter of this kernel's vector instructions, profiles/r06/pmc_commnet.txt) — and the few
         // non-zero entries are patched in behind the draws, after every wave has seen its zero stores complete (as
         // policy_step_kernel and tj_obs_fill_kernel do; bit-identical to ic3_env_observe).
-        if constexpr (KIND == IC3_ENV_PP) {
+        if constexpr (WIN != 0) {
+            // (the window form assembles no dense rows)
+        } else if constexpr (KIND == IC3_ENV_PP) {
             // (PP rows — 145 KB per env — keep the run-based store, every element evaluated and stored once: with the zero fill the
             //  wait for a tile's 872 KB of stores in front of the patches holds the workgroup's CU slot; IC launch 0.294 against 0.261 ms)
             if (a.obs) {
@@ -383,6 +437,14 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
             *reinterpret_cast<cn_f32x4*>(a.h_out + (r0 + row) * H + 4 * c4) = As4[row * LDA4 + HO4 + c4];
         }
     }
+    if constexpr (WIN != 0) {
+        if (a.win_h_fin) {                                       // (the tanh recurrence with an h_fin record: the same rows once more)
+            for (int idx = tid; idx < rows * H4; idx += NT) {
+                const int row = idx / H4, c4 = idx - row * H4;
+                *reinterpret_cast<cn_f32x4*>(a.win_h_fin + (r0 + row) * H + 4 * c4) = As4[row * LDA4 + HO4 + c4];
+            }
+        }
+    }
     __syncthreads();
     for (int task = tid; task < rows * a.OT; task += NT) {
         const int row = task / a.OT, o = task - row * a.OT;
@@ -417,7 +479,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
     }
     if constexpr (KIND != 0) {
         // ---- the non-zero entries of the tile's obs rows, on top of the zero fill issued at the start ---------------------------
-        if constexpr (KIND == IC3_ENV_TJ) {
+        if constexpr (KIND == IC3_ENV_TJ && WIN == 0) {
             if (a.obs) {
                 IC3_WAIT_VMEM();                                 // this wave's zero stores ...
                 __syncthreads();                                 // ... and every other wave's have completed
@@ -427,6 +489,25 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
                     const int el = div_small(sg, inv_q), q = sg - el * (nsegE + N);
                     tj_obs_patch(tj_tile_at(tile + el * tjw, N), a.tj, orow0 + (size_t)el * N * a.obs_dim, a.obs_dim, WW, q);
                 }
+            }
+        }
+        // ---- WIN: the integer state ENTERING this step -> the step's snapshot, the tile's envs' words of every field (what
+        //      ic3_env_snapshot copies in front of a per-step call; the layout of policy_step_kernel's WIN).  env.step below is the
+        //      state's only writer and sits behind the barrier.  A tile's share of a field is at most EPT * per <= 2H words (checked
+        //      by the host): every load is issued before the first store.
+        if constexpr (WIN != 0) {
+            if (a.win_snaps) {   // (uniform)
+                const int32_t* const st = a.win_state;
+                int32_t* const sn = a.win_snaps + (long long)step * a.win_snap_words;
+                int32_t sv[16];
+#pragma unroll
+                for (int f = 0; f < 16; ++f) {
+                    sv[f] = 0;
+                    if (f < a.win_nfld && tid < nenv * a.win_per[f]) sv[f] = st[(long long)a.win_off[f] + (long long)e0 * a.win_per[f] + tid];
+                }
+#pragma unroll
+                for (int f = 0; f < 16; ++f)
+                    if (f < a.win_nfld && tid < nenv * a.win_per[f]) sn[(long long)a.win_off[f] + (long long)e0 * a.win_per[f] + tid] = sv[f];
             }
         }
         // ---- env.step for the tile's envs with the env-action head (env_wrappers.py:76-77) -------------------------------------
@@ -443,6 +524,21 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
             }
         }
     }
+    if constexpr (WIN != 0) {
+        if (step + 1 < a.win_T) {   // (uniform) the hand-off to the next step
+            // What step t + 1 reads back — the envs' integer state and counters (env.step above), alive[t], the last head's
+            // action[t], slot t + 1 of h — was stored by OTHER lanes and waves of THIS workgroup, all of it in front of this point.
+            // The pairing measured for policy_step_kernel's window (profiles/r20/window_launch.txt): every wave waits for its own
+            // stores, the barrier, and an agent-scope acquire invalidates the CU's vector L1 before the next step's first load.
+            // No agent-scope release (it writes the XCD's dirty L2 lines back, for nobody), no atomics.
+            IC3_WAIT_VMEM();
+            __syncthreads();
+            IC3_ACQUIRE_AGENT();
+            continue;
+        }
+    }
+    break;
+    }   // step
 }
 
 // Wp[kb][col][hh][j] = W[col][8 kb + 4 hh + j], W = [C | F] (H x 2H): the layout the kernel's B fragments read
@@ -714,4 +810,104 @@ extern "C" int ic3_commnet_step(ic3_env* env, const float* enc_wt, const float* 
         if (pp) return launch_kernel_timed(commnet_forward_kernel<HH, IC3_ENV_PP>, grid, block, (size_t)lds, s, ev0, ev1, a);
         return launch_kernel_timed(commnet_forward_kernel<HH, IC3_ENV_TJ>, grid, block, (size_t)lds, s, ev0, ev1, a);
     });
+}
+
+// ic3_policy_step on an ic3_commnet_window (dispatched there by the descriptor's tag): T steps of ic3_commnet_step in one launch —
+// the WIN instantiations.  Every refusal comes before the launch.
+int ic3::commnet_step_window(ic3_env* env, const ic3_commnet_window* w, float* h, float* c, const int32_t* alive_in,
+                             const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
+                             int32_t* alive, int32_t* is_completed, ic3_stream stream)
+{
+    using namespace ic3;
+    const std::string who = "ic3_policy_step (ic3_commnet_window)";
+    if (!env) return fail(-22, who + ": null handle");
+    // the one-shots of the per-step calls have no meaning here (the descriptor names the records): disarmed, and the call refused
+    const bool armed = env->h_out || env->c_out || env->gates_out || env->xh_out || env->ev_start || env->ev_stop;
+    env->h_out = env->c_out = env->gates_out = env->xh_out = nullptr;
+    env->ev_start = env->ev_stop = nullptr;
+    if (armed)
+        return fail(-22, who + ": ic3_env_set_hidden_out / ic3_env_set_record_out / ic3_env_set_step_events armed on the handle (disarmed; the "
+                               "window's records are named by the descriptor)");
+    const ic3_policy& p = w->policy;
+    if (p.c_wp || p.lstm_wp || p.lstm_bias || p.lstm_wp3 || p.pass_index)
+        return fail(-22, who + ": c_wp, lstm_wp, lstm_bias, lstm_wp3 and pass_index must be NULL / 0");
+    if (!p.enc_wt || !p.enc_bias || !p.head_w || !p.head_b || !w->wp || !w->bias || !out || !action || !reward || !done || p.npasses < 1)
+        return fail(-22, who + ": null argument, or npasses < 1");
+    if (obs) return fail(-22, who + ": obs must be NULL (the window form assembles no dense observation rows)");
+    if (c) return fail(-22, who + ": c must be NULL");
+    if (w->T < 1) return fail(-22, who + ": T >= 1");
+    if (w->recurrence != 0 && w->recurrence != 1) return fail(-22, who + ": recurrence is 0 or 1");
+    if (w->recurrence ? (!h || p.npasses != 1 || !p.comm_zero) : h != nullptr)
+        return fail(-22, who + ": the tanh recurrence takes h = the [T+1][E*N][H] record, one pass and the communication block off; "
+                               "without it h must be NULL");
+    if (w->snaps && w->snap_words < env->dims.state_words) return fail(-22, who + ": snap_words >= dims.state_words");
+    if (w->alive_mode != IC3_WINDOW_ALIVE_ALL && w->alive_mode != IC3_WINDOW_ALIVE_PREV) return fail(-22, who + ": alive_mode");
+    if (w->comm_mode != IC3_WINDOW_COMM_ALL && w->comm_mode != IC3_WINDOW_COMM_LAST_HEAD && w->comm_mode != IC3_WINDOW_COMM_ONES)
+        return fail(-22, who + ": comm_mode");
+    if (w->alive_mode == IC3_WINDOW_ALIVE_PREV && !alive) return fail(-22, who + ": IC3_WINDOW_ALIVE_PREV needs the alive output");
+    if (env->resets == 0) return fail(-22, who + ": reset() has not been called");
+    if (p.nheads < 1 || p.nheads > 4) return fail(-22, who + ": 1..4 action heads");
+    const int H = p.H;
+    const int lds = ic3_commnet_step_supported(env, H);
+    if (!lds || (H != 64 && H != 128))
+        return fail(-38, who + ": needs hid_size 64 / 128, <= 64 agents per env and an env tile that fits in LDS (use one call per step)");
+    if (!w->wp3) return fail(-38, who + ": needs wp3, the split products (use one call per step)");
+    CommnetArgs a{};
+    a.wp = w->wp;
+    a.wp3 = w->wp3;
+    a.bias = w->bias;
+    a.head_w = p.head_w;
+    a.head_b = p.head_b;
+    a.alive_in = alive_in;
+    a.comm_in = comm_in;
+    a.out = out;
+    a.h_in = w->recurrence ? h : nullptr;
+    a.win_h_fin = w->h_fin;
+    a.passes = p.npasses;
+    a.mode_avg = p.mode_avg;
+    a.comm_zero = p.comm_zero;
+    a.nheads = p.nheads;
+    int sz[4];
+    if (int rc = parse_heads(p.head_sizes, p.nheads, who.c_str(), a.OT, sz)) return rc;
+    a.a0 = sz[0];
+    a.a1 = sz[1];
+    a.a2 = sz[2];
+    a.a3 = sz[3];
+    a.Wt = reinterpret_cast<const cn_f32x4*>(p.enc_wt);
+    a.enc_bias = reinterpret_cast<const cn_f32x4*>(p.enc_bias);
+    a.loc_table = reinterpret_cast<const cn_f32x4*>(p.loc_table);
+    a.action = action;
+    hipEvent_t ev0, ev1;
+    fill_env_args(a, env, reward, done, alive, is_completed, false, ev0, ev1);
+    a.win_T = w->T;
+    a.win_alive = w->alive_mode;
+    a.win_comm = w->comm_mode;
+    a.win_state = env->state;
+    a.win_snaps = w->snaps;
+    a.win_snap_words = w->snap_words;
+    // the handle's field table: the state is one block, a field is env-major and a tile owns its envs' words of it
+    if (env->fields.size() > 16) return fail(-38, who + ": more than 16 state fields");
+    for (const Field& f : env->fields) {
+        const int64_t per = f.count / a.E;
+        if (per * a.E != f.count || per * a.EPT > 2 * H) return fail(-38, who + ": an env tile's share of a state field does not fit");
+        a.win_off[a.win_nfld] = (int)f.off;
+        a.win_per[a.win_nfld] = (int)per;
+        a.win_nfld += 1;
+    }
+    const bool pp = env->kind == IC3_ENV_PP;
+    hipStream_t s = (hipStream_t)stream;
+    // the tile of the per-step call: narrow for one pass with the communication block off.  No launch of this form is bound by obs
+    // stores: full + short tiles (an env's trajectory is the same bits in every plan)
+    const bool narrow = p.comm_zero && p.npasses == 1;
+    const size_t ldsn = commnet_step_lds(env, H, true);
+    const int tiles = plan_commnet_tiles(a);
+    auto go = [&](auto hid) {
+        constexpr int HH = decltype(hid)::value;
+        const dim3 grid(tiles), block(2 * HH);
+        if (narrow && pp) return launch_kernel(commnet_forward_kernel<HH, IC3_ENV_PP, true, false, 1>, grid, block, ldsn, s, a);
+        if (narrow) return launch_kernel(commnet_forward_kernel<HH, IC3_ENV_TJ, true, false, 1>, grid, block, ldsn, s, a);
+        if (pp) return launch_kernel(commnet_forward_kernel<HH, IC3_ENV_PP, false, false, 1>, grid, block, (size_t)lds, s, a);
+        return launch_kernel(commnet_forward_kernel<HH, IC3_ENV_TJ, false, false, 1>, grid, block, (size_t)lds, s, a);
+    };
+    return H == 128 ? go(std::integral_constant<int, 128>{}) : go(std::integral_constant<int, 64>{});
 }

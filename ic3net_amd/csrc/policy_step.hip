@@ -155,18 +155,8 @@ __device__ __forceinline__ TileGeom tile_geom(const StepArgs& a, int tile_id)
     return g;
 }
 
-// the kernel arguments once more, by scalar loads from the kernarg segment behind an opaque pointer (the compiler cannot
-// tell that they are the values it already holds, so none of the first copy has to stay alive for the second)
-__device__ __forceinline__ void reload_args(StepArgs& a)
-{
-    typedef const __attribute__((address_space(4))) int* KWords;
-    KWords kp = (KWords)__builtin_amdgcn_kernarg_segment_ptr();
-    IC3_OPAQUE_SGPR(kp);
-    static_assert(sizeof(StepArgs) % 4 == 0, "StepArgs is a whole number of dwords");
-    int* dst = reinterpret_cast<int*>(&a);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(StepArgs) / 4); ++i) dst[i] = kp[i];
-}
+// (reload_args — the kernel arguments once more, behind an opaque pointer — is in ps_common.hpp: commnet_fwd.hip's window form
+//  re-reads its arguments the same way)
 
 // The arguments of step t of a window (WIN): every per-step pointer moved by t steps, offsets in 64 bits; the masks of a step
 // t >= 1 are what step t - 1 wrote (Trainer._after_launch / _commit_step hand over the same tensors between two per-step calls).
@@ -1530,6 +1520,14 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
                                  ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
         return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), h, c, alive_in, comm_in, out, action, obs, reward,
                                   done, alive, is_completed, stream);
+    }
+    // (likewise the window of ic3_commnet_step's families, played by commnet_fwd.hip's kernel)
+    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_COMMNET_WINDOW) {
+        if (p->struct_size != sizeof(ic3_commnet_window))
+            return fail(-22, "ic3_policy_step (ic3_commnet_window): struct_size is " + std::to_string(p->struct_size) +
+                                 ", this library's ic3_commnet_window has " + std::to_string(sizeof(ic3_commnet_window)) + " bytes");
+        return commnet_step_window(env, reinterpret_cast<const ic3_commnet_window*>(p), h, c, alive_in, comm_in, out, action, obs, reward,
+                                   done, alive, is_completed, stream);
     }
     if (int src = check_policy_struct(p, "ic3_policy_step")) return src;      // before any other field is read
     if (!env || !p || !h || !c) return fail(-22, "ic3_policy_step: null argument");

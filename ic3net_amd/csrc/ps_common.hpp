@@ -8,6 +8,8 @@
 
 #include <cstdint>
 
+#include "ic3_common.hpp"
+
 namespace ic3 {
 
 typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
@@ -99,6 +101,20 @@ __device__ __forceinline__ void ps_split_frag(ps_f32x4 x0, ps_f32x4 x1, ps_u32x4
     ps_split_pair(ps_f32x2{ x1[2], x1[3] }, p[0][3], p[1][3], p[2][3]);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) out[pl] = ps_u32x4{ p[pl][0], p[pl][1], p[pl][2], p[pl][3] };
+}
+
+// the kernel arguments once more, by scalar loads from the kernarg segment behind an opaque pointer (the compiler cannot
+// tell that they are the values it already holds, so none of the first copy has to stay alive for the second)
+template <class Args>
+__device__ __forceinline__ void reload_args(Args& a)
+{
+    typedef const __attribute__((address_space(4))) int* KWords;
+    KWords kp = (KWords)__builtin_amdgcn_kernarg_segment_ptr();
+    IC3_OPAQUE_SGPR(kp);
+    static_assert(sizeof(Args) % 4 == 0, "the argument block is a whole number of dwords");
+    int* dst = reinterpret_cast<int*>(&a);
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(Args) / 4); ++i) dst[i] = kp[i];
 }
 
 }  // namespace ic3

@@ -59,6 +59,11 @@ inline void fill_env_args(Args& a, ic3_env* env, float* reward, int32_t* done, i
     }
 }
 
+// ic3_policy_step on an ic3_commnet_window (commnet_fwd.hip): ic3_policy_step's arguments behind the descriptor's tag and size check
+int commnet_step_window(ic3_env* env, const ic3_commnet_window* w, float* h, float* c, const int32_t* alive_in, const int32_t* comm_in,
+                        float* out, int32_t* action, float* obs, float* reward, int32_t* done, int32_t* alive, int32_t* is_completed,
+                        ic3_stream stream);
+
 // f(std::integral_constant<int, H>) for hid_size 64 / 128 / 256 (every caller has refused any other H before it plans a launch).
 // What f instantiates is what gets built: an instantiation that exists for some H only stays outside (policy_step.hip's pass loop).
 template <class F>

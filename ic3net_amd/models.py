@@ -82,6 +82,24 @@ class MLP(nn.Module):
         self._stand_in.done()
         return out
 
+    def commnet_window_supported(self, env):
+        """A recorded training window may be played in ONE launch (CommNetMLP.step_env_commnet_window on the stand-in): models.MLP,
+        and models.RNN with the tanh recurrence at the kernels' own hidden sizes."""
+        from . import ops
+        if type(self) is not MLP and getattr(self.args, 'rnn_type', 'MLP') == 'LSTM':
+            return False
+        if torch.is_grad_enabled() or ops.padded_hidden(self.args.hid_size) is not None:
+            return False
+        n = self._stand_in.get()
+        return n is not None and n.commnet_window_supported(env)
+
+    def step_env_commnet_window(self, env, info, T, *bufs, **kw):
+        n = self._stand_in.get()
+        out = n.step_env_commnet_window(env, info, T, *bufs, **kw)
+        self._stand_in.done()
+        self.window_launches = getattr(self, 'window_launches', 0) + 1
+        return out
+
     def refresh_derived(self):
         """Trainer.begin_episode in front of graph replays (comm.CommNetMLP.refresh_derived): the stand-in's copies of the
         parameters and the caches it has built, in place."""

@@ -943,6 +943,45 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     return out
 
 
+def commnet_step_window_supported(env, cn, H):
+    """ic3_policy_step on an ic3_commnet_window can run this env / hid_size: the split products, hid 64 / 128, a tile that fits."""
+    return H in (64, 128) and cn.get('wp3') is not None and commnet_step_supported(env, H)
+
+
+def commnet_step_window(env, cn, H, head_sizes, mode_avg, comm_zero, T, alive_in, comm_in, out, action, reward, done, alive,
+                        is_completed, hs=None, h_fin=None, snaps=None, alive_prev=False, comm_mode='all'):
+    """T consecutive commnet_step calls of the recorded training rollout in ONE launch — ic3_policy_step on an ic3_commnet_window.
+    `cn`: the module's derived weights, as for commnet_step.  alive_in / comm_in: the masks of step 0; out (T, E*N, OT); action
+    (T, heads, E, N) int32; reward / alive / is_completed (T, E, N); done (T, E).  hs (T+1, E*N, H): the tanh recurrence — step t
+    reads slot t as h_in and writes slot t+1 — or None; h_fin (T, E*N, H) or None: the module's final hidden state of every step;
+    snaps (T, words >= state_words) int32 or None: the env state entering every step.  The masks of step t >= 1 as in
+    policy_step_window.  No dense observation rows.  Same bits as T commnet_step calls.  NotImplementedError where the library
+    answers -ENOSYS (hid 256, no split planes, a tile that does not fit)."""
+    _need_cuda(out, "commnet_step_window")
+    T, H = int(T), int(H)
+    R, nh, OT = out.shape[1], len(head_sizes), sum(int(a) for a in head_sizes) + 1
+    assert T >= 1 and _dense(out, (T, R, OT), torch.float32) and _i32(action, T * nh * R)
+    assert _mask(alive_in, R) and _mask(comm_in, R)
+    assert _f32(reward, T * R) and _i32(alive, T * R, none_ok=True) and _i32(is_completed, T * R, none_ok=True)
+    assert _i32(done, T * env.nenvs)
+    assert _f32(hs, (T + 1, R, H), none_ok=True) and _f32(h_fin, (T, R, H), none_ok=True)
+    assert snaps is None or (snaps.dtype == torch.int32 and snaps.is_contiguous() and snaps.dim() == 2 and snaps.shape[0] == T)
+    assert not alive_prev or alive is not None
+    win = _lib.CommnetWindow()
+    win.inner_pass = win.WINDOW
+    win.H, win.nheads, win.head_sizes = H, nh, int32_array(head_sizes, 4)
+    win.mode_avg, win.comm_zero, win.npasses = int(bool(mode_avg)), int(bool(comm_zero)), int(cn['wp'].shape[0])
+    win.T, win.recurrence = T, int(hs is not None)
+    win.alive_mode = _lib.PolicyWindow.ALIVE_PREV if alive_prev else _lib.PolicyWindow.ALIVE_ALL
+    win.comm_mode = WINDOW_COMM_MODES[comm_mode]
+    _set_ptrs(win, dict(enc_wt=cn['wt'], enc_bias=cn['enc_bias'], head_w=cn['w_heads'], head_b=cn['b_heads'], wp=cn['wp'], bias=cn['bias']),
+              loc_table=cn['loc_table'], wp3=cn.get('wp3'), h_fin=h_fin, snaps=snaps)
+    win.snap_words = int(snaps.shape[1]) if snaps is not None else 0
+    check(_lib.lib().ic3_policy_step(env._h, C.cast(C.byref(win), C.POINTER(_lib.Policy)), ptr(hs), None, ptr(alive_in), ptr(comm_in),
+                                     ptr(out), ptr(action), None, ptr(reward), ptr(done), ptr(alive), ptr(is_completed), stream()))
+    return out
+
+
 def episode_finalize(done, reward, alive=None, is_completed=None, gate=None, gate_ones=False, auto_reset=False,
                      forced_last=False, work=None):
     """The per-step derivations of get_episode (trainer.py:70-105,109-110) for n slots of E envs in one launch —

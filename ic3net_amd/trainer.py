@@ -126,7 +126,9 @@ class Trainer(object):
         (CommNetMLP.step_env_window: ic3_policy_step on an ic3_policy_window) where every step of it would be the same one-launch
         step writing into the episode record: the in-place (h, c) record with its gate / inp rows, no dense observation rows, nothing
         that looks at a single step (store_states, display, the step timer, done_check_every), a lock-step handle (collection
-        windows — args.auto_reset — keep the per-step path) and a policy that answers window_supported.  A window the library
+        windows — args.auto_reset — keep the per-step path) and a policy that answers window_supported.  The families of
+        ic3_commnet_step (the non-recurrent CommNet module, the IC baseline, IRIC with the tanh recurrence) play theirs through
+        step_env_commnet_window under the same exclusions, where the policy answers commnet_window_supported.  A window the library
         refused (-38) is not asked for again."""
         a, rec, raw = self.args, self._rec, getattr(self.env, 'env', None)
         if not getattr(a, 'window_launch', False) or getattr(self, '_window_refused', False) or rec is None or raw is None:
@@ -135,8 +137,16 @@ class Trainer(object):
                 or getattr(a, 'rollout_grad', False) or getattr(self, '_should_display', False) \
                 or getattr(raw, 'step_timer', None) is not None or self._dense_obs():
             return False
-        if not (a.recurrent and a.rnn_type == 'LSTM') or not rec.recurrent or rec.gates is None or rec.xh is None \
-                or rec.xh.shape[2] != 2 * rec.hs.shape[2]:
+        if not (a.recurrent and a.rnn_type == 'LSTM'):
+            # the families of ic3_commnet_step (the non-recurrent CommNet module, the IC baseline, IRIC with the tanh recurrence):
+            # CommNetMLP.step_env_commnet_window — ic3_policy_step on an ic3_commnet_window — where every step would be
+            # _step_body_commnet / _step_body_rnn
+            ok = getattr(self.policy_net, 'commnet_window_supported', None)
+            with torch.no_grad():
+                if ok is None or rec.recurrent != bool(a.recurrent) or not bool(ok(raw)):
+                    return False
+                return self._rnn_expected(raw) if a.recurrent else self._commnet_expected(raw)
+        if not rec.recurrent or rec.gates is None or rec.xh is None or rec.xh.shape[2] != 2 * rec.hs.shape[2]:
             return False
         ok = getattr(self.policy_net, 'window_supported', None)
         with torch.no_grad():                                      # (the grad mode the steps of this rollout run in)
@@ -154,14 +164,25 @@ class Trainer(object):
             info = self._info
             if args.hard_attn and args.commnet:                    # trainer.py:45-46 (quirk Q22)
                 info['comm_action'] = self._zeros_comm
-            self._prev_hid = self._first_hidden(self._state, False)
-            if self._prev_hid[0].data_ptr() != rec.hs[0].data_ptr():
-                return False
+            lstm = args.recurrent and args.rnn_type == 'LSTM'
+            if lstm:
+                self._prev_hid = self._first_hidden(self._state, False)
+                if self._prev_hid[0].data_ptr() != rec.hs[0].data_ptr():
+                    return False
             if rec.out is None:
                 rec.out = torch.empty((T, E * args.nagents, sum(int(o) for o in args.naction_heads) + 1), dtype=torch.float32, device=dev)
             try:
-                outs = net.step_env_window(raw, info, T, rec.hs, rec.cs, rec.out, buf['action'], buf['reward'], buf['done'],
-                                           buf['alive'], buf['is_completed'], rec.gates, rec.xh, rec.snaps)
+                if lstm:
+                    outs = net.step_env_window(raw, info, T, rec.hs, rec.cs, rec.out, buf['action'], buf['reward'], buf['done'],
+                                               buf['alive'], buf['is_completed'], rec.gates, rec.xh, rec.snaps)
+                else:
+                    # ic3_commnet_step's families.  The tanh recurrence runs in the record itself: slot 0 = the zero state the
+                    # episode enters with (the per-step bodies copy theirs into slot t), slot T = what it ends with
+                    if args.recurrent:
+                        rec.hs[0].zero_()
+                    outs = net.step_env_commnet_window(raw, info, T, rec.out, buf['action'], buf['reward'], buf['done'], buf['alive'],
+                                                       buf['is_completed'], rec.snaps, hs=rec.hs if args.recurrent else None,
+                                                       h_fin=rec.h_fin)
             except NotImplementedError:
                 self._window_refused = True
                 return False
@@ -177,8 +198,15 @@ class Trainer(object):
             if args.hard_attn and args.commnet:                    # trainer.py:70-71
                 info['comm_action'] = buf['action'][t][-1] if not args.comm_action_one else self._ones_comm
             self._step_out[t] = (None, outs[t][0], outs[t][1], None)
-        rec.n = rec.gates_n = rec.out_n = T
-        self._prev_hid = rec.slot(T)
+        rec.n = rec.out_n = T
+        if lstm:
+            rec.gates_n = T
+            self._prev_hid = rec.slot(T)
+        else:
+            if rec.h_fin is not None:
+                rec.h_fin_n = T
+            if args.recurrent:                                     # (E, N, H) as step_env_rnn hands it on; end_episode: h_last = slot T
+                self._prev_hid = rec.hs[T].view(E, args.nagents, args.hid_size)
         self._state = self.env._flatten_obs(raw._obs) if hasattr(self.env, '_flatten_obs') else raw._obs
         self._info = info
         self._nsteps = T

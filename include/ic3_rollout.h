@@ -863,6 +863,49 @@ typedef struct ic3_policy_window {
     int32_t* snaps;
     int64_t snap_words;
 } ic3_policy_window;
+/* ic3_policy header followed by the operands of a WINDOW of T steps of ic3_commnet_step — the non-recurrent CommNet module, the IC
+ * baseline's stand-in and the tanh recurrence: handed to ic3_policy_step in place of an ic3_policy, with policy.inner_pass =
+ * IC3_COMMNET_WINDOW — the tag that selects this form — AND policy.struct_size = sizeof(ic3_commnet_window): a tagged descriptor of
+ * any other size is refused with -EINVAL before anything else is read or launched, and every other entry point refuses this struct
+ * by its size (the rule of ic3_policy_window; ic3_commnet_step takes positional arguments and cannot carry a descriptor, and ABI 601
+ * gains no symbol).  ONE launch plays T consecutive ic3_commnet_step calls: a workgroup walks its tile of whole envs through
+ * t = 0 .. T-1, writes every per-step output at its step offset and stores its envs' share of the env snapshot in front of every
+ * step.  Everything the launch writes — and the state it leaves in the handle — is the SAME BITS as T ic3_commnet_step calls on a
+ * twin handle that runs ic3_env_snapshot in front of every step and is handed the masks of step t-1.
+ * Of the header the call reads H, nheads, head_sizes, mode_avg, comm_zero, enc_wt, enc_bias, loc_table, head_w, head_b and npasses
+ * (= comm_passes >= 1); c_wp, lstm_wp, lstm_bias, lstm_wp3 and pass_index must be NULL / 0 (-EINVAL).  Behind the header:
+ *   T, alive_mode, comm_mode   IC3_WINDOW_ALIVE_*, IC3_WINDOW_COMM_*: as in ic3_policy_window
+ *   recurrence    0, or 1: the tanh recurrence of ic3_commnet_step's h_in (one pass, comm_zero)
+ *   wp, wp3, bias what ic3_commnet_step takes
+ *   h_fin [T][E*N][H] or NULL   the module's final hidden state of every step (ic3_commnet_step's h_out with h_in == NULL)
+ *   snaps, snap_words           as in ic3_policy_window
+ * Meaning of the call's arguments in this form:
+ *   h             recurrence = 1: base of [T+1][E*N][H], step t reads slot t and writes slot t+1; otherwise NULL
+ *   c             NULL
+ *   alive_in, comm_in   the masks of step 0 only
+ *   out [T][E*N][OT];  action [T][nheads][E*N];  reward, alive, is_completed [T][E][N];  done [T][E]
+ *   obs           must be NULL: anything else is -EINVAL
+ * Lock-step and auto-reset handles: an env with t == 0 inside the window starts an episode (nobody dead, gate 0, its h rows read as
+ * zero), as in the per-step kernel.  Needs hid_size 64 / 128, wp3 (the split products) and an env tile that fits: -ENOSYS before any
+ * launch otherwise (use one call per step).  A call that finds ic3_env_set_hidden_out, ic3_env_set_record_out or
+ * ic3_env_set_step_events armed on the handle disarms them and is refused with -EINVAL.  Error messages begin
+ * "ic3_policy_step (ic3_commnet_window)".
+ * (As for IC3_POLICY_WINDOW: a plain ic3_policy whose inner_pass carries the value IC3_COMMNET_WINDOW is refused with -EINVAL in
+ * ic3_policy_step as a window descriptor of the wrong size.  Pass 1 for an inner pass.) */
+#define IC3_COMMNET_WINDOW 4
+typedef struct ic3_commnet_window {
+    ic3_policy policy;
+    int32_t T;
+    int32_t alive_mode;
+    int32_t comm_mode;
+    int32_t recurrence;
+    const float* wp;
+    const void* wp3;
+    const float* bias;
+    float* h_fin;
+    int32_t* snaps;
+    int64_t snap_words;
+} ic3_commnet_window;
 
 /* The NON-recurrent CommNet module after the encoder (comm.py:127-129,179-205,220-224,228-239), every communication pass
  * in ONE launch:  x = tanh(enc);  h_0 = x;  h_{i+1} = tanh(x + f_modules[i](h_i) + C_modules[i](comm(h_i)));

@@ -6,7 +6,8 @@ COMM_PASSES=<P> (with SHARE_WEIGHTS=1: one C for every pass) overrides the workl
 the update of such a policy through the per-step loop instead of bptt._backward_window_multipass (the line then says which ran);
 MULTIPASS_COLLECTION=1 sends its collection-mode windows (argument 7 = 1) through the window path too (args.multipass_window_collection,
 off by default).  WINDOW_LAUNCH=1 sets args.window_launch: the recorded rollout of an update as one launch per window (the line says how
-many windows went through it)."""
+many windows went through it: the LSTM policies' ic3_policy_window, and the ic3_commnet_window of tj_medium_commnet_mlp, pp_hard_ic and
+pp_hard_iric_tanh)."""
 import os
 import sys
 import time
