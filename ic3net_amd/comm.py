@@ -759,10 +759,13 @@ class CommNetMLP(nn.Module):
 
     def window_supported(self, env):
         """step_env_window() may play a recorded training window on this env: the one-launch step at this hidden size itself (a
-        zero-padded twin answers no), one communication pass, the split gate product, hid 64 / 128."""
-        if torch.is_grad_enabled() or self._twin() is not None or self.comm_passes != 1 or not self.mega_supported(env):
+        zero-padded twin answers no), the split gate product, hid 64 / 128; one communication pass, or 2..4 where every step would be
+        the in-launch pass loop (step_env: ops.policy_step_passes_supported and args.passes_in_launch; share_weights or not)."""
+        if torch.is_grad_enabled() or self._twin() is not None or not self.mega_supported(env):
             return False
-        return ops.policy_step_window_supported(env, self._fused_cache(), self.hid_size)
+        if self.comm_passes != 1 and not (self._multi_pass_ok() and getattr(self.args, 'passes_in_launch', True)):
+            return False
+        return ops.policy_step_window_supported(env, self._fused_cache(), self.hid_size, passes=self.comm_passes)
 
     def step_env_window(self, env, info, T, hs, cs, out, action, reward, done, alive, is_completed, gates, inp, snaps):
         """T consecutive step_env() calls of the recorded training rollout in ONE launch (ic3_policy_step on an ic3_policy_window):
@@ -771,16 +774,19 @@ class CommNetMLP(nn.Module):
         env state entering every step; `info`: step 0's.  The masks of a step t >= 1 are what the Trainer hands over between two
         step_env() calls: Traffic-Junction's alive slice of step t-1, the last head's draws (args.hard_attn) or ones
         (args.comm_action_one).  No dense observation rows.  Returns [(action_out, value)] per step, views of `out`.  -38 from the
-        library surfaces as NotImplementedError before anything was launched."""
+        library surfaces as NotImplementedError before anything was launched.  comm_passes 2..4: every step runs its passes inside
+        the launch (the inner passes hand c on through slot t+1); gates and inp are None — that rollout keeps no gate record."""
         n, H, a = self.nagents, self.hid_size, self.args
-        assert self._twin() is None and self.comm_passes == 1, "window_supported() answers first"
+        assert self._twin() is None and 1 <= self.comm_passes <= 4, "window_supported() answers first"
+        assert self.comm_passes == 1 or (gates is None and inp is None)
         batch = reward.shape[1]
         fc = self._fused_cache()
         alive_in, comm_in, mode_avg, mz = self._call_inputs(info, batch, hs.device)
         heads = [int(o) for o in a.naction_heads]
         comm_mode = 'all' if not a.hard_attn else 'ones' if getattr(a, 'comm_action_one', False) else 'last_head'
         ops.policy_step_window(env, fc, H, heads, mode_avg, mz, T, hs, cs, alive_in, comm_in, out, action, reward, done, alive,
-                               is_completed, gates=gates, inp=inp, snaps=snaps, alive_prev=env.dims.kind == 2, comm_mode=comm_mode)
+                               is_completed, gates=gates, inp=inp, snaps=snaps, alive_prev=env.dims.kind == 2, comm_mode=comm_mode,
+                               passes=self.comm_passes)
         self.window_launches = getattr(self, 'window_launches', 0) + 1
         return [self._split_out(out[t], batch, n) for t in range(T)]
 

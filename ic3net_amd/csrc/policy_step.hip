@@ -198,12 +198,17 @@ __device__ __forceinline__ void window_step_args(StepArgs& a, int t)
 // state, slot t + 1 of (h, c), the alive slice, the last head's draws) was written by OTHER lanes and waves of this workgroup, so
 // behind the step's stores come the drain of every wave's stores, the workgroup barrier and an agent-scope acquire (the vector L1
 // is invalidated; see the hand-off itself for the pairing and what the full agent-scope release cost).  WIN = 0 compiles to what it was.
+// MP = 1, WIN = 1 (ic3_policy_step on an ic3_policy_window tagged IC3_POLICY_WINDOW_PASSES): T steps of npass passes each in the one
+// loop.  What MP keys on the pass keeps doing so (first / last, the pass's C weights and bias, the inner passes' early end); what WIN
+// keys on the step (window_step_args, the snapshot, the hand-off, the exit) keys on `wstep`.  Pass 0 of step t reads slot t of (h, c);
+// the inner passes hand c' on through slot t + 1 (the window's c_out), the last pass stores h', c' there: slot t is never written.
+// No gate / inp record (the MP launch has none).
 template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0, int WIN = 0>
 __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(const StepArgs a_in)
 {
     static_assert(!MP || (SPLIT && KIND != 0), "the in-launch pass loop exists for the split gate product on an env handle");
     static_assert(!REC || (SPLIT && KIND == 0 && !MP), "the recording pass exists for the split gate product on a caller's encoder output");
-    static_assert(!WIN || (SPLIT && KIND != 0 && !MP && !REC && H <= 128), "the window form exists for the one-pass split gate product on an env handle");
+    static_assert(!WIN || (SPLIT && KIND != 0 && !REC && H <= 128), "the window form exists for the split gate product on an env handle");
     constexpr int K = 2 * H, LDA = K + 4, LDA4 = LDA / 4, BM = 64, NT = 2 * H, NW = H / 32, H4 = H / 4;
     IC3_DYNAMIC_LDS(float, smem);
     float* const As = smem;                                      // [BM][LDA]: cols [0,H) enc / comm / inp, [H,2H) h / h'
@@ -233,14 +238,20 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
         zso += NW * 1024;
     };
 
-    for (int pass = 0;; ++pass) {   // (one iteration unless MP; WIN: the step of the window)
+    // (one iteration unless MP or WIN.  MP: the communication pass of the step; WIN: the step of the window; MP and WIN: the pass, with
+    //  the step in `wstep` — the hand-off to the next step starts the passes again.  The step of the window is spelled out as
+    //  `(MP && WIN) ? wstep : pass` where it is used: a named copy of it in front of the body changed the register allocation of the
+    //  MP instantiations, which must stay what they were)
+    int wstep = 0;
+    (void)wstep;
+    for (int pass = 0;; ++pass) {
     // =====================================================================================================================
     // FRONT: masks, descriptors, encoder, comm, C product, gate GEMM
     // =====================================================================================================================
     {
         StepArgs a_re;                                               // MP: the arguments again for every pass (kernarg segment),
         if constexpr (MP != 0 || WIN != 0) reload_args(a_re);        // nothing of them lives across a pass
-        if constexpr (WIN != 0) window_step_args<H>(a_re, pass);
+        if constexpr (WIN != 0) window_step_args<H>(a_re, (MP && WIN) ? wstep : pass);
         const StepArgs& a = (MP || WIN) ? a_re : a_in;
         int tid_v = threadIdx.x;
         if constexpr (MP != 0 || WIN != 0) IC3_OPAQUE_VGPR(tid_v);               // (per pass: nothing derived from it is hoisted out of the pass loop)
@@ -807,7 +818,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
     {
         StepArgs a;
         reload_args(a);
-        if constexpr (WIN != 0) window_step_args<H>(a, pass);
+        if constexpr (WIN != 0) window_step_args<H>(a, (MP && WIN) ? wstep : pass);
         int tid = threadIdx.x;
         IC3_OPAQUE_VGPR(tid);
         const bool first = !MP || pass == 0, last = !MP || pass + 1 == a.npass;
@@ -938,7 +949,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
         if constexpr (WIN != 0) {
             if (a.win_snaps) {   // (uniform)
                 const int32_t* __restrict__ const st = a.win_state;
-                int32_t* __restrict__ const sn = a.win_snaps + (long long)pass * a.win_snap_words;
+                int32_t* __restrict__ const sn = a.win_snaps + (long long)((MP && WIN) ? wstep : pass) * a.win_snap_words;
                 int32_t sv[16];
 #pragma unroll
                 for (int f = 0; f < 16; ++f) {
@@ -1103,7 +1114,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
             }
         }
         if constexpr (WIN != 0) {
-            if (pass + 1 < a.win_T) {   // (uniform) the hand-off to the next step, see above
+            if (((MP && WIN) ? wstep : pass) + 1 < a.win_T) {   // (uniform) the hand-off to the next step, see above
                 // Producer and consumer are waves of ONE workgroup: one CU, one XCD, one L2.  Every wave waits for its own stores
                 // (`s_waitcnt vmcnt(0)`: the write-through stores have been acknowledged by the L2; a barrier alone does not drain
                 // them), the barrier, and every wave invalidates the CU's vector L1 (agent-scope acquire: `s_waitcnt vmcnt(0);
@@ -1113,6 +1124,10 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                 IC3_WAIT_VMEM();
                 __syncthreads();
                 IC3_ACQUIRE_AGENT();
+                if constexpr (MP != 0) {   // the next step starts at its pass 0
+                    pass = -1;
+                    wstep += 1;
+                }
                 continue;
             }
         }
@@ -1438,11 +1453,13 @@ extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, 
 }
 
 // ic3_policy_step on an ic3_policy_window: T lock-steps of the recorded training rollout in one launch (the WIN instantiations).
-static int policy_step_window(ic3_env* env, const ic3_policy_window* w, float* h, float* c, const int32_t* alive_in,
+// `passes`: the descriptor is tagged IC3_POLICY_WINDOW_PASSES — npasses = 2..4 communication passes per step (the MP + WIN
+// instantiations), no gate / inp record.
+static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool passes, float* h, float* c, const int32_t* alive_in,
                               const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
                               int32_t* alive, int32_t* is_completed, ic3_stream stream)
 {
-    const std::string who = "ic3_policy_step (ic3_policy_window)";
+    const std::string who = passes ? "ic3_policy_step (ic3_policy_window, passes)" : "ic3_policy_step (ic3_policy_window)";
     if (!env) return fail(-22, who + ": null handle");
     // the one-shots of the per-step call have no meaning here (the descriptor names the record): disarmed, and the call refused
     const bool armed = env->h_out || env->c_out || env->gates_out || env->xh_out || env->ev_start || env->ev_stop;
@@ -1459,6 +1476,8 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, float* h
     if (obs) return fail(-22, who + ": obs must be NULL (the window form assembles no dense observation rows)");
     if (w->T < 1 || w->reserved) return fail(-22, who + ": T >= 1, reserved = 0");
     if ((w->gates == nullptr) != (w->inp == nullptr)) return fail(-22, who + ": gates and inp come together");
+    if (passes && (w->gates || w->inp))
+        return fail(-22, who + ": gates and inp must be NULL (the in-launch passes keep no gate record; the update re-evaluates them)");
     if (w->snaps && w->snap_words < env->dims.state_words) return fail(-22, who + ": snap_words >= dims.state_words");
     if (w->alive_mode != IC3_WINDOW_ALIVE_ALL && w->alive_mode != IC3_WINDOW_ALIVE_PREV) return fail(-22, who + ": alive_mode");
     if (w->comm_mode != IC3_WINDOW_COMM_ALL && w->comm_mode != IC3_WINDOW_COMM_LAST_HEAD && w->comm_mode != IC3_WINDOW_COMM_ONES)
@@ -1468,12 +1487,24 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, float* h
     if (!p->enc_wt || !p->enc_bias) return fail(-22, who + ": incomplete ic3_policy (encoder)");
     const int H = p->H;
     const int lds = policy_step_lds(env, H);
-    if (!lds || (H != 64 && H != 128))
-        return fail(-38, who + ": needs hid_size 64 / 128, <= 64 agents per env and an env tile that fits in LDS (use one call per step)");
-    if (!p->gate_split || !p->lstm_wp3) return fail(-38, who + ": needs gate_split with lstm_wp3 (use one call per step)");
-    if (p->npasses >= 2 || p->pass_index) return fail(-38, who + ": one communication pass per step (use one call per step)");
+    auto shape_ok = [&]() {
+        if (!lds || (H != 64 && H != 128))
+            return fail(-38, who + ": needs hid_size 64 / 128, <= 64 agents per env and an env tile that fits in LDS (use one call per step)");
+        if (!p->gate_split || !p->lstm_wp3) return fail(-38, who + ": needs gate_split with lstm_wp3 (use one call per step)");
+        return 0;
+    };
+    if (!passes) {
+        if (int src = shape_ok()) return src;
+        if (p->npasses >= 2 || p->pass_index) return fail(-38, who + ": one communication pass per step (use one call per step)");
+    } else {
+        if (p->npasses < 2 || p->npasses > 4) return fail(-38, who + ": npasses takes 2..4 passes per step (use one call per step)");
+        if (p->pass_index) return fail(-38, who + ": pass_index must be 0 (use one call per pass)");
+    }
     StepArgs a{};
     if (int frc = fill_policy(a, p, who.c_str())) return frc;
+    if (passes) {
+        if (int src = shape_ok()) return src;
+    }
     a.h = a.h_out = h;
     a.c = a.c_out = c;
     a.gates_out = w->gates;
@@ -1502,6 +1533,11 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, float* h
     const bool pp = env->kind == IC3_ENV_PP;
     hipStream_t s = (hipStream_t)stream;
     const int tiles = plan_tiles(a, H, p, s);
+    if (passes) {
+        if (H == 128)
+            return pp ? launch_step<128, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<128, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
+        return pp ? launch_step<64, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<64, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
+    }
     if (H == 128)
         return pp ? launch_step<128, IC3_ENV_PP, 1, 0, 0, 1>(a, tiles, lds, s) : launch_step<128, IC3_ENV_TJ, 1, 0, 0, 1>(a, tiles, lds, s);
     return pp ? launch_step<64, IC3_ENV_PP, 1, 0, 0, 1>(a, tiles, lds, s) : launch_step<64, IC3_ENV_TJ, 1, 0, 0, 1>(a, tiles, lds, s);
@@ -1518,8 +1554,16 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
         if (p->struct_size != sizeof(ic3_policy_window))
             return fail(-22, "ic3_policy_step (ic3_policy_window): struct_size is " + std::to_string(p->struct_size) +
                                  ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
-        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), h, c, alive_in, comm_in, out, action, obs, reward,
-                                  done, alive, is_completed, stream);
+        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), false, h, c, alive_in, comm_in, out, action, obs,
+                                  reward, done, alive, is_completed, stream);
+    }
+    // (the same struct with npasses = 2..4 communication passes per step: a tag of its own, so that IC3_POLICY_WINDOW keeps its answers)
+    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_POLICY_WINDOW_PASSES) {
+        if (p->struct_size != sizeof(ic3_policy_window))
+            return fail(-22, "ic3_policy_step (ic3_policy_window, passes): struct_size is " + std::to_string(p->struct_size) +
+                                 ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
+        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), true, h, c, alive_in, comm_in, out, action, obs,
+                                  reward, done, alive, is_completed, stream);
     }
     // (likewise the window of ic3_commnet_step's families, played by commnet_fwd.hip's kernel)
     if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_COMMNET_WINDOW) {

@@ -63,9 +63,9 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  # 1: ... in collection mode (--auto_reset) too; 0 (default): collection-mode windows of such a policy keep the loop
                  ('multipass_window_collection', int, 0),
                  # the recorded rollout of a native update as ONE launch per window of max_steps lock-steps (Trainer._play_window:
-                 # ic3_policy_step on an ic3_policy_window for the LSTM policies, on an ic3_commnet_window for the non-recurrent
-                 # CommNet module, the IC baseline and IRIC with the tanh recurrence) where the policy supports it; off: one
-                 # launch per step
+                 # ic3_policy_step on an ic3_policy_window for the LSTM policies — comm_passes 2..4 included, their passes inside
+                 # the launch and no gate record —, on an ic3_commnet_window for the non-recurrent CommNet module, the IC baseline
+                 # and IRIC with the tanh recurrence) where the policy supports it; off, and comm_passes > 4: one launch per step
                  ('window_launch', 'flag', False)]
 
 

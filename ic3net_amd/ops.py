@@ -904,19 +904,24 @@ def policy_step(env, fc, H, head_sizes, mode_avg, comm_zero, h, c, alive_in, com
 WINDOW_COMM_MODES = dict(all=_lib.PolicyWindow.COMM_ALL, last_head=_lib.PolicyWindow.COMM_LAST_HEAD, ones=_lib.PolicyWindow.COMM_ONES)
 
 
-def policy_step_window_supported(env, fc, H):
-    """ic3_policy_step on an ic3_policy_window can run this env / hid_size: the split gate product, hid 64 / 128, a tile that fits."""
+def policy_step_window_supported(env, fc, H, passes=1):
+    """ic3_policy_step on an ic3_policy_window can run this env / hid_size: the split gate product, hid 64 / 128, a tile that fits;
+    passes 2..4: the form tagged WINDOW_PASSES, where the per-step call would be the in-launch pass loop."""
+    if passes != 1 and not policy_step_passes_supported(fc, H, passes):
+        return False
     return H in (64, 128) and fc.get('ps_l_wp3') is not None and policy_step_supported(env, H)
 
 
 def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, alive_in, comm_in, out, action, reward, done,
-                       alive=None, is_completed=None, gates=None, inp=None, snaps=None, alive_prev=False, comm_mode='all'):
+                       alive=None, is_completed=None, gates=None, inp=None, snaps=None, alive_prev=False, comm_mode='all', passes=1):
     """T consecutive policy_step calls of the recorded training rollout in ONE launch — ic3_policy_step on an ic3_policy_window.
     hs, cs (T+1, E*N, H): step t reads slot t and writes slot t+1; alive_in / comm_in: the masks of step 0; out (T, E*N, OT); action
     (T, heads, E, N) int32; reward / alive / is_completed (T, E, N); done (T, E); gates (T, E*N, 4H) with inp (T, E*N, 2H) or both
     None; snaps (T, words >= state_words) int32 or None: the env state entering every step.  The masks of step t >= 1: alive_prev —
     the alive slice of step t-1 (Traffic-Junction), else everyone; comm_mode 'all' | 'last_head' (the last head's draws of step t-1)
-    | 'ones'.  No dense observation rows.  Same bits as T policy_step calls on the same handle."""
+    | 'ones'.  No dense observation rows.  Same bits as T policy_step calls on the same handle.  passes >= 2: every step runs that
+    many communication passes inside the launch (the descriptor tagged WINDOW_PASSES, the passes' weights from `fc` as policy_step
+    takes them); no gate record then.  NotImplementedError where the library answers -ENOSYS."""
     _need_cuda(hs, "policy_step_window")
     T = int(T)
     R, nh, OT = hs.shape[1], len(head_sizes), sum(head_sizes) + 1
@@ -928,10 +933,12 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     assert (gates is None) == (inp is None) and (gates is None or (_dense(gates, (T, R, 4 * H)) and _dense(inp, (T, R, 2 * H))))
     assert snaps is None or (snaps.dtype == torch.int32 and snaps.is_contiguous() and snaps.dim() == 2 and snaps.shape[0] == T)
     assert not alive_prev or alive is not None
-    pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero)
+    passes = int(passes)
+    assert passes == 1 or gates is None, "the in-launch passes keep no gate record"
+    pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, passes=passes)
     win = _lib.PolicyWindow()
     C.memmove(C.addressof(win), C.addressof(pol), C.sizeof(pol))
-    win.struct_size, win.inner_pass = C.sizeof(win), win.WINDOW
+    win.struct_size, win.inner_pass = C.sizeof(win), win.WINDOW if passes == 1 else win.WINDOW_PASSES
     win.T = T
     win.alive_mode = win.ALIVE_PREV if alive_prev else win.ALIVE_ALL
     win.comm_mode = WINDOW_COMM_MODES[comm_mode]

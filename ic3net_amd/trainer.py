@@ -128,8 +128,10 @@ class Trainer(object):
         that looks at a single step (store_states, display, the step timer, done_check_every), a lock-step handle (collection
         windows — args.auto_reset — keep the per-step path) and a policy that answers window_supported.  The families of
         ic3_commnet_step (the non-recurrent CommNet module, the IC baseline, IRIC with the tanh recurrence) play theirs through
-        step_env_commnet_window under the same exclusions, where the policy answers commnet_window_supported.  A window the library
-        refused (-38) is not asked for again."""
+        step_env_commnet_window under the same exclusions, where the policy answers commnet_window_supported.  Recurrent CommNet /
+        IC3Net with comm_passes 2..4 — whose steps would be the in-launch pass loop, copying (h, c) into the record — play theirs in
+        the record too, without a gate record (the multipass update re-evaluates the passes itself).  A window the library refused
+        (-38) is not asked for again."""
         a, rec, raw = self.args, self._rec, getattr(self.env, 'env', None)
         if not getattr(a, 'window_launch', False) or getattr(self, '_window_refused', False) or rec is None or raw is None:
             return False
@@ -146,11 +148,22 @@ class Trainer(object):
                 if ok is None or rec.recurrent != bool(a.recurrent) or not bool(ok(raw)):
                     return False
                 return self._rnn_expected(raw) if a.recurrent else self._commnet_expected(raw)
+        ok = getattr(self.policy_net, 'window_supported', None)
+        if self._window_passes() > 1:
+            # comm_passes > 1: no gate record, and a record the per-step rollout copies into (_rec_inplace answers no) — the window
+            # runs in it where every step would be ic3_policy_step at the record's own width
+            ok_rec = getattr(self.policy_net, 'record_inplace_ok', None)
+            with torch.no_grad():
+                return rec.recurrent and rec.gates is None and ok is not None and self._mega_expected(raw) \
+                    and (ok_rec is None or ok_rec()) and rec.hs.shape[2] == a.hid_size and bool(ok(raw))
         if not rec.recurrent or rec.gates is None or rec.xh is None or rec.xh.shape[2] != 2 * rec.hs.shape[2]:
             return False
-        ok = getattr(self.policy_net, 'window_supported', None)
         with torch.no_grad():                                      # (the grad mode the steps of this rollout run in)
             return ok is not None and self._rec_inplace() and bool(ok(raw))
+
+    def _window_passes(self):
+        """Communication passes per step of the policy a window would play (1 where it has no such loop)."""
+        return int(getattr(self.policy_net, 'comm_passes', 1))
 
     def _play_window(self):
         """The max_steps step bodies of get_episode as one launch, and what they leave behind: the record's counters and mask views,
@@ -165,7 +178,11 @@ class Trainer(object):
             if args.hard_attn and args.commnet:                    # trainer.py:45-46 (quirk Q22)
                 info['comm_action'] = self._zeros_comm
             lstm = args.recurrent and args.rnn_type == 'LSTM'
-            if lstm:
+            multipass = lstm and self._window_passes() > 1
+            if multipass:
+                # slot 0 = the zero state the episode enters with (the per-step bodies of this family copy theirs into slot t)
+                self._prev_hid = rec.start()
+            elif lstm:
                 self._prev_hid = self._first_hidden(self._state, False)
                 if self._prev_hid[0].data_ptr() != rec.hs[0].data_ptr():
                     return False
@@ -174,7 +191,8 @@ class Trainer(object):
             try:
                 if lstm:
                     outs = net.step_env_window(raw, info, T, rec.hs, rec.cs, rec.out, buf['action'], buf['reward'], buf['done'],
-                                               buf['alive'], buf['is_completed'], rec.gates, rec.xh, rec.snaps)
+                                               buf['alive'], buf['is_completed'], None if multipass else rec.gates,
+                                               None if multipass else rec.xh, rec.snaps)
                 else:
                     # ic3_commnet_step's families.  The tanh recurrence runs in the record itself: slot 0 = the zero state the
                     # episode enters with (the per-step bodies copy theirs into slot t), slot T = what it ends with
@@ -199,7 +217,11 @@ class Trainer(object):
                 info['comm_action'] = buf['action'][t][-1] if not args.comm_action_one else self._ones_comm
             self._step_out[t] = (None, outs[t][0], outs[t][1], None)
         rec.n = rec.out_n = T
-        if lstm:
+        if multipass:
+            # what T step bodies of this family leave: the final state in tensors of its own (finish() then keeps h_last beside
+            # the record, and the heads' gradient takes the same two passes over the rows as behind a per-step rollout)
+            self._prev_hid = tuple(x.clone() for x in rec.slot(T))
+        elif lstm:
             rec.gates_n = T
             self._prev_hid = rec.slot(T)
         else:

@@ -863,6 +863,25 @@ typedef struct ic3_policy_window {
     int32_t* snaps;
     int64_t snap_words;
 } ic3_policy_window;
+/* The same struct for a policy with comm_passes = 2..4 — recurrent CommNet / IC3Net whose per-step call is the npasses launch:
+ * policy.inner_pass = IC3_POLICY_WINDOW_PASSES AND policy.struct_size = sizeof(ic3_policy_window) (a tag of its own, so that
+ * IC3_POLICY_WINDOW keeps every answer it gives, -ENOSYS for npasses >= 2 among them; no new symbol, no new struct).  ONE launch
+ * plays T consecutive ic3_policy_step calls that each run policy.npasses communication passes: per step, pass 0 builds the masks and
+ * descriptors from the state entering the step and reads (h, c) from slot t; the inner passes keep h' on chip and hand c' on through
+ * slot t + 1; the last pass stores h', c' to slot t + 1, draws, stores the step's share of the snapshot and steps the env.  Slot t is
+ * never written.  An auto-reset env with t == 0 starts from zero state at pass 0 only.  The call's arguments and T, alive_mode,
+ * comm_mode, snaps, snap_words mean what they mean for IC3_POLICY_WINDOW; gates and inp must be NULL (the npasses launch keeps no
+ * gate record).  Everything the launch writes, and the state it leaves in the handle, is the SAME BITS as T per-step calls with the
+ * same npasses on a twin handle that runs ic3_env_snapshot in front of every step, arms ic3_env_set_hidden_out to slot t + 1 and is
+ * handed the masks of step t - 1.
+ * Checked in this order, all before any launch: a tagged descriptor of any other size: -EINVAL (a plain ic3_policy whose inner_pass
+ * carries the value 5 is refused the same way, as a window descriptor of the wrong size — the rule of tags 3 and 4; pass 1 for an
+ * inner pass); every other entry point refuses the struct by its size; ic3_env_set_hidden_out, ic3_env_set_record_out or
+ * ic3_env_set_step_events armed on the handle: disarmed, -EINVAL; obs != NULL, reserved != 0, a bad alive_mode / comm_mode, gates
+ * or inp non-NULL: -EINVAL; npasses outside 2..4: -ENOSYS; pass_index != 0: -ENOSYS; a missing c_wp_pass[i] / enc_bias_pass[i]:
+ * -EINVAL; no gate_split / lstm_wp3, hid_size other than 64 / 128, an env tile or a state field that does not fit: -ENOSYS.
+ * Error messages begin "ic3_policy_step (ic3_policy_window, passes)". */
+#define IC3_POLICY_WINDOW_PASSES 5
 /* ic3_policy header followed by the operands of a WINDOW of T steps of ic3_commnet_step — the non-recurrent CommNet module, the IC
  * baseline's stand-in and the tanh recurrence: handed to ic3_policy_step in place of an ic3_policy, with policy.inner_pass =
  * IC3_COMMNET_WINDOW — the tag that selects this form — AND policy.struct_size = sizeof(ic3_commnet_window): a tagged descriptor of
