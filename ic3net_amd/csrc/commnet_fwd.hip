@@ -174,6 +174,8 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void comm
             if (a.auto_reset && in && a.tstep[e0 + div_small(tid, invN)] == 0) {   // the env starts an episode at this step
                 al = 1;
                 cm = a.comm_in ? 0 : 1;                          // (a gated policy: gate 0; CommNet without a gate head talks)
+                // WIN: a step t >= 1 of IC3_WINDOW_COMM_ONES stands for a per-step call that is handed a gate of ones — gated too
+                if constexpr (WIN != 0) cm = (step > 0 && a.win_comm == IC3_WINDOW_COMM_ONES) ? 0 : cm;
             }
         }
         sm[tid] = in ? (float)(al * cm) : 0.f;

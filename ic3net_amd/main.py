@@ -66,7 +66,11 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  # ic3_policy_step on an ic3_policy_window for the LSTM policies — comm_passes 2..4 included, their passes inside
                  # the launch and no gate record —, on an ic3_commnet_window for the non-recurrent CommNet module, the IC baseline
                  # and IRIC with the tanh recurrence) where the policy supports it; off, and comm_passes > 4: one launch per step
-                 ('window_launch', 'flag', False)]
+                 ('window_launch', 'flag', False),
+                 # 1: ... in collection mode (--auto_reset) too — the window that starts the E streams and every window that
+                 # continues them (step 0 handed the previous window's masks and state; restarts happen inside the launch); acts
+                 # only together with --window_launch and --auto_reset.  0 (default): collection windows keep one launch per step
+                 ('window_launch_collection', int, 0)]
 
 
 def build_parser(argv):

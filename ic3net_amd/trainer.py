@@ -126,7 +126,8 @@ class Trainer(object):
         (CommNetMLP.step_env_window: ic3_policy_step on an ic3_policy_window) where every step of it would be the same one-launch
         step writing into the episode record: the in-place (h, c) record with its gate / inp rows, no dense observation rows, nothing
         that looks at a single step (store_states, display, the step timer, done_check_every), a lock-step handle (collection
-        windows — args.auto_reset — keep the per-step path) and a policy that answers window_supported.  The families of
+        windows — args.auto_reset, _run_batch_streams — keep the per-step path unless args.window_launch_collection is set too) and
+        a policy that answers window_supported.  The families of
         ic3_commnet_step (the non-recurrent CommNet module, the IC baseline, IRIC with the tanh recurrence) play theirs through
         step_env_commnet_window under the same exclusions, where the policy answers commnet_window_supported.  Recurrent CommNet /
         IC3Net with comm_passes 2..4 — whose steps would be the in-launch pass loop, copying (h, c) into the record — play theirs in
@@ -135,8 +136,11 @@ class Trainer(object):
         a, rec, raw = self.args, self._rec, getattr(self.env, 'env', None)
         if not getattr(a, 'window_launch', False) or getattr(self, '_window_refused', False) or rec is None or raw is None:
             return False
-        if check_every or self._auto_reset() or getattr(raw, 'auto_max_steps', 0) or getattr(a, 'store_states', False) \
-                or getattr(a, 'rollout_grad', False) or getattr(self, '_should_display', False) \
+        # a collection window (args.auto_reset: the streams' restarts happen inside the launch, step 0 continues what the previous
+        # window left) only behind args.window_launch_collection
+        if (self._auto_reset() or getattr(raw, 'auto_max_steps', 0)) and not int(getattr(a, 'window_launch_collection', 0)):
+            return False
+        if check_every or getattr(a, 'store_states', False) or getattr(a, 'rollout_grad', False) or getattr(self, '_should_display', False) \
                 or getattr(raw, 'step_timer', None) is not None or self._dense_obs():
             return False
         if not (a.recurrent and a.rnn_type == 'LSTM'):
@@ -166,24 +170,30 @@ class Trainer(object):
         return int(getattr(self.policy_net, 'comm_passes', 1))
 
     def _play_window(self):
-        """The max_steps step bodies of get_episode as one launch, and what they leave behind: the record's counters and mask views,
+        """The max_steps step bodies of get_episode — or of a collection window of _run_batch_streams, the one that starts the
+        streams and every one that continues them — as one launch, and what they leave behind: the record's counters and mask views,
         the per-step outputs, the state the window ends with.  False (nothing played, nothing changed that step 0 would not set
         again) when the library refuses the window."""
         args, net, rec, buf = self.args, self.policy_net, self._rec, self._buf
         raw = self.env.env
         T = args.max_steps
         E, dev = self._state.shape[0], self._state.device
+        # collection mode (args.window_launch_collection): a window that continues E running streams — step 0 is handed the masks
+        # the previous window left (self._info, no zero gate) and the state it ended with; an env whose t == 0 starts an episode
+        # at any step of the window, step 0 included: the launch itself gives it the zero state, no masks and gate 0
+        cont = self._stream_continues()
         with torch.no_grad():
             info = self._info
-            if args.hard_attn and args.commnet:                    # trainer.py:45-46 (quirk Q22)
+            if args.hard_attn and args.commnet and not cont:       # trainer.py:45-46 (quirk Q22)
                 info['comm_action'] = self._zeros_comm
             lstm = args.recurrent and args.rnn_type == 'LSTM'
             multipass = lstm and self._window_passes() > 1
             if multipass:
-                # slot 0 = the zero state the episode enters with (the per-step bodies of this family copy theirs into slot t)
-                self._prev_hid = rec.start()
+                # slot 0 = the zero state the episode enters with, or what the previous window ended with (the per-step bodies of
+                # this family copy theirs into slot t)
+                self._prev_hid = rec.start_from(*self._prev_hid) if cont else rec.start()
             elif lstm:
-                self._prev_hid = self._first_hidden(self._state, False)
+                self._prev_hid = self._first_hidden(self._state, cont)
                 if self._prev_hid[0].data_ptr() != rec.hs[0].data_ptr():
                     return False
             if rec.out is None:
@@ -195,8 +205,11 @@ class Trainer(object):
                                                None if multipass else rec.xh, rec.snaps)
                 else:
                     # ic3_commnet_step's families.  The tanh recurrence runs in the record itself: slot 0 = the zero state the
-                    # episode enters with (the per-step bodies copy theirs into slot t), slot T = what it ends with
-                    if args.recurrent:
+                    # episode enters with, or the h the previous window ended with (the per-step bodies copy theirs into slot t),
+                    # slot T = what it ends with
+                    if args.recurrent and cont:
+                        rec.hs[0].copy_(self._prev_hid.detach().reshape(rec.hs.shape[1:]))
+                    elif args.recurrent:
                         rec.hs[0].zero_()
                     outs = net.step_env_commnet_window(raw, info, T, rec.out, buf['action'], buf['reward'], buf['done'], buf['alive'],
                                                        buf['is_completed'], rec.snaps, hs=rec.hs if args.recurrent else None,
@@ -959,14 +972,17 @@ class Trainer(object):
         E, T, N = self.env.nenvs, args.max_steps, args.nagents
         self.stats = dict()
         wins, slots = [], 0
+        check_every = int(getattr(args, 'done_check_every', 0))
         try:
             while slots < args.batch_size:
                 if args.batch_size - slots <= T * E:
                     self.last_step = True
                 self._stream = dict(cont=bool(wins))
                 self.begin_episode(epoch)
-                for t in range(T):
-                    self.step_episode(t)
+                # the T step launches as ONE launch (args.window_launch with args.window_launch_collection), or one by one
+                if not (self._window_launch_ok(check_every) and self._play_window()):
+                    for t in range(T):
+                        self.step_episode(t)
                 wins.append(self._end_window())
                 slots += T * E
         finally:

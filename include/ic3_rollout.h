@@ -843,6 +843,9 @@ typedef struct ic3_policy_record {
  * that does not fit); Predator-Prey and Traffic-Junction handles, lock-step and auto-reset.  A call that finds ic3_env_set_hidden_out,
  * ic3_env_set_record_out or ic3_env_set_step_events armed on the handle disarms them and is refused with -EINVAL.  Error messages
  * begin "ic3_policy_step (ic3_policy_window)".
+ * A window that CONTINUES running streams of an auto-reset handle — step 0 handed the previous window's last alive slice / last-head
+ * draws and its slot T as slot 0, every env mid-episode there and restarting inside the window — is covered by tests
+ * (tests/test_host_window_continue_cpu.py, tests/test_window_continue_gpu.py: two consecutive windows against 2T per-step calls).
  * (A change for callers of the per-step form: ic3_policy.inner_pass used to mean "inner pass" for ANY non-zero value.  The value
  * IC3_POLICY_WINDOW is now this tag in ic3_policy_step — a plain ic3_policy that carries it is refused with -EINVAL as a window
  * descriptor of the wrong size, as IC3_POLICY_RECORD_PASS already is in ic3_policy_forward.  Pass 1 for an inner pass.) */
@@ -873,7 +876,8 @@ typedef struct ic3_policy_window {
  * comm_mode, snaps, snap_words mean what they mean for IC3_POLICY_WINDOW; gates and inp must be NULL (the npasses launch keeps no
  * gate record).  Everything the launch writes, and the state it leaves in the handle, is the SAME BITS as T per-step calls with the
  * same npasses on a twin handle that runs ic3_env_snapshot in front of every step, arms ic3_env_set_hidden_out to slot t + 1 and is
- * handed the masks of step t - 1.
+ * handed the masks of step t - 1.  A window of this form that continues running streams of an auto-reset handle (slot 0 = the state the
+ * previous window ended with, not the zero state) is covered by the same tests as IC3_POLICY_WINDOW's.
  * Checked in this order, all before any launch: a tagged descriptor of any other size: -EINVAL (a plain ic3_policy whose inner_pass
  * carries the value 5 is refused the same way, as a window descriptor of the wrong size — the rule of tags 3 and 4; pass 1 for an
  * inner pass); every other entry point refuses the struct by its size; ic3_env_set_hidden_out, ic3_env_set_record_out or
@@ -905,7 +909,10 @@ typedef struct ic3_policy_window {
  *   out [T][E*N][OT];  action [T][nheads][E*N];  reward, alive, is_completed [T][E][N];  done [T][E]
  *   obs           must be NULL: anything else is -EINVAL
  * Lock-step and auto-reset handles: an env with t == 0 inside the window starts an episode (nobody dead, gate 0, its h rows read as
- * zero), as in the per-step kernel.  Needs hid_size 64 / 128, wp3 (the split products) and an env tile that fits: -ENOSYS before any
+ * zero), as in the per-step kernel — under IC3_WINDOW_COMM_ONES too: a step t >= 1 stands for a per-step call that is handed a gate
+ * of ones, and an env that starts an episode there gets gate 0 like an env of that call (IC3_WINDOW_COMM_ALL: no gate head, it talks).
+ * A window that continues running streams of an auto-reset handle (step 0 handed the previous window's masks, h slot 0 = the
+ * previous window's slot T; recurrence 0 and 1) is covered by the tests named at ic3_policy_window.  Needs hid_size 64 / 128, wp3 (the split products) and an env tile that fits: -ENOSYS before any
  * launch otherwise (use one call per step).  A call that finds ic3_env_set_hidden_out, ic3_env_set_record_out or
  * ic3_env_set_step_events armed on the handle disarms them and is refused with -EINVAL.  Error messages begin
  * "ic3_policy_step (ic3_commnet_window)".

@@ -7,7 +7,9 @@ the update of such a policy through the per-step loop instead of bptt._backward_
 MULTIPASS_COLLECTION=1 sends its collection-mode windows (argument 7 = 1) through the window path too (args.multipass_window_collection,
 off by default).  WINDOW_LAUNCH=1 sets args.window_launch: the recorded rollout of an update as one launch per window (the line says how
 many windows went through it: the LSTM policies' ic3_policy_window, and the ic3_commnet_window of tj_medium_commnet_mlp, pp_hard_ic and
-pp_hard_iric_tanh)."""
+pp_hard_iric_tanh); WINDOW_LAUNCH_COLLECTION=1 sets args.window_launch_collection beside it: the windows of collection mode (argument 7
+= 1) too.  BATCH_WINDOWS=<k>: an update of k windows of max_steps steps (default 1; in collection mode the first starts the streams and
+the others continue them)."""
 import os
 import sys
 import time
@@ -36,6 +38,7 @@ def main():
     if over and 'MULTIPASS_COLLECTION' in os.environ:
         a.multipass_window_collection = os.environ['MULTIPASS_COLLECTION'] == '1'
     a.window_launch = os.environ.get('WINDOW_LAUNCH', '0') == '1'
+    a.window_launch_collection = int(os.environ.get('WINDOW_LAUNCH_COLLECTION', '0'))
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
@@ -44,7 +47,7 @@ def main():
     a.fused_loss = os.environ.get('FUSED_LOSS', '1') == '1'           # A/B: compute_grad's losses + their gradients as one launch
     a.enc_window = os.environ.get('ENC_WINDOW', '1') == '1'           # A/B: the encoder backward's stage 1 once per window
     a.__dict__.update(gamma=1.0, normalize_rewards=False, entr=0, value_coeff=0.01, advantages_per_action=False,
-                      batch_size=E * a.max_steps)
+                      batch_size=int(os.environ.get('BATCH_WINDOWS', '1')) * E * a.max_steps)
     tune = os.environ.get('TUNE', '1') == '1'
     if tune:                                  # TunableOp picks the GEMM solutions during the first (untimed) update
         import torch.cuda.tunable as tunable
