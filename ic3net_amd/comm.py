@@ -492,14 +492,16 @@ class CommNetMLP(nn.Module):
         action_out, value = self._split_out(out, batch, n)
         return action_out, value.reshape(batch, n, 1)
 
-    def commnet_window_supported(self, env):
+    def commnet_window_supported(self, env, wide=False):
         """step_env_commnet_window() may play a recorded training window on this env: the non-recurrent module's one-launch step at
-        this hidden size itself (a zero-padded twin answers no), no autograd, the split products, hid 64 / 128."""
+        this hidden size itself (a zero-padded twin answers no), no autograd, the split products, hid 64 / 128; wide: hid 256 as
+        well (ops.commnet_step_window's wide form; --window_launch_wide)."""
         a = self.args
         if torch.is_grad_enabled() or self._twin() is not None or a.recurrent or not self._args_ok() \
                 or not getattr(a, 'mega_policy', True) or not self._env_ok(env):
             return False
-        return ops.commnet_step_window_supported(env, self._commnet_cache(), self.hid_size)
+        H = self.hid_size
+        return ops.commnet_step_window_supported(env, self._commnet_cache(), H, wide=bool(wide) and H == 256)
 
     def step_env_commnet_window(self, env, info, T, out, action, reward, done, alive, is_completed, snaps, hs=None, h_fin=None):
         """T consecutive step_env_commnet() calls of the recorded training rollout in ONE launch (ic3_policy_step on an
@@ -517,7 +519,7 @@ class CommNetMLP(nn.Module):
         heads = [int(o) for o in a.naction_heads]
         comm_mode = 'all' if not a.hard_attn else 'ones' if getattr(a, 'comm_action_one', False) else 'last_head'
         ops.commnet_step_window(env, cn, H, heads, mode_avg, mz, T, alive_in, comm_in, out, action, reward, done, alive, is_completed,
-                                hs=hs, h_fin=h_fin, snaps=snaps, alive_prev=env.dims.kind == 2, comm_mode=comm_mode)
+                                hs=hs, h_fin=h_fin, snaps=snaps, alive_prev=env.dims.kind == 2, comm_mode=comm_mode, wide=H == 256)
         self.window_launches = getattr(self, 'window_launches', 0) + 1
         steps = [self._split_out(out[t], batch, n) for t in range(T)]
         return [(action_out, value.reshape(batch, n, 1)) for action_out, value in steps]
@@ -757,20 +759,22 @@ class CommNetMLP(nn.Module):
         self.mega_steps = getattr(self, 'mega_steps', 0) + 1
         return self._split_out(out, batch, n) + ((h, c) if hidden_out is None else tuple(hidden_out),)
 
-    def window_supported(self, env):
+    def window_supported(self, env, wide=False):
         """step_env_window() may play a recorded training window on this env: the one-launch step at this hidden size itself (a
         zero-padded twin answers no), the split gate product, hid 64 / 128; one communication pass, or 2..4 where every step would be
-        the in-launch pass loop (step_env: ops.policy_step_passes_supported and args.passes_in_launch; share_weights or not)."""
+        the in-launch pass loop (step_env: ops.policy_step_passes_supported and args.passes_in_launch; share_weights or not).
+        wide: hid 256 with one pass as well (ops.policy_step_window's wide form; --window_launch_wide)."""
         if torch.is_grad_enabled() or self._twin() is not None or not self.mega_supported(env):
             return False
         if self.comm_passes != 1 and not (self._multi_pass_ok() and getattr(self.args, 'passes_in_launch', True)):
             return False
-        return ops.policy_step_window_supported(env, self._fused_cache(), self.hid_size, passes=self.comm_passes)
+        H = self.hid_size
+        return ops.policy_step_window_supported(env, self._fused_cache(), H, passes=self.comm_passes, wide=bool(wide) and H == 256)
 
     def step_env_window(self, env, info, T, hs, cs, out, action, reward, done, alive, is_completed, gates, inp, snaps):
         """T consecutive step_env() calls of the recorded training rollout in ONE launch (ic3_policy_step on an ic3_policy_window):
         hs / cs (T+1, R, H) the (h, c) record — step t reads slot t, writes slot t+1 —, out (T, R, OT), action (T, heads, E, N),
-        reward / alive / is_completed (T, E, N), done (T, E), gates (T, R, 4H) / inp (T, R, 2H) the gate record, snaps (T, words) the
+        reward / alive / is_completed (T, E, N), done (T, E), gates (T, R, 4H) / inp (T, R, 2H; hid 256: H) the gate record, snaps (T, words) the
         env state entering every step; `info`: step 0's.  The masks of a step t >= 1 are what the Trainer hands over between two
         step_env() calls: Traffic-Junction's alive slice of step t-1, the last head's draws (args.hard_attn) or ones
         (args.comm_action_one).  No dense observation rows.  Returns [(action_out, value)] per step, views of `out`.  -38 from the
@@ -786,7 +790,7 @@ class CommNetMLP(nn.Module):
         comm_mode = 'all' if not a.hard_attn else 'ones' if getattr(a, 'comm_action_one', False) else 'last_head'
         ops.policy_step_window(env, fc, H, heads, mode_avg, mz, T, hs, cs, alive_in, comm_in, out, action, reward, done, alive,
                                is_completed, gates=gates, inp=inp, snaps=snaps, alive_prev=env.dims.kind == 2, comm_mode=comm_mode,
-                               passes=self.comm_passes)
+                               passes=self.comm_passes, wide=H == 256)
         self.window_launches = getattr(self, 'window_launches', 0) + 1
         return [self._split_out(out[t], batch, n) for t in range(T)]
 

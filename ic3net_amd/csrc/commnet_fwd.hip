@@ -126,7 +126,7 @@ template <int H, int KIND = 0, bool NARROW = false, bool RECORD = false, int WIN
 __global__ __launch_bounds__(2 * H, (H <= 128) ? (NARROW ? 3 : 2) : 1) void commnet_forward_kernel(CommnetArgs a)
 {
     static_assert(!RECORD || (KIND == 0 && !NARROW), "the recording instantiation is the plain forward's");
-    static_assert(!WIN || (KIND != 0 && !RECORD && H <= 128), "the window form exists for the env instantiations at hid 64 / 128");
+    static_assert(!WIN || (KIND != 0 && !RECORD), "the window form exists for the env instantiations");
     for (int step = 0;; ++step) {   // (one iteration unless WIN: the step of the window)
     if constexpr (WIN != 0) {                                    // WIN: the arguments again for every step (kernarg segment),
         reload_args(a);                                          // nothing of them lives across a step.  The parameter itself is
@@ -815,13 +815,14 @@ extern "C" int ic3_commnet_step(ic3_env* env, const float* enc_wt, const float* 
 }
 
 // ic3_policy_step on an ic3_commnet_window (dispatched there by the descriptor's tag): T steps of ic3_commnet_step in one launch —
-// the WIN instantiations.  Every refusal comes before the launch.
-int ic3::commnet_step_window(ic3_env* env, const ic3_commnet_window* w, float* h, float* c, const int32_t* alive_in,
+// the WIN instantiations.  `wide`: the descriptor is tagged IC3_COMMNET_WINDOW_WIDE — the same window at hid 256 and nothing else.
+// Every refusal comes before the launch.
+int ic3::commnet_step_window(ic3_env* env, const ic3_commnet_window* w, bool wide, float* h, float* c, const int32_t* alive_in,
                              const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
                              int32_t* alive, int32_t* is_completed, ic3_stream stream)
 {
     using namespace ic3;
-    const std::string who = "ic3_policy_step (ic3_commnet_window)";
+    const std::string who = wide ? "ic3_policy_step (ic3_commnet_window, wide)" : "ic3_policy_step (ic3_commnet_window)";
     if (!env) return fail(-22, who + ": null handle");
     // the one-shots of the per-step calls have no meaning here (the descriptor names the records): disarmed, and the call refused
     const bool armed = env->h_out || env->c_out || env->gates_out || env->xh_out || env->ev_start || env->ev_stop;
@@ -851,7 +852,12 @@ int ic3::commnet_step_window(ic3_env* env, const ic3_commnet_window* w, float* h
     if (p.nheads < 1 || p.nheads > 4) return fail(-22, who + ": 1..4 action heads");
     const int H = p.H;
     const int lds = ic3_commnet_step_supported(env, H);
-    if (!lds || (H != 64 && H != 128))
+    if (wide && (H == 64 || H == 128))
+        return fail(-38, who + ": IC3_COMMNET_WINDOW_WIDE is the window at hid_size 256 (hid_size 64 / 128: tag the descriptor IC3_COMMNET_WINDOW)");
+    if (wide && (!lds || H != 256))
+        return fail(-38, who + ": needs hid_size 256, <= 64 agents per env and an env tile that fits in LDS (hid_size 64 / 128: tag the "
+                               "descriptor IC3_COMMNET_WINDOW; otherwise use one call per step)");
+    if (!wide && (!lds || (H != 64 && H != 128)))
         return fail(-38, who + ": needs hid_size 64 / 128, <= 64 agents per env and an env tile that fits in LDS (use one call per step)");
     if (!w->wp3) return fail(-38, who + ": needs wp3, the split products (use one call per step)");
     CommnetArgs a{};
@@ -911,5 +917,6 @@ int ic3::commnet_step_window(ic3_env* env, const ic3_commnet_window* w, float* h
         if (pp) return launch_kernel(commnet_forward_kernel<HH, IC3_ENV_PP, false, false, 1>, grid, block, (size_t)lds, s, a);
         return launch_kernel(commnet_forward_kernel<HH, IC3_ENV_TJ, false, false, 1>, grid, block, (size_t)lds, s, a);
     };
+    if (wide) return go(std::integral_constant<int, 256>{});
     return H == 128 ? go(std::integral_constant<int, 128>{}) : go(std::integral_constant<int, 64>{});
 }

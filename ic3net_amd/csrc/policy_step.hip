@@ -177,7 +177,7 @@ __device__ __forceinline__ void window_step_args(StepArgs& a, int t)
     if (a.so.alive_out) a.so.alive_out += t * R;
     if (a.so.comp_out) a.so.comp_out += t * R;
     if (a.gates_out) a.gates_out += t * R * 4 * H;
-    if (a.xh_out) a.xh_out += t * R * 2 * H;
+    if (a.xh_out) a.xh_out += t * R * (H == 256 ? H : 2 * H);   // (the record's row stride: XLD of the store)
     if (t > 0) {
         a.alive_in = a.win_alive == IC3_WINDOW_ALIVE_PREV ? alive0 + (t - 1) * R : nullptr;
         a.comm_in = a.win_comm == IC3_WINDOW_COMM_LAST_HEAD ? action0 + ((long long)(t - 1) * a.nheads + a.nheads - 1) * R : nullptr;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
 {
     static_assert(!MP || (SPLIT && KIND != 0), "the in-launch pass loop exists for the split gate product on an env handle");
     static_assert(!REC || (SPLIT && KIND == 0 && !MP), "the recording pass exists for the split gate product on a caller's encoder output");
-    static_assert(!WIN || (SPLIT && KIND != 0 && !REC && H <= 128), "the window form exists for the split gate product on an env handle");
+    static_assert(!WIN || (SPLIT && KIND != 0 && !REC && (H <= 128 || !MP)), "the window form exists for the split gate product on an env handle");
     constexpr int K = 2 * H, LDA = K + 4, LDA4 = LDA / 4, BM = 64, NT = 2 * H, NW = H / 32, H4 = H / 4;
     IC3_DYNAMIC_LDS(float, smem);
     float* const As = smem;                                      // [BM][LDA]: cols [0,H) enc / comm / inp, [H,2H) h / h'
@@ -1454,12 +1454,14 @@ extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, 
 
 // ic3_policy_step on an ic3_policy_window: T lock-steps of the recorded training rollout in one launch (the WIN instantiations).
 // `passes`: the descriptor is tagged IC3_POLICY_WINDOW_PASSES — npasses = 2..4 communication passes per step (the MP + WIN
-// instantiations), no gate / inp record.
-static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool passes, float* h, float* c, const int32_t* alive_in,
+// instantiations), no gate / inp record.  `wide`: tagged IC3_POLICY_WINDOW_WIDE — the one-pass window at hid 256 and nothing else
+// (one workgroup of 512 threads per CU; the inp record has row stride H).
+static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool passes, bool wide, float* h, float* c, const int32_t* alive_in,
                               const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
                               int32_t* alive, int32_t* is_completed, ic3_stream stream)
 {
-    const std::string who = passes ? "ic3_policy_step (ic3_policy_window, passes)" : "ic3_policy_step (ic3_policy_window)";
+    const std::string who = passes ? "ic3_policy_step (ic3_policy_window, passes)"
+                            : wide ? "ic3_policy_step (ic3_policy_window, wide)" : "ic3_policy_step (ic3_policy_window)";
     if (!env) return fail(-22, who + ": null handle");
     // the one-shots of the per-step call have no meaning here (the descriptor names the record): disarmed, and the call refused
     const bool armed = env->h_out || env->c_out || env->gates_out || env->xh_out || env->ev_start || env->ev_stop;
@@ -1488,7 +1490,12 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool pas
     const int H = p->H;
     const int lds = policy_step_lds(env, H);
     auto shape_ok = [&]() {
-        if (!lds || (H != 64 && H != 128))
+        if (wide && (H == 64 || H == 128))
+            return fail(-38, who + ": IC3_POLICY_WINDOW_WIDE is the window at hid_size 256 (hid_size 64 / 128: tag the descriptor IC3_POLICY_WINDOW)");
+        if (wide && (!lds || H != 256))
+            return fail(-38, who + ": needs hid_size 256, <= 64 agents per env and an env tile that fits in LDS (hid_size 64 / 128: tag "
+                                   "the descriptor IC3_POLICY_WINDOW; otherwise use one call per step)");
+        if (!wide && (!lds || (H != 64 && H != 128)))
             return fail(-38, who + ": needs hid_size 64 / 128, <= 64 agents per env and an env tile that fits in LDS (use one call per step)");
         if (!p->gate_split || !p->lstm_wp3) return fail(-38, who + ": needs gate_split with lstm_wp3 (use one call per step)");
         return 0;
@@ -1538,6 +1545,7 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool pas
             return pp ? launch_step<128, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<128, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
         return pp ? launch_step<64, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<64, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
     }
+    if (wide) return pp ? launch_step<256, IC3_ENV_PP, 1, 0, 0, 1>(a, tiles, lds, s) : launch_step<256, IC3_ENV_TJ, 1, 0, 0, 1>(a, tiles, lds, s);
     if (H == 128)
         return pp ? launch_step<128, IC3_ENV_PP, 1, 0, 0, 1>(a, tiles, lds, s) : launch_step<128, IC3_ENV_TJ, 1, 0, 0, 1>(a, tiles, lds, s);
     return pp ? launch_step<64, IC3_ENV_PP, 1, 0, 0, 1>(a, tiles, lds, s) : launch_step<64, IC3_ENV_TJ, 1, 0, 0, 1>(a, tiles, lds, s);
@@ -1554,7 +1562,7 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
         if (p->struct_size != sizeof(ic3_policy_window))
             return fail(-22, "ic3_policy_step (ic3_policy_window): struct_size is " + std::to_string(p->struct_size) +
                                  ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
-        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), false, h, c, alive_in, comm_in, out, action, obs,
+        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), false, false, h, c, alive_in, comm_in, out, action, obs,
                                   reward, done, alive, is_completed, stream);
     }
     // (the same struct with npasses = 2..4 communication passes per step: a tag of its own, so that IC3_POLICY_WINDOW keeps its answers)
@@ -1562,15 +1570,25 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
         if (p->struct_size != sizeof(ic3_policy_window))
             return fail(-22, "ic3_policy_step (ic3_policy_window, passes): struct_size is " + std::to_string(p->struct_size) +
                                  ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
-        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), true, h, c, alive_in, comm_in, out, action, obs,
+        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), true, false, h, c, alive_in, comm_in, out, action, obs,
                                   reward, done, alive, is_completed, stream);
     }
-    // (likewise the window of ic3_commnet_step's families, played by commnet_fwd.hip's kernel)
-    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_COMMNET_WINDOW) {
+    // (and with hid 256: again a tag of its own, so that IC3_POLICY_WINDOW keeps its -ENOSYS there)
+    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_POLICY_WINDOW_WIDE) {
+        if (p->struct_size != sizeof(ic3_policy_window))
+            return fail(-22, "ic3_policy_step (ic3_policy_window, wide): struct_size is " + std::to_string(p->struct_size) +
+                                 ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
+        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), false, true, h, c, alive_in, comm_in, out, action, obs,
+                                  reward, done, alive, is_completed, stream);
+    }
+    // (likewise the window of ic3_commnet_step's families, played by commnet_fwd.hip's kernel; IC3_COMMNET_WINDOW_WIDE: at hid 256)
+    if (p && p->struct_size >= sizeof(ic3_policy) && (p->inner_pass == IC3_COMMNET_WINDOW || p->inner_pass == IC3_COMMNET_WINDOW_WIDE)) {
+        const bool wide = p->inner_pass == IC3_COMMNET_WINDOW_WIDE;
         if (p->struct_size != sizeof(ic3_commnet_window))
-            return fail(-22, "ic3_policy_step (ic3_commnet_window): struct_size is " + std::to_string(p->struct_size) +
+            return fail(-22, std::string(wide ? "ic3_policy_step (ic3_commnet_window, wide)" : "ic3_policy_step (ic3_commnet_window)") +
+                                 ": struct_size is " + std::to_string(p->struct_size) +
                                  ", this library's ic3_commnet_window has " + std::to_string(sizeof(ic3_commnet_window)) + " bytes");
-        return commnet_step_window(env, reinterpret_cast<const ic3_commnet_window*>(p), h, c, alive_in, comm_in, out, action, obs, reward,
+        return commnet_step_window(env, reinterpret_cast<const ic3_commnet_window*>(p), wide, h, c, alive_in, comm_in, out, action, obs, reward,
                                    done, alive, is_completed, stream);
     }
     if (int src = check_policy_struct(p, "ic3_policy_step")) return src;      // before any other field is read

@@ -60,7 +60,8 @@ inline void fill_env_args(Args& a, ic3_env* env, float* reward, int32_t* done, i
 }
 
 // ic3_policy_step on an ic3_commnet_window (commnet_fwd.hip): ic3_policy_step's arguments behind the descriptor's tag and size check
-int commnet_step_window(ic3_env* env, const ic3_commnet_window* w, float* h, float* c, const int32_t* alive_in, const int32_t* comm_in,
+// (`wide`: the tag was IC3_COMMNET_WINDOW_WIDE)
+int commnet_step_window(ic3_env* env, const ic3_commnet_window* w, bool wide, float* h, float* c, const int32_t* alive_in, const int32_t* comm_in,
                         float* out, int32_t* action, float* obs, float* reward, int32_t* done, int32_t* alive, int32_t* is_completed,
                         ic3_stream stream);
 

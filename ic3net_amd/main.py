@@ -70,7 +70,12 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  # 1: ... in collection mode (--auto_reset) too — the window that starts the E streams and every window that
                  # continues them (step 0 handed the previous window's masks and state; restarts happen inside the launch); acts
                  # only together with --window_launch and --auto_reset.  0 (default): collection windows keep one launch per step
-                 ('window_launch_collection', int, 0)]
+                 ('window_launch_collection', int, 0),
+                 # 1: ... at hid_size 256 too (the library's IC3_POLICY_WINDOW_WIDE / IC3_COMMNET_WINDOW_WIDE descriptors): the
+                 # one-pass LSTM policy, the non-recurrent CommNet module, the IC baseline and IRIC with the tanh recurrence; acts only
+                 # together with --window_launch, combines with --window_launch_collection / --auto_reset.  0 (default): hid 256
+                 # keeps one launch per step (as do IRIC's LSTM cell and comm_passes > 1 at that width, whatever this says)
+                 ('window_launch_wide', int, 0)]
 
 
 def build_parser(argv):

@@ -82,16 +82,16 @@ class MLP(nn.Module):
         self._stand_in.done()
         return out
 
-    def commnet_window_supported(self, env):
+    def commnet_window_supported(self, env, wide=False):
         """A recorded training window may be played in ONE launch (CommNetMLP.step_env_commnet_window on the stand-in): models.MLP,
-        and models.RNN with the tanh recurrence at the kernels' own hidden sizes."""
+        and models.RNN with the tanh recurrence at the kernels' own hidden sizes (hid 256: with `wide`)."""
         from . import ops
         if type(self) is not MLP and getattr(self.args, 'rnn_type', 'MLP') == 'LSTM':
             return False
         if torch.is_grad_enabled() or ops.padded_hidden(self.args.hid_size) is not None:
             return False
         n = self._stand_in.get()
-        return n is not None and n.commnet_window_supported(env)
+        return n is not None and n.commnet_window_supported(env, wide=wide)
 
     def step_env_commnet_window(self, env, info, T, *bufs, **kw):
         n = self._stand_in.get()
@@ -257,9 +257,9 @@ class RNN(MLP):
         self._stand_in.done()
         return out
 
-    def window_supported(self, env):
+    def window_supported(self, env, wide=False):
         n = self._kernel()
-        return n is not None and self.record_inplace_ok() and n.window_supported(env)
+        return n is not None and self.record_inplace_ok() and n.window_supported(env, wide=wide)
 
     def step_env_window(self, env, info, T, *bufs):
         """A recorded training window of T steps in ONE launch (CommNetMLP.step_env_window on the stand-in)."""

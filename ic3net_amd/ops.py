@@ -904,16 +904,20 @@ def policy_step(env, fc, H, head_sizes, mode_avg, comm_zero, h, c, alive_in, com
 WINDOW_COMM_MODES = dict(all=_lib.PolicyWindow.COMM_ALL, last_head=_lib.PolicyWindow.COMM_LAST_HEAD, ones=_lib.PolicyWindow.COMM_ONES)
 
 
-def policy_step_window_supported(env, fc, H, passes=1):
+def policy_step_window_supported(env, fc, H, passes=1, wide=False):
     """ic3_policy_step on an ic3_policy_window can run this env / hid_size: the split gate product, hid 64 / 128, a tile that fits;
-    passes 2..4: the form tagged WINDOW_PASSES, where the per-step call would be the in-launch pass loop."""
+    passes 2..4: the form tagged WINDOW_PASSES, where the per-step call would be the in-launch pass loop.  wide: the form tagged
+    WINDOW_WIDE — hid 256 and one pass, nothing else (hid 64 / 128 are the narrow tag's)."""
     if passes != 1 and not policy_step_passes_supported(fc, H, passes):
         return False
+    if wide:
+        return H == 256 and passes == 1 and fc.get('ps_l_wp3') is not None and policy_step_supported(env, H)
     return H in (64, 128) and fc.get('ps_l_wp3') is not None and policy_step_supported(env, H)
 
 
 def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, alive_in, comm_in, out, action, reward, done,
-                       alive=None, is_completed=None, gates=None, inp=None, snaps=None, alive_prev=False, comm_mode='all', passes=1):
+                       alive=None, is_completed=None, gates=None, inp=None, snaps=None, alive_prev=False, comm_mode='all', passes=1,
+                       wide=False):
     """T consecutive policy_step calls of the recorded training rollout in ONE launch — ic3_policy_step on an ic3_policy_window.
     hs, cs (T+1, E*N, H): step t reads slot t and writes slot t+1; alive_in / comm_in: the masks of step 0; out (T, E*N, OT); action
     (T, heads, E, N) int32; reward / alive / is_completed (T, E, N); done (T, E); gates (T, E*N, 4H) with inp (T, E*N, 2H) or both
@@ -921,7 +925,8 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     the alive slice of step t-1 (Traffic-Junction), else everyone; comm_mode 'all' | 'last_head' (the last head's draws of step t-1)
     | 'ones'.  No dense observation rows.  Same bits as T policy_step calls on the same handle.  passes >= 2: every step runs that
     many communication passes inside the launch (the descriptor tagged WINDOW_PASSES, the passes' weights from `fc` as policy_step
-    takes them); no gate record then.  NotImplementedError where the library answers -ENOSYS."""
+    takes them); no gate record then.  wide: the descriptor tagged WINDOW_WIDE — hid 256, one pass, and inp (T, E*N, H): the inp rows
+    alone (record_xh_width).  NotImplementedError where the library answers -ENOSYS."""
     _need_cuda(hs, "policy_step_window")
     T = int(T)
     R, nh, OT = hs.shape[1], len(head_sizes), sum(head_sizes) + 1
@@ -930,7 +935,9 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     assert _mask(alive_in, R) and _mask(comm_in, R)
     assert _f32(reward, T * R) and _i32(alive, T * R, none_ok=True) and _i32(is_completed, T * R, none_ok=True)
     assert _i32(done, T * env.nenvs)
-    assert (gates is None) == (inp is None) and (gates is None or (_dense(gates, (T, R, 4 * H)) and _dense(inp, (T, R, 2 * H))))
+    assert not wide or (H == 256 and int(passes) == 1), "WINDOW_WIDE is the one-pass window at hid 256"
+    XW = record_xh_width(H) if wide else 2 * H
+    assert (gates is None) == (inp is None) and (gates is None or (_dense(gates, (T, R, 4 * H)) and _dense(inp, (T, R, XW))))
     assert snaps is None or (snaps.dtype == torch.int32 and snaps.is_contiguous() and snaps.dim() == 2 and snaps.shape[0] == T)
     assert not alive_prev or alive is not None
     passes = int(passes)
@@ -938,7 +945,7 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, passes=passes)
     win = _lib.PolicyWindow()
     C.memmove(C.addressof(win), C.addressof(pol), C.sizeof(pol))
-    win.struct_size, win.inner_pass = C.sizeof(win), win.WINDOW if passes == 1 else win.WINDOW_PASSES
+    win.struct_size, win.inner_pass = C.sizeof(win), win.WINDOW_WIDE if wide else win.WINDOW if passes == 1 else win.WINDOW_PASSES
     win.T = T
     win.alive_mode = win.ALIVE_PREV if alive_prev else win.ALIVE_ALL
     win.comm_mode = WINDOW_COMM_MODES[comm_mode]
@@ -950,22 +957,25 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     return out
 
 
-def commnet_step_window_supported(env, cn, H):
-    """ic3_policy_step on an ic3_commnet_window can run this env / hid_size: the split products, hid 64 / 128, a tile that fits."""
-    return H in (64, 128) and cn.get('wp3') is not None and commnet_step_supported(env, H)
+def commnet_step_window_supported(env, cn, H, wide=False):
+    """ic3_policy_step on an ic3_commnet_window can run this env / hid_size: the split products, hid 64 / 128, a tile that fits.
+    wide: the form tagged WINDOW_WIDE — hid 256, nothing else."""
+    return (H == 256 if wide else H in (64, 128)) and cn.get('wp3') is not None and commnet_step_supported(env, H)
 
 
 def commnet_step_window(env, cn, H, head_sizes, mode_avg, comm_zero, T, alive_in, comm_in, out, action, reward, done, alive,
-                        is_completed, hs=None, h_fin=None, snaps=None, alive_prev=False, comm_mode='all'):
+                        is_completed, hs=None, h_fin=None, snaps=None, alive_prev=False, comm_mode='all', wide=False):
     """T consecutive commnet_step calls of the recorded training rollout in ONE launch — ic3_policy_step on an ic3_commnet_window.
     `cn`: the module's derived weights, as for commnet_step.  alive_in / comm_in: the masks of step 0; out (T, E*N, OT); action
     (T, heads, E, N) int32; reward / alive / is_completed (T, E, N); done (T, E).  hs (T+1, E*N, H): the tanh recurrence — step t
     reads slot t as h_in and writes slot t+1 — or None; h_fin (T, E*N, H) or None: the module's final hidden state of every step;
     snaps (T, words >= state_words) int32 or None: the env state entering every step.  The masks of step t >= 1 as in
-    policy_step_window.  No dense observation rows.  Same bits as T commnet_step calls.  NotImplementedError where the library
-    answers -ENOSYS (hid 256, no split planes, a tile that does not fit)."""
+    policy_step_window.  No dense observation rows.  Same bits as T commnet_step calls.  wide: the descriptor tagged WINDOW_WIDE —
+    hid 256.  NotImplementedError where the library answers -ENOSYS (hid 256 without `wide`, no split planes, a tile that does not
+    fit)."""
     _need_cuda(out, "commnet_step_window")
     T, H = int(T), int(H)
+    assert not wide or H == 256, "WINDOW_WIDE is the window at hid 256"
     R, nh, OT = out.shape[1], len(head_sizes), sum(int(a) for a in head_sizes) + 1
     assert T >= 1 and _dense(out, (T, R, OT), torch.float32) and _i32(action, T * nh * R)
     assert _mask(alive_in, R) and _mask(comm_in, R)
@@ -975,7 +985,7 @@ def commnet_step_window(env, cn, H, head_sizes, mode_avg, comm_zero, T, alive_in
     assert snaps is None or (snaps.dtype == torch.int32 and snaps.is_contiguous() and snaps.dim() == 2 and snaps.shape[0] == T)
     assert not alive_prev or alive is not None
     win = _lib.CommnetWindow()
-    win.inner_pass = win.WINDOW
+    win.inner_pass = win.WINDOW_WIDE if wide else win.WINDOW
     win.H, win.nheads, win.head_sizes = H, nh, int32_array(head_sizes, 4)
     win.mode_avg, win.comm_zero, win.npasses = int(bool(mode_avg)), int(bool(comm_zero)), int(cn['wp'].shape[0])
     win.T, win.recurrence = T, int(hs is not None)

@@ -932,6 +932,23 @@ typedef struct ic3_commnet_window {
     int32_t* snaps;
     int64_t snap_words;
 } ic3_commnet_window;
+/* The two one-pass windows at hid_size 256 — tags of their own, so that IC3_POLICY_WINDOW and IC3_COMMNET_WINDOW keep every answer
+ * they give (-ENOSYS at hid_size 256 among them); no new symbol, no new struct:
+ *   IC3_POLICY_WINDOW_WIDE    policy.inner_pass = 6 AND policy.struct_size = sizeof(ic3_policy_window)
+ *   IC3_COMMNET_WINDOW_WIDE   policy.inner_pass = 7 AND policy.struct_size = sizeof(ic3_commnet_window)
+ * Each means "the same window at hid_size 256" and nothing else: the arguments, the modes, the snapshots, the auto-reset restarts,
+ * continuing windows and the order of the refusals are those of the narrow tag, and everything the launch writes is the SAME BITS
+ * as T per-step calls at hid_size 256 on a twin handle.  One workgroup of 512 threads per CU plays a tile (the per-step launch's
+ * geometry at this width); an env tile's share of a state field must fit 512 words.
+ * The one difference in layout, under IC3_POLICY_WINDOW_WIDE:  inp is [T][E*N][H] — the inp rows alone with row stride H, as
+ * ic3_env_set_record_out writes them per step at hid_size 256 (the window backward reads h from the (h, c) record there) — where
+ * the narrow tag's is [T][E*N][2H].  gates stays [T][E*N][4H].
+ * Any other hid_size under a wide tag: -ENOSYS with a message that names the narrow tag (64 / 128) to use.  A tagged descriptor of
+ * any other size: -EINVAL, and a plain ic3_policy whose inner_pass carries 6 or 7 is refused the same way (pass 1 for an inner
+ * pass).  IC3_POLICY_WINDOW_PASSES has no wide twin: the npasses launch exists for hid_size 64 / 128 only.
+ * Error messages begin "ic3_policy_step (ic3_policy_window, wide)" / "ic3_policy_step (ic3_commnet_window, wide)". */
+#define IC3_POLICY_WINDOW_WIDE 6
+#define IC3_COMMNET_WINDOW_WIDE 7
 
 /* The NON-recurrent CommNet module after the encoder (comm.py:127-129,179-205,220-224,228-239), every communication pass
  * in ONE launch:  x = tanh(enc);  h_0 = x;  h_{i+1} = tanh(x + f_modules[i](h_i) + C_modules[i](comm(h_i)));

@@ -8,7 +8,8 @@ MULTIPASS_COLLECTION=1 sends its collection-mode windows (argument 7 = 1) throug
 off by default).  WINDOW_LAUNCH=1 sets args.window_launch: the recorded rollout of an update as one launch per window (the line says how
 many windows went through it: the LSTM policies' ic3_policy_window, and the ic3_commnet_window of tj_medium_commnet_mlp, pp_hard_ic and
 pp_hard_iric_tanh); WINDOW_LAUNCH_COLLECTION=1 sets args.window_launch_collection beside it: the windows of collection mode (argument 7
-= 1) too.  BATCH_WINDOWS=<k>: an update of k windows of max_steps steps (default 1; in collection mode the first starts the streams and
+= 1) too; WINDOW_LAUNCH_WIDE=1 sets args.window_launch_wide beside WINDOW_LAUNCH: the windows of a hid-256 policy too.  HID=<H> overrides
+the workload's hid_size (HID=256: the hid-128 workloads at the width of pp_scaled).  BATCH_WINDOWS=<k>: an update of k windows of max_steps steps (default 1; in collection mode the first starts the streams and
 the others continue them)."""
 import os
 import sys
@@ -32,13 +33,15 @@ def main():
         over['comm_passes'] = int(os.environ['COMM_PASSES'])
         if os.environ.get('SHARE_WEIGHTS', '0') == '1':
             over['share_weights'] = True
-    tr, a = bench.build_trainer(wl, E, 0, 0, 0, **over)
+    shape = dict(hid_size=int(os.environ['HID'])) if os.environ.get('HID') else {}
+    tr, a = bench.build_trainer(wl, E, 0, 0, 0, **dict(over, **shape))
     if over and 'MULTIPASS_WINDOW' in os.environ:            # A/B: the window backward of comm_passes > 1 policies against the loop
         a.multipass_window_backward = os.environ['MULTIPASS_WINDOW'] == '1'
     if over and 'MULTIPASS_COLLECTION' in os.environ:
         a.multipass_window_collection = os.environ['MULTIPASS_COLLECTION'] == '1'
     a.window_launch = os.environ.get('WINDOW_LAUNCH', '0') == '1'
     a.window_launch_collection = int(os.environ.get('WINDOW_LAUNCH_COLLECTION', '0'))
+    a.window_launch_wide = int(os.environ.get('WINDOW_LAUNCH_WIDE', '0'))
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
@@ -73,7 +76,7 @@ def main():
     passes = "" if not over else " comm_passes=%d%s (window backwards %d, chunk of %s steps; loop backwards %d)" % (
         over['comm_passes'], " shared" if over.get('share_weights') else "", getattr(knet, 'multipass_window_backwards', 0),
         getattr(knet, 'multipass_window_chunk', '-'), getattr(knet, 'multipass_loop_backwards', 0))
-    label = wl + passes + (" (obs rows assembled in the rollout)" if a.train_dense_obs else "") + ("" if split else " (fp32 MFMA gate product)") + \
+    label = wl + (" hid=%d" % a.hid_size if shape else "") + passes + (" (obs rows assembled in the rollout)" if a.train_dense_obs else "") + ("" if split else " (fp32 MFMA gate product)") + \
         (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "") + \
         (" (window_launch: %d windows in one launch each)" % getattr(knet, 'window_launches', 0) if a.window_launch else "")
     print("train_batch [%s] %s E=%d: %.0f env-steps/s = %.2f M agent-steps/s (%.2f s per update of %d env-steps), "
