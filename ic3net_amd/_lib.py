@@ -70,10 +70,11 @@ class PolicyWindow(_SizedStruct):
     """ic3_policy_window (include/ic3_rollout.h): an ic3_policy followed by the operands of a window of T lock-steps; handed to
     ic3_policy_step in place of a Policy, with inner_pass = WINDOW (the tag that selects this form) and its own struct_size.
     WINDOW_PASSES: the same struct for npasses = 2..4 communication passes per step (no gate record).  WINDOW_WIDE: the same struct
-    for the one-pass window at hid 256 (inp rows of width H)."""
+    for the one-pass window at hid 256 (inp rows of width H).  WINDOW_WIDE_PASSES: the same struct for npasses = 2..4 at hid 256."""
     WINDOW = 3                                 # IC3_POLICY_WINDOW
     WINDOW_PASSES = 5                          # IC3_POLICY_WINDOW_PASSES
     WINDOW_WIDE = 6                            # IC3_POLICY_WINDOW_WIDE
+    WINDOW_WIDE_PASSES = 8                     # IC3_POLICY_WINDOW_WIDE_PASSES
     ALIVE_ALL, ALIVE_PREV = 0, 1               # IC3_WINDOW_ALIVE_*: the alive mask of step t >= 1
     COMM_ALL, COMM_LAST_HEAD, COMM_ONES = 0, 1, 2   # IC3_WINDOW_COMM_*: the gate of step t >= 1
     _fields_ = Policy._fields_ + [("T", C.c_int32), ("alive_mode", C.c_int32), ("comm_mode", C.c_int32), ("reserved", C.c_int32),

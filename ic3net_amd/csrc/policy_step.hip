@@ -203,12 +203,14 @@ __device__ __forceinline__ void window_step_args(StepArgs& a, int t)
 // keys on the step (window_step_args, the snapshot, the hand-off, the exit) keys on `wstep`.  Pass 0 of step t reads slot t of (h, c);
 // the inner passes hand c' on through slot t + 1 (the window's c_out), the last pass stores h', c' there: slot t is never written.
 // No gate / inp record (the MP launch has none).
+// MP = 1 at H = 256 (with and without WIN; the latter under the tag IC3_POLICY_WINDOW_WIDE_PASSES): the same loops in the geometry of
+// every hid-256 step kernel, one workgroup of 512 threads per CU.
 template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0, int WIN = 0>
 __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(const StepArgs a_in)
 {
     static_assert(!MP || (SPLIT && KIND != 0), "the in-launch pass loop exists for the split gate product on an env handle");
     static_assert(!REC || (SPLIT && KIND == 0 && !MP), "the recording pass exists for the split gate product on a caller's encoder output");
-    static_assert(!WIN || (SPLIT && KIND != 0 && !REC && (H <= 128 || !MP)), "the window form exists for the split gate product on an env handle");
+    static_assert(!WIN || (SPLIT && KIND != 0 && !REC), "the window form exists for the split gate product on an env handle");
     constexpr int K = 2 * H, LDA = K + 4, LDA4 = LDA / 4, BM = 64, NT = 2 * H, NW = H / 32, H4 = H / 4;
     IC3_DYNAMIC_LDS(float, smem);
     float* const As = smem;                                      // [BM][LDA]: cols [0,H) enc / comm / inp, [H,2H) h / h'
@@ -1455,12 +1457,13 @@ extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, 
 // ic3_policy_step on an ic3_policy_window: T lock-steps of the recorded training rollout in one launch (the WIN instantiations).
 // `passes`: the descriptor is tagged IC3_POLICY_WINDOW_PASSES — npasses = 2..4 communication passes per step (the MP + WIN
 // instantiations), no gate / inp record.  `wide`: tagged IC3_POLICY_WINDOW_WIDE — the one-pass window at hid 256 and nothing else
-// (one workgroup of 512 threads per CU; the inp record has row stride H).
+// (one workgroup of 512 threads per CU; the inp record has row stride H).  `passes` and `wide`: tagged IC3_POLICY_WINDOW_WIDE_PASSES —
+// the npasses window at hid 256 and nothing else (the MP + WIN instantiations at 256).
 static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool passes, bool wide, float* h, float* c, const int32_t* alive_in,
                               const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
                               int32_t* alive, int32_t* is_completed, ic3_stream stream)
 {
-    const std::string who = passes ? "ic3_policy_step (ic3_policy_window, passes)"
+    const std::string who = passes ? (wide ? "ic3_policy_step (ic3_policy_window, wide passes)" : "ic3_policy_step (ic3_policy_window, passes)")
                             : wide ? "ic3_policy_step (ic3_policy_window, wide)" : "ic3_policy_step (ic3_policy_window)";
     if (!env) return fail(-22, who + ": null handle");
     // the one-shots of the per-step call have no meaning here (the descriptor names the record): disarmed, and the call refused
@@ -1490,11 +1493,12 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool pas
     const int H = p->H;
     const int lds = policy_step_lds(env, H);
     auto shape_ok = [&]() {
+        const std::string narrow = passes ? "IC3_POLICY_WINDOW_PASSES" : "IC3_POLICY_WINDOW";
         if (wide && (H == 64 || H == 128))
-            return fail(-38, who + ": IC3_POLICY_WINDOW_WIDE is the window at hid_size 256 (hid_size 64 / 128: tag the descriptor IC3_POLICY_WINDOW)");
+            return fail(-38, who + ": " + (passes ? "IC3_POLICY_WINDOW_WIDE_PASSES" : "IC3_POLICY_WINDOW_WIDE") + " is the window at hid_size 256 (hid_size 64 / 128: tag the descriptor " + narrow + ")");
         if (wide && (!lds || H != 256))
             return fail(-38, who + ": needs hid_size 256, <= 64 agents per env and an env tile that fits in LDS (hid_size 64 / 128: tag "
-                                   "the descriptor IC3_POLICY_WINDOW; otherwise use one call per step)");
+                                   "the descriptor " + narrow + "; otherwise use one call per step)");
         if (!wide && (!lds || (H != 64 && H != 128)))
             return fail(-38, who + ": needs hid_size 64 / 128, <= 64 agents per env and an env tile that fits in LDS (use one call per step)");
         if (!p->gate_split || !p->lstm_wp3) return fail(-38, who + ": needs gate_split with lstm_wp3 (use one call per step)");
@@ -1541,6 +1545,7 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool pas
     hipStream_t s = (hipStream_t)stream;
     const int tiles = plan_tiles(a, H, p, s);
     if (passes) {
+        if (wide) return pp ? launch_step<256, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<256, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
         if (H == 128)
             return pp ? launch_step<128, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<128, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
         return pp ? launch_step<64, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<64, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
@@ -1579,6 +1584,14 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
             return fail(-22, "ic3_policy_step (ic3_policy_window, wide): struct_size is " + std::to_string(p->struct_size) +
                                  ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
         return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), false, true, h, c, alive_in, comm_in, out, action, obs,
+                                  reward, done, alive, is_completed, stream);
+    }
+    // (and the npasses window at hid 256: IC3_POLICY_WINDOW_PASSES and IC3_POLICY_WINDOW_WIDE keep their -ENOSYS there)
+    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_POLICY_WINDOW_WIDE_PASSES) {
+        if (p->struct_size != sizeof(ic3_policy_window))
+            return fail(-22, "ic3_policy_step (ic3_policy_window, wide passes): struct_size is " + std::to_string(p->struct_size) +
+                                 ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
+        return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), true, true, h, c, alive_in, comm_in, out, action, obs,
                                   reward, done, alive, is_completed, stream);
     }
     // (likewise the window of ic3_commnet_step's families, played by commnet_fwd.hip's kernel; IC3_COMMNET_WINDOW_WIDE: at hid 256)
@@ -1691,9 +1704,10 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
         a.zrest = (fused_obs && !incr_valid) ? (int)(left > 0 ? left + 1 : 0) : 0;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (a.npass > 1) {   // comm_passes > 1 as a loop inside the launch (MP instantiations: split gate product, hid 64 / 128)
-        if (!a.l_wp3 || (H != 128 && H != 64))
-            return fail(-38, "ic3_policy_step: npasses >= 2 needs gate_split and hid_size 64 / 128 (use one call per pass)");
+    if (a.npass > 1) {   // comm_passes > 1 as a loop inside the launch (MP instantiations: split gate product, hid 64 / 128 / 256)
+        if (!a.l_wp3 || (H != 256 && H != 128 && H != 64))
+            return fail(-38, "ic3_policy_step: npasses >= 2 needs gate_split and hid_size 64 / 128 / 256 (use one call per pass)");
+        if (H == 256) return launch_step_env<256, 1, 1>(pp, a, tiles, lds, s, ev0, ev1);
         return H == 128 ? launch_step_env<128, 1, 1>(pp, a, tiles, lds, s, ev0, ev1) : launch_step_env<64, 1, 1>(pp, a, tiles, lds, s, ev0, ev1);
     }
     return with_hid(H, [&](auto hid) {

@@ -74,8 +74,16 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  # 1: ... at hid_size 256 too (the library's IC3_POLICY_WINDOW_WIDE / IC3_COMMNET_WINDOW_WIDE descriptors): the
                  # one-pass LSTM policy, the non-recurrent CommNet module, the IC baseline and IRIC with the tanh recurrence; acts only
                  # together with --window_launch, combines with --window_launch_collection / --auto_reset.  0 (default): hid 256
-                 # keeps one launch per step (as do IRIC's LSTM cell and comm_passes > 1 at that width, whatever this says)
-                 ('window_launch_wide', int, 0)]
+                 # keeps one launch per step (as do IRIC's LSTM cell and comm_passes > 1 at that width, whatever this says — the
+                 # latter unless --passes_in_launch_wide is set)
+                 ('window_launch_wide', int, 0),
+                 # 1: a hid_size 256 recurrent CommNet / IC3Net policy with comm_passes 2..4 runs every step as ONE launch with the
+                 # passes inside (ic3_policy.npasses, as hid 64 / 128 do by default) — evaluation and training rollouts, with or without
+                 # obs rows; together with --window_launch and --window_launch_wide 1 its recorded training windows play in one launch
+                 # each (the library's IC3_POLICY_WINDOW_WIDE_PASSES descriptor), and with --window_launch_collection 1 / --auto_reset
+                 # its collection windows too.  0 (default): comm_passes launches per step at that width.  Zero-padded twins,
+                 # comm_passes > 4, passes_in_launch = False and IRIC's LSTM cell keep their per-step path whatever this says
+                 ('passes_in_launch_wide', int, 0)]
 
 
 def build_parser(argv):

@@ -257,9 +257,9 @@ class RNN(MLP):
         self._stand_in.done()
         return out
 
-    def window_supported(self, env, wide=False):
+    def window_supported(self, env, wide=False, **kw):
         n = self._kernel()
-        return n is not None and self.record_inplace_ok() and n.window_supported(env, wide=wide)
+        return n is not None and self.record_inplace_ok() and n.window_supported(env, wide=wide, **kw)
 
     def step_env_window(self, env, info, T, *bufs):
         """A recorded training window of T steps in ONE launch (CommNetMLP.step_env_window on the stand-in)."""

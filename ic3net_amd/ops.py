@@ -808,10 +808,11 @@ def policy_pack_split_bwd(w_ih, w_hh):
     return _pack_split(_lib.lib().ic3_policy_pack_split_bwd, "policy_pack_split_bwd", w_ih, w_hh)
 
 
-def policy_step_passes_supported(fc, H, passes):
+def policy_step_passes_supported(fc, H, passes, wide_passes=False):
     """comm_passes > 1 as a loop INSIDE one ic3_policy_step launch (ic3_policy.npasses): the split gate product, hid 64 / 128,
-    at most 4 passes; otherwise one launch per pass."""
-    return 2 <= passes <= 4 and H in (64, 128) and fc.get('ps_l_wp3') is not None
+    at most 4 passes; otherwise one launch per pass.  wide_passes: hid 256 as well (the library runs it there; this layer asks for
+    it only behind --passes_in_launch_wide)."""
+    return 2 <= passes <= 4 and (H in (64, 128) or (bool(wide_passes) and H == 256)) and fc.get('ps_l_wp3') is not None
 
 
 def _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, encoder=True, pass_index=0, inner=False, passes=1):
@@ -904,10 +905,13 @@ def policy_step(env, fc, H, head_sizes, mode_avg, comm_zero, h, c, alive_in, com
 WINDOW_COMM_MODES = dict(all=_lib.PolicyWindow.COMM_ALL, last_head=_lib.PolicyWindow.COMM_LAST_HEAD, ones=_lib.PolicyWindow.COMM_ONES)
 
 
-def policy_step_window_supported(env, fc, H, passes=1, wide=False):
+def policy_step_window_supported(env, fc, H, passes=1, wide=False, wide_passes=False):
     """ic3_policy_step on an ic3_policy_window can run this env / hid_size: the split gate product, hid 64 / 128, a tile that fits;
     passes 2..4: the form tagged WINDOW_PASSES, where the per-step call would be the in-launch pass loop.  wide: the form tagged
-    WINDOW_WIDE — hid 256 and one pass, nothing else (hid 64 / 128 are the narrow tag's)."""
+    WINDOW_WIDE — hid 256 and one pass, nothing else (hid 64 / 128 are the narrow tag's).  wide_passes: the form tagged
+    WINDOW_WIDE_PASSES — hid 256 and passes 2..4, nothing else (every other shape is answered as without it)."""
+    if wide_passes and H == 256 and passes != 1:
+        return policy_step_passes_supported(fc, H, passes, wide_passes=True) and policy_step_supported(env, H)
     if passes != 1 and not policy_step_passes_supported(fc, H, passes):
         return False
     if wide:
@@ -917,7 +921,7 @@ def policy_step_window_supported(env, fc, H, passes=1, wide=False):
 
 def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, alive_in, comm_in, out, action, reward, done,
                        alive=None, is_completed=None, gates=None, inp=None, snaps=None, alive_prev=False, comm_mode='all', passes=1,
-                       wide=False):
+                       wide=False, wide_passes=False):
     """T consecutive policy_step calls of the recorded training rollout in ONE launch — ic3_policy_step on an ic3_policy_window.
     hs, cs (T+1, E*N, H): step t reads slot t and writes slot t+1; alive_in / comm_in: the masks of step 0; out (T, E*N, OT); action
     (T, heads, E, N) int32; reward / alive / is_completed (T, E, N); done (T, E); gates (T, E*N, 4H) with inp (T, E*N, 2H) or both
@@ -926,7 +930,8 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     | 'ones'.  No dense observation rows.  Same bits as T policy_step calls on the same handle.  passes >= 2: every step runs that
     many communication passes inside the launch (the descriptor tagged WINDOW_PASSES, the passes' weights from `fc` as policy_step
     takes them); no gate record then.  wide: the descriptor tagged WINDOW_WIDE — hid 256, one pass, and inp (T, E*N, H): the inp rows
-    alone (record_xh_width).  NotImplementedError where the library answers -ENOSYS."""
+    alone (record_xh_width).  wide_passes: the descriptor tagged WINDOW_WIDE_PASSES — hid 256, passes 2..4, no gate record.
+    NotImplementedError where the library answers -ENOSYS."""
     _need_cuda(hs, "policy_step_window")
     T = int(T)
     R, nh, OT = hs.shape[1], len(head_sizes), sum(head_sizes) + 1
@@ -936,6 +941,7 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     assert _f32(reward, T * R) and _i32(alive, T * R, none_ok=True) and _i32(is_completed, T * R, none_ok=True)
     assert _i32(done, T * env.nenvs)
     assert not wide or (H == 256 and int(passes) == 1), "WINDOW_WIDE is the one-pass window at hid 256"
+    assert not wide_passes or (H == 256 and 2 <= int(passes) <= 4 and not wide), "WINDOW_WIDE_PASSES is the 2..4-pass window at hid 256"
     XW = record_xh_width(H) if wide else 2 * H
     assert (gates is None) == (inp is None) and (gates is None or (_dense(gates, (T, R, 4 * H)) and _dense(inp, (T, R, XW))))
     assert snaps is None or (snaps.dtype == torch.int32 and snaps.is_contiguous() and snaps.dim() == 2 and snaps.shape[0] == T)
@@ -945,7 +951,8 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, passes=passes)
     win = _lib.PolicyWindow()
     C.memmove(C.addressof(win), C.addressof(pol), C.sizeof(pol))
-    win.struct_size, win.inner_pass = C.sizeof(win), win.WINDOW_WIDE if wide else win.WINDOW if passes == 1 else win.WINDOW_PASSES
+    win.struct_size, win.inner_pass = C.sizeof(win), win.WINDOW_WIDE_PASSES if wide_passes else win.WINDOW_WIDE if wide else \
+        win.WINDOW if passes == 1 else win.WINDOW_PASSES
     win.T = T
     win.alive_mode = win.ALIVE_PREV if alive_prev else win.ALIVE_ALL
     win.comm_mode = WINDOW_COMM_MODES[comm_mode]

@@ -133,10 +133,13 @@ class Trainer(object):
         IC3Net with comm_passes 2..4 — whose steps would be the in-launch pass loop, copying (h, c) into the record — play theirs in
         the record too, without a gate record (the multipass update re-evaluates the passes itself).  hid 256 — the one-pass LSTM
         policy with its gate record (inp rows of width ops.record_xh_width), the non-recurrent module, the IC baseline and the tanh
-        recurrence — only behind args.window_launch_wide (the library's WINDOW_WIDE tags); IRIC's LSTM cell (no gate record there)
-        and comm_passes > 1 keep one launch per step at that width.  A window the library refused (-38) is not asked for again."""
+        recurrence — only behind args.window_launch_wide (the library's WINDOW_WIDE tags); comm_passes 2..4 at that width only
+        with args.passes_in_launch_wide beside it (the WINDOW_WIDE_PASSES tag: window_supported is handed wide_passes = True then, and
+        only then — a policy that knows `wide` alone is called as before).  IRIC's LSTM cell (no gate record there), zero-padded
+        twins and comm_passes > 4 keep one launch per step at that width.  A window the library refused (-38) is not asked for again."""
         a, rec, raw = self.args, self._rec, getattr(self.env, 'env', None)
         wide = bool(int(getattr(a, 'window_launch_wide', 0)))
+        kw = dict(wide_passes=True) if int(getattr(a, 'passes_in_launch_wide', 0)) else {}
         if not getattr(a, 'window_launch', False) or getattr(self, '_window_refused', False) or rec is None or raw is None:
             return False
         # a collection window (args.auto_reset: the streams' restarts happen inside the launch, step 0 continues what the previous
@@ -162,7 +165,7 @@ class Trainer(object):
             ok_rec = getattr(self.policy_net, 'record_inplace_ok', None)
             with torch.no_grad():
                 return rec.recurrent and rec.gates is None and ok is not None and self._mega_expected(raw) \
-                    and (ok_rec is None or ok_rec()) and rec.hs.shape[2] == a.hid_size and bool(ok(raw, wide=wide))
+                    and (ok_rec is None or ok_rec()) and rec.hs.shape[2] == a.hid_size and bool(ok(raw, wide=wide, **kw))
         if not rec.recurrent or rec.gates is None or rec.xh is None:
             return False
         H = rec.hs.shape[2]
@@ -170,7 +173,7 @@ class Trainer(object):
         if rec.xh.shape[2] != (ops.record_xh_width(H) if wide and H == 256 else 2 * H):
             return False
         with torch.no_grad():                                      # (the grad mode the steps of this rollout run in)
-            return ok is not None and self._rec_inplace() and bool(ok(raw, wide=wide))
+            return ok is not None and self._rec_inplace() and bool(ok(raw, wide=wide, **kw))
 
     def _window_passes(self):
         """Communication passes per step of the policy a window would play (1 where it has no such loop)."""

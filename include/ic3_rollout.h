@@ -797,7 +797,8 @@ typedef struct {
     /* npasses >= 2 (round 5): EVERY communication pass of the step inside ONE ic3_policy_step launch — pass i uses
      * c_wp_pass[i] / enc_bias_pass[i] (those of C_modules[i], as above); h stays in LDS between the passes (only the last
      * pass's h' goes to memory), c passes through c_out.  pass_index and inner_pass must be 0; needs gate_split and
-     * hid_size 64 / 128, at most 4 passes (-ENOSYS otherwise: one call per pass as above).  0 or 1: one pass per call. */
+     * hid_size 64 / 128 / 256, at most 4 passes (-ENOSYS otherwise: one call per pass as above).  At 256 the launch has the
+     * geometry of every step launch of that width, one workgroup of 512 threads per CU.  0 or 1: one pass per call. */
     int32_t npasses;
     const void* lstm_wp3;
     const float* c_wp_pass[4];
@@ -945,10 +946,25 @@ typedef struct ic3_commnet_window {
  * the narrow tag's is [T][E*N][2H].  gates stays [T][E*N][4H].
  * Any other hid_size under a wide tag: -ENOSYS with a message that names the narrow tag (64 / 128) to use.  A tagged descriptor of
  * any other size: -EINVAL, and a plain ic3_policy whose inner_pass carries 6 or 7 is refused the same way (pass 1 for an inner
- * pass).  IC3_POLICY_WINDOW_PASSES has no wide twin: the npasses launch exists for hid_size 64 / 128 only.
+ * pass).  IC3_POLICY_WINDOW_PASSES' wide twin is IC3_POLICY_WINDOW_WIDE_PASSES below.
  * Error messages begin "ic3_policy_step (ic3_policy_window, wide)" / "ic3_policy_step (ic3_commnet_window, wide)". */
 #define IC3_POLICY_WINDOW_WIDE 6
 #define IC3_COMMNET_WINDOW_WIDE 7
+/* The npasses window at hid_size 256 — once more a tag of its own, so that IC3_POLICY_WINDOW_PASSES keeps its -ENOSYS at hid_size 256
+ * and IC3_POLICY_WINDOW_WIDE its -ENOSYS for npasses >= 2; no new symbol, no new struct:
+ *   IC3_POLICY_WINDOW_WIDE_PASSES   policy.inner_pass = 8 AND policy.struct_size = sizeof(ic3_policy_window)
+ * It means "IC3_POLICY_WINDOW_PASSES at hid_size 256" and nothing else: npasses = 2..4, gates = inp = NULL, pass 0 of step t reads
+ * slot t of (h, c), the inner passes hand c' on through slot t + 1, the last pass stores h', c' there, slot t is never written; the
+ * arguments, the modes, the snapshots, the auto-reset restarts (zero state at pass 0 only) and windows that continue running streams
+ * are those of tag 5.  Everything the launch writes, and the state it leaves in the handle, is the SAME BITS as T per-step calls with
+ * the same npasses at hid_size 256 on a twin handle.  One workgroup of 512 threads per CU plays a tile.
+ * Checked in tag 5's order, all before any launch: a tagged descriptor of any other size: -EINVAL (so is a plain ic3_policy whose
+ * inner_pass carries 8; pass 1 for an inner pass); armed one-shots: disarmed, -EINVAL; obs != NULL, reserved != 0, a bad alive_mode /
+ * comm_mode, gates or inp non-NULL: -EINVAL; npasses outside 2..4: -ENOSYS; pass_index != 0: -ENOSYS; a missing c_wp_pass[i] /
+ * enc_bias_pass[i]: -EINVAL; hid_size 64 / 128: -ENOSYS with a message that names IC3_POLICY_WINDOW_PASSES, the tag to use there; any
+ * other hid_size, no gate_split / lstm_wp3, an env tile or a state field that does not fit: -ENOSYS.
+ * Error messages begin "ic3_policy_step (ic3_policy_window, wide passes)". */
+#define IC3_POLICY_WINDOW_WIDE_PASSES 8
 
 /* The NON-recurrent CommNet module after the encoder (comm.py:127-129,179-205,220-224,228-239), every communication pass
  * in ONE launch:  x = tanh(enc);  h_0 = x;  h_{i+1} = tanh(x + f_modules[i](h_i) + C_modules[i](comm(h_i)));

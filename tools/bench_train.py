@@ -8,7 +8,10 @@ MULTIPASS_COLLECTION=1 sends its collection-mode windows (argument 7 = 1) throug
 off by default).  WINDOW_LAUNCH=1 sets args.window_launch: the recorded rollout of an update as one launch per window (the line says how
 many windows went through it: the LSTM policies' ic3_policy_window, and the ic3_commnet_window of tj_medium_commnet_mlp, pp_hard_ic and
 pp_hard_iric_tanh); WINDOW_LAUNCH_COLLECTION=1 sets args.window_launch_collection beside it: the windows of collection mode (argument 7
-= 1) too; WINDOW_LAUNCH_WIDE=1 sets args.window_launch_wide beside WINDOW_LAUNCH: the windows of a hid-256 policy too.  HID=<H> overrides
+= 1) too; WINDOW_LAUNCH_WIDE=1 sets args.window_launch_wide beside WINDOW_LAUNCH: the windows of a hid-256 policy too;
+PASSES_IN_LAUNCH_WIDE=1 sets args.passes_in_launch_wide: a hid-256 policy with COMM_PASSES 2..4 runs each step as one launch (and, with
+the three window switches, its windows as one launch each).  ROLLOUT_ONLY=1 times the rollout half of the timed updates by itself
+(Trainer.run_batch between two synchronisations) and prints its time per step.  HID=<H> overrides
 the workload's hid_size (HID=256: the hid-128 workloads at the width of pp_scaled).  BATCH_WINDOWS=<k>: an update of k windows of max_steps steps (default 1; in collection mode the first starts the streams and
 the others continue them)."""
 import os
@@ -42,6 +45,7 @@ def main():
     a.window_launch = os.environ.get('WINDOW_LAUNCH', '0') == '1'
     a.window_launch_collection = int(os.environ.get('WINDOW_LAUNCH_COLLECTION', '0'))
     a.window_launch_wide = int(os.environ.get('WINDOW_LAUNCH_WIDE', '0'))
+    a.passes_in_launch_wide = int(os.environ.get('PASSES_IN_LAUNCH_WIDE', '0'))
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
@@ -65,6 +69,18 @@ def main():
     gc.freeze()
     torch.cuda.reset_peak_memory_stats()
     torch.cuda.synchronize()
+    rollout_only = os.environ.get('ROLLOUT_ONLY', '0') == '1'
+    if rollout_only:                                          # the rollout half of every timed update (run_batch), timed by itself
+        spent, inner = [0.0], tr.run_batch
+
+        def timed_run_batch(epoch):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = inner(epoch)
+            torch.cuda.synchronize()
+            spent[0] += time.perf_counter() - t
+            return out
+        tr.run_batch = timed_run_batch
     t0 = time.perf_counter()
     steps = 0
     for u in range(updates):
@@ -73,12 +89,19 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     knet = tr._kernel_net()
+    if rollout_only:
+        nsteps = updates * int(os.environ.get('BATCH_WINDOWS', '1')) * a.max_steps
+        print("rollout [%s hid=%d comm_passes=%s%s passes_in_launch_wide=%d] E=%d: %.1f us per step (%d steps of %d updates; %d step launches "
+              "in the process)" % (wl, a.hid_size, over.get('comm_passes', '-'), " shared" if over.get('share_weights') else "",
+                                   a.passes_in_launch_wide, E, spent[0] / nsteps * 1e6, nsteps, updates, getattr(knet, 'mega_steps', 0)))
+        return
     passes = "" if not over else " comm_passes=%d%s (window backwards %d, chunk of %s steps; loop backwards %d)" % (
         over['comm_passes'], " shared" if over.get('share_weights') else "", getattr(knet, 'multipass_window_backwards', 0),
         getattr(knet, 'multipass_window_chunk', '-'), getattr(knet, 'multipass_loop_backwards', 0))
     label = wl + (" hid=%d" % a.hid_size if shape else "") + passes + (" (obs rows assembled in the rollout)" if a.train_dense_obs else "") + ("" if split else " (fp32 MFMA gate product)") + \
         (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "") + \
-        (" (window_launch: %d windows in one launch each)" % getattr(knet, 'window_launches', 0) if a.window_launch else "")
+        (" (window_launch: %d windows in one launch each)" % getattr(knet, 'window_launches', 0) if a.window_launch else "") + \
+        (" (passes_in_launch_wide)" if a.passes_in_launch_wide else "")
     print("train_batch [%s] %s E=%d: %.0f env-steps/s = %.2f M agent-steps/s (%.2f s per update of %d env-steps), "
           "peak mem %.1f GB, gemm %s" % (mode, label, E, steps / dt, a.nagents * steps / dt / 1e6, dt / updates,
                                          steps // updates, torch.cuda.max_memory_allocated() / 2 ** 30,
