@@ -143,6 +143,17 @@ class RnnBptt(_SizedStruct):
                 ("wgrad_scratch", C.c_void_p)]
 
 
+class RnnBpttWalk(_SizedStruct):
+    """ic3_rnn_bptt_walk (include/ic3_rollout.h): an RnnBptt's window with its T steps walked in ONE launch; handed to
+    ic3_rnn_backward_wide in place of an RnnBptt (magic selects this form).  dbias_partials: one row per 64-row tile."""
+    MAGIC = 0x4b4c4157                         # IC3_RNN_BPTT_WALK_MAGIC: the word that selects this form (an ic3_rnn_bptt holds T there)
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32)] + RnnBptt._fields_[1:] + [("reserved", C.c_int64)]
+
+    def __init__(self, *a, **kw):             # positional arguments start at T
+        super().__init__(*((self.MAGIC,) + a if a else a), **kw)
+        self.magic = self.MAGIC
+
+
 class MlpBptt(_SizedStruct):
     """ic3_mlp_bptt (include/ic3_rollout.h): one window of the IC baseline's (models.MLP) backward."""
     _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "enc_first", "enc_window")] + \

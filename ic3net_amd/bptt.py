@@ -1134,14 +1134,17 @@ def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
     the column sums of dz_t as per-workgroup partials; then the sparse encoder's first stage over the ring, and affine2's weight
     gradient sum_t dz_t^T (live_t h_{t-1}) over all T x R rows in one launch.  Behind it: the encoder's expansion (affine1.weight),
     the partials' sum (both biases: affine1(obs) + affine2(h) share dz), the heads' pass beside the chain.  Same cuts as the loop
-    (detach points; collection mode: keep / row_live, the carry in and out); the record is read, never written."""
+    (detach points; collection mode: keep / row_live, the carry in and out); the record is read, never written.
+    args.backward_walk: the T launches as ONE (an ic3_rnn_bptt_walk descriptor: every 64-row tile walked last step to first by one
+    workgroup, dL/dh on chip) — the same dz, dh and weight gradients bit for bit, the bias partials one row per tile."""
     T, R, H = rec.n, rec.hs.shape[1], rec.hs.shape[2]
     N = net.args.nagents
     E = R // N
     dev = rec.hs.device
     dh = torch.zeros((R, H), dtype=torch.float32, device=dev)
     dz = torch.empty((T, R, H), dtype=torch.float32, device=dev)
-    parts = torch.zeros((ops.rnn_backward_partials(R, H), H), dtype=torch.float32, device=dev)
+    walk = bool(getattr(args, 'backward_walk', 0))
+    parts = torch.zeros(((R + 63) // 64 if walk else ops.rnn_backward_partials(R, H), H), dtype=torch.float32, device=dev)
     cuts = _Cuts(args, rec, T, E, N, dev)
     cuts.carry_in(carry, dh, at_border=True)
     dhead = _dhead_rows(d_out, T)
@@ -1151,12 +1154,14 @@ def _backward_window_rnn(args, net, raw, rec, d_out, acc, carry=None):
     with _heads_grad_beside(args, rec, d_out, acc, T, R, H):
         ops.rnn_backward(raw, T, E, N, H, rec.hs, dhead, rec.snaps, a2, w_heads, dh, dz, parts, h_last=h_last,
                          detach_gap=cuts.gap, row_live=cuts.live_flat, row_keep=cuts.keep_flat, enc_first=True,
-                         enc_window=enc_window, a2_grad=acc['a2_w'], work=acc.setdefault('_work', {}))
+                         enc_window=enc_window, a2_grad=acc['a2_w'], work=acc.setdefault('_work', {}), walk=walk)
         dwt, _ = raw.encode_backward_window_finish(H, want_bias=False) if enc_window else raw.encode_backward_finish(H, want_bias=False)
         acc['wt'].add_(dwt)
         bsum = parts.sum(0)
         acc['a1_b'].add_(bsum)
         acc['a2_b'].add_(bsum)
+    if walk:
+        net.rnn_backward_walks = getattr(net, 'rnn_backward_walks', 0) + 1
     return (dh, dh)
 
 

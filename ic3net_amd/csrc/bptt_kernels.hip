@@ -17,6 +17,8 @@
 //                         encoder's backward stage 1 — three launches per step, no host work between them.
 //   ic3_rnn_tanh_backward_step / ic3_rnn_backward   the IC / IRIC baselines' tanh recurrence: one launch per recorded step
 //                         (rnn_tanh_bwd_kernel), and the loop over a window's steps as one host call.
+//                         ic3_rnn_backward_wide on an ic3_rnn_bptt_walk descriptor: the window's T steps walked in ONE launch
+//                         (rnn_tanh_bwd_walk_kernel: a workgroup walks its 64-row tiles last step to first, dL/dh on chip).
 //   ic3_rnn_weight_grad   ONE launch per window: dA2 += dz^T . (row_live h_prev) over all T x R rows (rnn_wgrad_kernel).
 //   ic3_mlp_backward_step / ic3_mlp_backward   the IC baseline (models.MLP): a window is T x R independent rows, ONE launch over
 //                         all of them (mlp_bwd_kernel), and the window as one host call.
@@ -40,6 +42,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <type_traits>
 #include <vector>
 
 #include "enc_bwd.hpp"
@@ -1187,6 +1190,146 @@ __global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void rnn_tanh_bwd_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// rnn_tanh_bwd_walk_kernel<H>: the T launches of rnn_tanh_bwd_kernel over a window as ONE (ic3_rnn_backward_wide on an
+// ic3_rnn_bptt_walk descriptor).  No row's gradient depends on another row, so the workgroup that owns a 64-row tile walks
+// t = T - 1 .. 0 by itself and finishes the tile's whole window before its next tile: no grid barrier, no flag, nothing that waits for
+// another workgroup.  The tile machine, the phase-0 arithmetic, the product and the scaling are rnn_tanh_bwd_kernel's, element by
+// element; A2 (64 / 128) and W_heads are staged once per launch, not once per step.
+// Where dL/dh lives between the steps: in the Dz TILE — the epilogue writes (dz_t . A2) * row_keep[t - 1] over it from the accumulator
+// layout behind a barrier of its own (every wave is done reading dz_t), the next step's phase 0 reads it back in the (row group,
+// column chunk) layout and writes dz_{t-1} over its own slots.  Three barriers per step instead of two; taken over a second tile of
+// 64 x (H + 4) floats because that tile, at hid 256, leaves no room in 160 KB for the column sums' 16 H floats (153.6 + 16 KB), and
+// one layout serves the three sizes.  dh crosses HBM twice per tile: in from a.dh in front of the tile's first step (into the tile; a
+// detached step reads zeros instead, as the per-step launch takes a null dh_in), out to a.dh behind step 0.
+// Prefetch: the rows of h and dhead of step t - 1 and the row_keep factors of step t are requested in front of step t's product —
+// none depends on dh.  Buffer descriptors per step from 64-bit tile bases (no launch-wide 32-bit limit: R < 2^31, OT <= 16).
+// Bias partials: ONE ROW PER TILE, db_part [tiles][H].  Per step the thread sums over the thread's rows and their sum over the row
+// groups in group order (column_sums' order), added to a running total that STARTS FROM row `tile` — step T - 1 first, the row
+// written once behind step 0: the additions rnn_tanh_bwd_kernel makes to a workgroup's row over the T launches, in their order,
+// whatever the row held (one tile per workgroup there: the same bits).
+// LDS: TanhTile's + 16 H floats (the row groups' sums): 45 KB at 64 (two workgroups per CU), 117 KB at 128, 101 KB at 256 (one).
+// HBM per row and step: h_t in, dz out (2 H floats) + OT (+ one row_keep float).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct RnnWalkArgs {
+    const float* hs;         // [>= T (+1)][R][H]: slot t + 1 = h_t
+    const float* h_last;     // [R][H] or null: h_{T-1} when not slot T
+    const float* dhead;      // [T][R][OT]
+    const float* w_heads;    // [OT][H]
+    const float* a2;         // [H][H]
+    const float* row_keep;   // [T][R] or null
+    float* dh;               // [R][H] in: arriving at step T - 1, out: leaving step 0
+    float* dz;               // [T][R][H] the ring
+    float* db_part;          // [tiles][H], added to
+    int R, OT, tiles, T, detach_gap;
+};
+
+template <int H>
+__global__ __launch_bounds__(4 * H, (H <= 64) ? 2 : 1) void rnn_tanh_bwd_walk_kernel(const RnnWalkArgs a)
+{
+    using Tile = TanhTile<H>;
+    constexpr int NT = Tile::NT, H4 = Tile::H4, LDA4 = Tile::LDA4, RPP = Tile::RPP, PER = Tile::PER;
+    constexpr int SDN = (64 * 16 + NT - 1) / NT;                 // dhead values of a tile per thread, at the widest heads
+    IC3_DYNAMIC_LDS(float, smem);
+    const Tile t(smem);
+    bp_f32x4* const Gs4 = reinterpret_cast<bp_f32x4*>(smem + Tile::SD_AT + 64 * 16);   // [RPP][H4] the row groups' sums of a step
+    const int OT = a.OT, T = a.T;
+    const size_t R = (size_t)a.R;
+    t.stage_weights(a.a2, a.w_heads, OT);
+    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        const long long r0 = (long long)tile * 64;
+        const int rows = (a.R - r0) < 64 ? (int)(a.R - r0) : 64;
+        // (rows past the tile read 0 and their stores are dropped: the ranges of the buffer descriptors)
+        const long long hb = (long long)rows * H * 4;
+        bp_f32x4 hv[PER];
+        float sdv[SDN];
+        auto request = [&](int s) {                              // step s: its rows of h and dhead -> registers
+            const float* h_s = (s + 1 < T || !a.h_last) ? a.hs + (size_t)(s + 1) * R * H : a.h_last;
+            const __amdgpu_buffer_rsrc_t rh = bp_rsrc(h_s + r0 * H, hb);
+            const __amdgpu_buffer_rsrc_t rd = bp_rsrc(a.dhead + ((size_t)s * R + r0) * OT, (long long)rows * OT * 4);
+#pragma unroll
+            for (int i = 0; i < PER; ++i) hv[i] = bp_load4(rh, ((t.rg + RPP * i) * H + 4 * t.c4) * 4);
+#pragma unroll
+            for (int k = 0; k < SDN; ++k) sdv[k] = bp_load1(rd, (t.tid + k * NT) * 4);
+        };
+        request(T - 1);
+        {   // dL/dh arriving at the window's last step -> the thread's own slots of the tile
+            const __amdgpu_buffer_rsrc_t rdi = bp_rsrc(a.dh + r0 * H, hb);
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int row = t.rg + RPP * i;
+                t.Dz4[row * LDA4 + t.c4] = bp_load4(rdi, (row * H + 4 * t.c4) * 4);
+            }
+        }
+        bp_f32x4 total = { 0.f, 0.f, 0.f, 0.f };
+        bp_f32x4* const prow = reinterpret_cast<bp_f32x4*>(a.db_part + (size_t)tile * H) + t.tid;
+        if (t.tid < H4) total = *prow;
+        for (int s = T - 1; s >= 0; --s) {
+            const bool detached = a.detach_gap > 0 && (s + 1) % a.detach_gap == 0;
+#pragma unroll
+            for (int k = 0; k < SDN; ++k)
+                if (t.tid + k * NT < 64 * OT) t.Sd[t.tid + k * NT] = sdv[k];
+            __syncthreads();                                     // the step's d rows; what the epilogue left in the tile (the weights)
+            // ---- phase 0: dz of the tile -> ring, LDS (over the thread's own slots of dL/dh), column sums
+            const __amdgpu_buffer_rsrc_t rz = bp_rsrc(a.dz + ((size_t)s * R + r0) * H, hb);
+            bp_f32x4 bsum = { 0.f, 0.f, 0.f, 0.f };
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int row = t.rg + RPP * i;
+                bp_f32x4 dv = { 0.f, 0.f, 0.f, 0.f };
+                if (!detached) dv = t.Dz4[row * LDA4 + t.c4];
+                const bp_f32x4 v = t.heads_share(dv, row, OT);
+                const bp_f32x4 z = v * (1.0f - hv[i] * hv[i]);
+                {   // (the ROUNDED dz is what is summed, as in the per-step kernel: this add must not be fused with the product above,
+                    //  whatever the code around it invites the compiler to do)
+#pragma clang fp contract(off)
+                    bsum = bsum + z;
+                }
+                t.Dz4[row * LDA4 + t.c4] = z;
+                bp_store4(z, rz, (row * H + 4 * t.c4) * 4);
+            }
+            Gs4[t.rg * H4 + t.c4] = bsum;
+            __syncthreads();
+            // ---- what does not wait for dh: the next step's rows, this step's factors, the step's column sums
+            if (s > 0) request(s - 1);
+            const bool scaled = a.row_keep && s > 0;
+            float kv[16];
+            if (scaled) {
+                const __amdgpu_buffer_rsrc_t rsc = bp_rsrc(a.row_keep + (size_t)(s - 1) * R + r0, (long long)rows * 4);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) kv[reg] = bp_load1(rsc, (32 * t.rb + (reg & 3) + 8 * (reg >> 2) + 4 * t.lh) * 4);
+            }
+            if (t.tid < H4) {
+                bp_f32x4 g = Gs4[t.tid];
+                for (int j = 1; j < RPP; ++j) g += Gs4[j * H4 + t.tid];
+                total = total + g;
+            }
+            // ---- phase 1: (dz . A2) * row_keep[s - 1] -> the tile (the next step's dL/dh), or behind step 0 -> a.dh
+            const bp_f32x16 acc = t.product(a.a2);
+            if (s > 0) {
+                __syncthreads();                                 // every wave is done reading dz_s
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int lr = 32 * t.rb + (reg & 3) + 8 * (reg >> 2) + 4 * t.lh;
+                    float o = acc[reg];
+                    if (scaled) o *= kv[reg];
+                    t.Dz[lr * Tile::LDA + 32 * t.cb + t.li] = o;
+                }
+            } else {
+                const __amdgpu_buffer_rsrc_t rout = bp_rsrc(a.dh + r0 * H, hb);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int lr = 32 * t.rb + (reg & 3) + 8 * (reg >> 2) + 4 * t.lh;
+                    const float o = acc[reg];
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o), rout, (lr * H + 32 * t.cb + t.li) * 4, 0, 0);
+                }
+            }
+        }
+        if (t.tid < H4) *prow = total;
+        __syncthreads();                                         // every wave is done with the tile's LDS
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // ic3_rnn_weight_grad.  dA2[m][n] = sum_q dz[q][m] (row_live[q] h_prev[q][n]) over Q = T x R rows.  Workgroup = K slice of the
 // rows, all H x H outputs; 4 waves as 2 (m) x 2 (n), a wave holds (H / 2) x (H / 2) of the result (MB x MB blocks of 32 x 32).
 // Both operands row-major with q outermost — the K-major pair v_mfma_f32_32x32x2_f32 wants: lane (i, kk) supplies dz[q0 + kk][m(i)]
@@ -1405,12 +1548,32 @@ extern "C" int ic3_rnn_tanh_backward_step_wide(const float* dh_in, const float* 
                                   true);
 }
 
-static int rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream, bool wide)
+// The window's T steps as ONE launch of rnn_tanh_bwd_walk_kernel (an ic3_rnn_bptt_walk descriptor): the tile plan of the per-step
+// launch, one partial row per TILE.
+static int rnn_tanh_backward_walk(const ic3_rnn_bptt_walk* b, long long R, ic3_stream stream)
 {
     using namespace ic3;
-    const char* const fn = wide ? "ic3_rnn_backward_wide" : "ic3_rnn_backward";
+    if (R >= (1ll << 31)) return fail(-22, "ic3_rnn_backward_wide (ic3_rnn_bptt_walk): R < 2^31");
+    const int H = b->H, grid = tanh_partials(R, H, true);
+    const RnnWalkArgs a{ b->hs, b->h_last, b->dhead, b->w_heads, b->a2, b->row_keep, b->dh, b->dz, b->dbias_partials, (int)R, b->OT,
+                         (int)((R + 63) / 64), b->T, b->detach_gap };
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sums = (size_t)16 * H * sizeof(float);          // the row groups' sums of a step, behind the tile machine's LDS
+    return H == 256   ? launch_kernel(rnn_tanh_bwd_walk_kernel<256>, dim3(grid), dim3(1024), TanhTile<256>::LDS_BYTES + sums, s, a)
+           : H == 128 ? launch_kernel(rnn_tanh_bwd_walk_kernel<128>, dim3(grid), dim3(512), TanhTile<128>::LDS_BYTES + sums, s, a)
+                      : launch_kernel(rnn_tanh_bwd_walk_kernel<64>, dim3(grid), dim3(256), TanhTile<64>::LDS_BYTES + sums, s, a);
+}
+
+// B = ic3_rnn_bptt: one launch per step;  B = ic3_rnn_bptt_walk (the _wide entry only): one launch for the T steps — the same checks
+// in front, the same encoder stage and weight gradient behind (both read the dz ring and the record only)
+template <class B>
+static int rnn_backward(ic3_env* env, const B* b, ic3_stream stream, bool wide)
+{
+    using namespace ic3;
+    constexpr bool WALK = std::is_same<B, ic3_rnn_bptt_walk>::value;
+    const char* const fn = WALK ? "ic3_rnn_backward_wide (ic3_rnn_bptt_walk)" : wide ? "ic3_rnn_backward_wide" : "ic3_rnn_backward";
     const std::string f = std::string(fn) + ": ";
-    if (const int rc = window_open(fn, "ic3_rnn_bptt", env, b, wide ? tanh_supported_wide : tanh_supported,
+    if (const int rc = window_open(fn, WALK ? "ic3_rnn_bptt_walk" : "ic3_rnn_bptt", env, b, wide ? tanh_supported_wide : tanh_supported,
                                    (std::string(TANH_SIZES[wide]) + ", a grid whose encoder backward runs in its partial-sums form").c_str(),
                                    false);
         rc < 0)
@@ -1422,24 +1585,33 @@ static int rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream, 
     if (b->enc_window && ic3_env_encode_backward_window_work(env, H) <= 0)
         return fail(-22, f + "enc_window on a configuration without ic3_env_encode_backward_window");
     const long long R = (long long)E * N;
-    int enc_first = b->enc_first;
-    for (int t = T - 1; t >= 0; --t) {
-        // trainer.py:56-60: h_t was handed on detached — the launch reads zeros for dL/dh_t (a null input, no memset)
-        const bool detached = b->detach_gap > 0 && (t + 1) % b->detach_gap == 0;
-        const float* h_t = (t + 1 < T || !b->h_last) ? b->hs + (size_t)(t + 1) * R * H : b->h_last;
-        float* dz = b->dz + (size_t)t * R * H;
-        int rc = rnn_tanh_backward_step(detached ? nullptr : b->dh, h_t, b->dhead + (size_t)t * R * b->OT, b->w_heads, b->OT, b->a2,
-                                        (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R : nullptr, dz, b->dh,
-                                        b->dbias_partials, 1, R, H, stream, wide);
-        if (rc < 0) return rc;
-        if (b->enc_window) continue;                             // (the encoder's first stage: once, behind the loop)
-        rc = ic3_env_encode_backward_accumulate(env, b->snaps + (size_t)t * b->snap_words, dz, H, H, b->enc_work, enc_first, stream);
-        if (rc < 0) return rc;
-        enc_first = 0;
-    }
-    if (b->enc_window) {
-        const int rc = ic3_env_encode_backward_window(env, b->snaps, b->snap_words, T, b->dz, H, R * H, H, b->enc_work, enc_first, stream);
-        if (rc < 0) return rc;
+    if constexpr (WALK) {
+        if (b->reserved) return fail(-22, f + "reserved must be 0");
+        if (const int rc = rnn_tanh_backward_walk(b, R, stream); rc < 0) return rc;
+        if (const int rc = encoder_tail(env, b->snaps, b->snap_words, T, b->dz, H, R * H, H, b->enc_work, b->enc_first, b->enc_window != 0,
+                                        stream);
+            rc < 0)
+            return rc;
+    } else {
+        int enc_first = b->enc_first;
+        for (int t = T - 1; t >= 0; --t) {
+            // trainer.py:56-60: h_t was handed on detached — the launch reads zeros for dL/dh_t (a null input, no memset)
+            const bool detached = b->detach_gap > 0 && (t + 1) % b->detach_gap == 0;
+            const float* h_t = (t + 1 < T || !b->h_last) ? b->hs + (size_t)(t + 1) * R * H : b->h_last;
+            float* dz = b->dz + (size_t)t * R * H;
+            int rc = rnn_tanh_backward_step(detached ? nullptr : b->dh, h_t, b->dhead + (size_t)t * R * b->OT, b->w_heads, b->OT, b->a2,
+                                            (b->row_keep && t > 0) ? b->row_keep + (size_t)(t - 1) * R : nullptr, dz, b->dh,
+                                            b->dbias_partials, 1, R, H, stream, wide);
+            if (rc < 0) return rc;
+            if (b->enc_window) continue;                         // (the encoder's first stage: once, behind the loop)
+            rc = ic3_env_encode_backward_accumulate(env, b->snaps + (size_t)t * b->snap_words, dz, H, H, b->enc_work, enc_first, stream);
+            if (rc < 0) return rc;
+            enc_first = 0;
+        }
+        if (b->enc_window) {
+            const int rc = ic3_env_encode_backward_window(env, b->snaps, b->snap_words, T, b->dz, H, R * H, H, b->enc_work, enc_first, stream);
+            if (rc < 0) return rc;
+        }
     }
     if (b->a2_grad) {
         const int rc = rnn_weight_grad(b->dz, b->hs, b->row_live, (long long)T * R, H, b->a2_grad, 1, b->wgrad_scratch, stream, wide);
@@ -1449,7 +1621,15 @@ static int rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream, 
 }
 
 extern "C" int ic3_rnn_backward(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream) { return rnn_backward(env, b, stream, false); }
-extern "C" int ic3_rnn_backward_wide(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream) { return rnn_backward(env, b, stream, true); }
+extern "C" int ic3_rnn_backward_wide(ic3_env* env, const ic3_rnn_bptt* b, ic3_stream stream)
+{
+    // (by its second word: a tagged descriptor must have the walk struct's size exactly — window_open refuses it otherwise, before
+    //  anything else is read; an untagged one is an ic3_rnn_bptt)
+    static_assert(offsetof(ic3_rnn_bptt_walk, magic) == offsetof(ic3_rnn_bptt, T), "the tag sits where ic3_rnn_bptt holds T");
+    static_assert(sizeof(ic3_rnn_bptt_walk) != sizeof(ic3_rnn_bptt), "the two descriptors are told apart by their sizes too");
+    if (b && (uint32_t)b->T == IC3_RNN_BPTT_WALK_MAGIC) return rnn_backward(env, reinterpret_cast<const ic3_rnn_bptt_walk*>(b), stream, true);
+    return rnn_backward(env, b, stream, true);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // ic3_mlp_backward: the IC baseline (models.py:23-34, models.MLP), every step on its own:

@@ -83,7 +83,13 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  # each (the library's IC3_POLICY_WINDOW_WIDE_PASSES descriptor), and with --window_launch_collection 1 / --auto_reset
                  # its collection windows too.  0 (default): comm_passes launches per step at that width.  Zero-padded twins,
                  # comm_passes > 4, passes_in_launch = False and IRIC's LSTM cell keep their per-step path whatever this says
-                 ('passes_in_launch_wide', int, 0)]
+                 ('passes_in_launch_wide', int, 0),
+                 # 1: the update of IRIC with the tanh recurrence (models.RNN, rnn_type 'MLP'; hid 64 / 128 / 256) walks a recorded
+                 # window's backward through time in ONE launch (bptt._backward_window_rnn on the library's ic3_rnn_bptt_walk
+                 # descriptor: a workgroup walks its 64-row tiles last step to first, dL/dh on chip) — lock-step and collection
+                 # windows, the same parameter gradients bit for bit where a workgroup of the per-step launch owns one tile.
+                 # 0 (default): one launch per recorded step.  Every other policy keeps its path whatever this says
+                 ('backward_walk', int, 0)]
 
 
 def build_parser(argv):

@@ -534,11 +534,13 @@ def rnn_weight_grad(dz, h_prev, dA2, row_live=None, accumulate=True, work=None):
 
 
 def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_partials, h_last=None, detach_gap=0, row_live=None,
-                 row_keep=None, enc_first=True, enc_window=True, a2_grad=None, work=None):
+                 row_keep=None, enc_first=True, enc_window=True, a2_grad=None, work=None, walk=False):
     """ic3_rnn_backward_wide: the backward through a window of T recorded steps of the tanh-recurrence baseline as one host call (one
     launch per step, the encoder's first stage over the dz ring — enc_window — or per step, and with a2_grad affine2's weight
     gradient over the window).  hs (>= T, R, H) the states entering the steps (slot T, or h_last, the state leaving the last one),
-    dhead (T, R, OT), dz (T, R, H) the ring, dbias_partials (rnn_backward_partials(R, H), H) added to."""
+    dhead (T, R, OT), dz (T, R, H) the ring, dbias_partials (rnn_backward_partials(R, H), H) added to.
+    walk: the T steps in ONE launch (an ic3_rnn_bptt_walk descriptor: every 64-row tile walked last step to first by one workgroup,
+    dL/dh on chip) — the same dz, dh and a2_grad bit for bit; dbias_partials (ceil(R / 64), H), one row per tile."""
     _need_cuda(hs, "rnn_backward")
     R = E * N
     assert _f32(hs) and tuple(hs.shape[1:]) == (R, H)
@@ -547,15 +549,15 @@ def rnn_backward(env, T, E, N, H, hs, dhead, snaps, a2, w_heads, dh, dz, dbias_p
     OT = _window_inputs(dhead, snaps, T, R)
     assert _dense(dh, (R, H)) and _dense(dz, (T, R, H))
     assert _dense(a2, (H, H)) and _dense(w_heads, (OT, H))
-    assert _dense(dbias_partials, (rnn_backward_partials(R, H), H))
+    assert _dense(dbias_partials, ((R + 63) // 64 if walk else rnn_backward_partials(R, H), H))
     assert _f32(row_live, (T, R), none_ok=True) and _f32(row_keep, (T, R), none_ok=True)
-    b = _lib.RnnBptt(T, E, N, H, OT, int(detach_gap), int(bool(enc_first)), int(bool(enc_window)))
+    b = (_lib.RnnBpttWalk if walk else _lib.RnnBptt)(T, E, N, H, OT, int(detach_gap), int(bool(enc_first)), int(bool(enc_window)))
     _set_ptrs(b, dict(hs=hs, dhead=dhead, snaps=snaps, a2=a2, w_heads=w_heads, dh=dh, dz=dz, dbias_partials=dbias_partials),
               h_last=h_last, row_live=row_live, row_keep=row_keep)
     b.snap_words = snaps.stride(0)
     b.enc_work = _enc_work(env, H, enc_window)
     scratch = _a2_grad_fill(b, a2_grad, work, T * R, H, hs.device)       # (`scratch`: alive until the call has returned)
-    check(_lib.lib().ic3_rnn_backward_wide(env._h, C.byref(b), stream()))
+    check(_lib.lib().ic3_rnn_backward_wide(env._h, C.byref(b), stream()))      # (its magic says which descriptor this is)
 
 
 def mlp_backward_supported(env, H):

@@ -631,6 +631,47 @@ size_t ic3_rnn_weight_grad_wide_scratch_floats(long long Q, int H);
 int ic3_rnn_weight_grad_wide(const float* dz, const float* h_prev, const float* row_live /* or NULL */, long long Q, int H, float* dA2,
                              int accumulate, float* scratch, ic3_stream stream);
 
+/* The same window with its T steps WALKED IN ONE LAUNCH — ic3_rnn_backward_wide handed the descriptor below in place of an
+ * ic3_rnn_bptt.  The descriptor is selected by its second word, magic = IC3_RNN_BPTT_WALK_MAGIC (where an ic3_rnn_bptt holds T), AND
+ * struct_size = sizeof(ic3_rnn_bptt_walk): a tagged descriptor of another size is refused with -EINVAL before anything else is read,
+ * an untagged one is an ic3_rnn_bptt and behaves as above.  (ABI 601 is closed: a descriptor, not a symbol.  ic3_rnn_backward, the
+ * 64 / 128 entry, does not know the tag: it answers -EINVAL on the size.)  Error messages begin "ic3_rnn_backward_wide
+ * (ic3_rnn_bptt_walk)".  No row's gradient depends on another row, so the workgroup that owns a 64-row tile walks t = T - 1 .. 0 by
+ * itself with dL/dh kept on chip (no grid-wide barrier, no wait between workgroups): per step the arithmetic of the per-step launch,
+ * element by element — dz, dh and a2_grad are the per-step call's bits.  affine2.weight is staged once per launch, dh crosses memory
+ * twice per tile (in at the window's last step, out behind its first), the rows of h and dhead of step t - 1 are requested in front
+ * of step t's product.  Behind the launch: the encoder's first stage (enc_window, or per step over the ring's slots, last step first)
+ * and, with a2_grad, ic3_rnn_weight_grad_wide over the window, as the per-step call issues them.
+ *   The fields: as ic3_rnn_bptt, EXCEPT dbias_partials [ceil(R / 64)][H] — one row per 64-row TILE (not per workgroup; no query of its
+ *   own), row p ADDED to with tile p's column sums over the T steps: the steps' sums are added to the row's value last step first and
+ *   the row is written once — the additions the per-step call makes to a workgroup's row, in their order, so where that call runs one
+ *   tile per workgroup (ic3_rnn_backward_wide_partials(R, H) == ceil(R / 64)) row p is its row p bit for bit.  reserved: 0.
+ * Runs where ic3_rnn_backward_wide_supported(env, H) answers 1 (else -ENOSYS); R < 2^31, OT <= 16; -EINVAL before the launch as
+ * ic3_rnn_backward_wide (nothing is written).  No float atomics: identical run to run.  One stream. */
+#define IC3_RNN_BPTT_WALK_MAGIC 0x4b4c4157u /* "WALK" */
+typedef struct ic3_rnn_bptt_walk {
+    uint32_t struct_size;   /* sizeof(ic3_rnn_bptt_walk) of the caller's header (checked with the tag: -EINVAL on mismatch) */
+    uint32_t magic;         /* IC3_RNN_BPTT_WALK_MAGIC */
+    int32_t T, E, N, H, OT;
+    int32_t detach_gap, enc_first, enc_window;
+    const float* hs;
+    const float* h_last;
+    const float* dhead;
+    const int32_t* snaps;
+    int64_t snap_words;
+    const float* a2;
+    const float* w_heads;
+    const float* row_live;
+    const float* row_keep;
+    float* dh;
+    float* dz;
+    float* dbias_partials;  /* [ceil(R / 64)][H]: one row per tile */
+    float* enc_work;
+    float* a2_grad;
+    float* wgrad_scratch;
+    int64_t reserved;       /* 0 (keeps sizeof apart from ic3_rnn_bptt's) */
+} ic3_rnn_bptt_walk;
+
 /* The backward through a window of T recorded steps of the IC baseline (models.py:23-34, models.MLP: e = affine1(obs),
  * x1 = tanh(e), h = tanh(affine2(x1) + x1), heads and value on h) as ONE host call.  No state crosses a step, so the window is
  * Q = T x R independent rows: T x ic3_env_encode_at (e of every snapshot into the slots of the x1 ring), then ONE launch over all

@@ -10,7 +10,8 @@ many windows went through it: the LSTM policies' ic3_policy_window, and the ic3_
 pp_hard_iric_tanh); WINDOW_LAUNCH_COLLECTION=1 sets args.window_launch_collection beside it: the windows of collection mode (argument 7
 = 1) too; WINDOW_LAUNCH_WIDE=1 sets args.window_launch_wide beside WINDOW_LAUNCH: the windows of a hid-256 policy too;
 PASSES_IN_LAUNCH_WIDE=1 sets args.passes_in_launch_wide: a hid-256 policy with COMM_PASSES 2..4 runs each step as one launch (and, with
-the three window switches, its windows as one launch each).  ROLLOUT_ONLY=1 times the rollout half of the timed updates by itself
+the three window switches, its windows as one launch each).  BACKWARD_WALK=1 sets args.backward_walk: the backward through time of
+pp_hard_iric_tanh as one launch per window (the line says how many windows went through it).  ROLLOUT_ONLY=1 times the rollout half of the timed updates by itself
 (Trainer.run_batch between two synchronisations) and prints its time per step.  HID=<H> overrides
 the workload's hid_size (HID=256: the hid-128 workloads at the width of pp_scaled).  BATCH_WINDOWS=<k>: an update of k windows of max_steps steps (default 1; in collection mode the first starts the streams and
 the others continue them)."""
@@ -46,6 +47,7 @@ def main():
     a.window_launch_collection = int(os.environ.get('WINDOW_LAUNCH_COLLECTION', '0'))
     a.window_launch_wide = int(os.environ.get('WINDOW_LAUNCH_WIDE', '0'))
     a.passes_in_launch_wide = int(os.environ.get('PASSES_IN_LAUNCH_WIDE', '0'))
+    a.backward_walk = int(os.environ.get('BACKWARD_WALK', '0'))
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
@@ -101,7 +103,8 @@ def main():
     label = wl + (" hid=%d" % a.hid_size if shape else "") + passes + (" (obs rows assembled in the rollout)" if a.train_dense_obs else "") + ("" if split else " (fp32 MFMA gate product)") + \
         (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "") + \
         (" (window_launch: %d windows in one launch each)" % getattr(knet, 'window_launches', 0) if a.window_launch else "") + \
-        (" (passes_in_launch_wide)" if a.passes_in_launch_wide else "")
+        (" (passes_in_launch_wide)" if a.passes_in_launch_wide else "") + \
+        (" (backward_walk: %d windows walked in one launch each)" % getattr(tr.policy_net, 'rnn_backward_walks', 0) if a.backward_walk else "")
     print("train_batch [%s] %s E=%d: %.0f env-steps/s = %.2f M agent-steps/s (%.2f s per update of %d env-steps), "
           "peak mem %.1f GB, gemm %s" % (mode, label, E, steps / dt, a.nagents * steps / dt / 1e6, dt / updates,
                                          steps // updates, torch.cuda.max_memory_allocated() / 2 ** 30,
