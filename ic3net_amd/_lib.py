@@ -133,6 +133,22 @@ class BpttPasses(_SizedStruct):
         self.magic = self.MAGIC
 
 
+class BpttWalk(_SizedStruct):
+    """ic3_bptt_walk (include/ic3_rollout.h): a comm_zero window of a Bptt with its T steps walked in ONE launch; handed to
+    ic3_bptt_backward in place of a Bptt (magic selects this form).  max_workgroups: 0 = the library's plan, > 0 caps the grid."""
+    MAGIC = 0x4b4c574c                         # IC3_BPTT_WALK_MAGIC: the word that selects this form (an ic3_bptt holds T there)
+    _fields_ = [("struct_size", C.c_uint32), ("magic", C.c_uint32)] + \
+               [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "detach_gap", "enc_first", "max_workgroups")] + \
+               [("gates", C.c_void_p), ("hs", C.c_void_p), ("cs", C.c_void_p), ("dhead", C.c_void_p), ("snaps", C.c_void_p),
+                ("snap_words", C.c_int64), ("row_live", C.c_void_p), ("row_keep", C.c_void_p), ("lstm_wp3_bwd", C.c_void_p),
+                ("w_heads", C.c_void_p), ("dh", C.c_void_p), ("dc", C.c_void_p), ("dxh", C.c_void_p), ("dxh_step", C.c_int64),
+                ("dbias_partials", C.c_void_p), ("enc_work", C.c_void_p)]
+
+    def __init__(self, *a, **kw):             # positional arguments start at T
+        super().__init__(*((self.MAGIC,) + a if a else a), **kw)
+        self.magic = self.MAGIC
+
+
 class RnnBptt(_SizedStruct):
     """ic3_rnn_bptt (include/ic3_rollout.h): one window of the tanh-recurrence baseline's backward through time."""
     _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("T", "E", "N", "H", "OT", "detach_gap", "enc_first",

@@ -456,6 +456,14 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
     bias_parts = zeros((R + 63) // 64, 4 * H)
     # two chains of launches (envs [0, E1) and [E1, E) on two streams): one fills the ragged last round of the other's launches
     two = ring and bool(getattr(args, 'bptt_two_chains', True)) and ops.first_chain_envs(E, N) < E
+    # args.backward_walk_lstm: a window without communication (IRIC's LSTM cell on its stand-in, --comm_mask_zero) with the ring — its
+    # 2 T launches (gate launch + the copy of d h_prev, per step and chain) as ONE (an ic3_bptt_walk descriptor: every 64-row tile
+    # walked last step to first by one workgroup, dL/dh on chip), one stream, the same gradients bit for bit.  Not under bench's
+    # per-gate events (raw.gate_timer): they have no meaning in one launch
+    gate_timer = getattr(raw, 'gate_timer', None)
+    walk = bool(getattr(args, 'backward_walk_lstm', 0)) and mask_zero and ring and gate_timer is None
+    if walk:
+        two = False
     dcw_parts = None if mask_zero else zeros(ops.bptt_dcw_partials(E, N, two), H, H)
     cuts = _Cuts(args, rec, T, E, N, dev)
     cuts.carry_in(carry, dh_rec, dc_rec, at_border=True)
@@ -466,8 +474,8 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
                           None if mask_zero else net.C_modules[0].weight.detach(), dh_rec, dc_rec, dxh, bias_parts, dcw_parts,
                           mode_avg=mode_avg, comm_zero=mask_zero, detach_gap=cuts.gap, row_live=cuts.live_flat,
                           row_keep=cuts.keep_flat, enc_first=True,
-                          gate_events=getattr(raw, 'gate_timer', None),     # (bench.py --mode train: HIP events around the gate launches)
-                          two_chains=two)
+                          gate_events=gate_timer,     # (bench.py --mode train: HIP events around the gate launches)
+                          two_chains=two, walk=walk)
         if H == 256 and not bool(getattr(args, 'lstm_wgrad_kernel', True)):
             _weight_grad_products(rec, T, R, H, acc['w_cat_t'], cuts.live_flat)
         else:
@@ -480,6 +488,8 @@ def _backward_window_native(args, net, raw, rec, d_out, acc, carry, fc):
         acc['b_cat'].add_(bias_parts.sum(0))
         if not mask_zero:
             acc['c_w'].add_(dcw_parts.sum(0))
+    if walk:
+        net.lstm_backward_walks = getattr(net, 'lstm_backward_walks', 0) + 1
     return (dh_rec, dc_rec)
 
 
@@ -1094,7 +1104,11 @@ def _backward_episode_standin(net, si, raw, rec, d_out, acc, carry=None):
     acc2 = acc.get('_standin')
     if acc2 is None:
         acc2 = acc['_standin'] = new_accumulators(si)
-    return backward_episode(si.args, si, raw, rec, d_out, acc2, carry=carry)
+    walks = getattr(si, 'lstm_backward_walks', 0)
+    out = backward_episode(si.args, si, raw, rec, d_out, acc2, carry=carry)
+    # (args.backward_walk_lstm: the windows walked in one launch are counted on the policy the trainer holds)
+    net.lstm_backward_walks = getattr(net, 'lstm_backward_walks', 0) + getattr(si, 'lstm_backward_walks', 0) - walks
+    return out
 
 
 def fold_standin(acc):

@@ -15,6 +15,8 @@
 //   ic3_bptt_backward     the loop over a window's steps, last to first, as ONE host call: cell derivative + input gradient
 //                         (ic3_lstm_gates_backward_given, the heads' share of dL/dh folded in) -> ic3_comm_backward -> the sparse
 //                         encoder's backward stage 1 — three launches per step, no host work between them.
+//                         On an ic3_bptt_walk descriptor: a comm_zero window's T steps walked in ONE launch
+//                         (lstm_gates_bwd_walk_kernel, gates_bwd.hip: dL/dh on chip, no communication to wait for).
 //   ic3_rnn_tanh_backward_step / ic3_rnn_backward   the IC / IRIC baselines' tanh recurrence: one launch per recorded step
 //                         (rnn_tanh_bwd_kernel), and the loop over a window's steps as one host call.
 //                         ic3_rnn_backward_wide on an ic3_rnn_bptt_walk descriptor: the window's T steps walked in ONE launch
@@ -885,6 +887,36 @@ static int bptt_passes_backward(ic3_env* env, const ic3_bptt_passes* b, ic3_stre
     return 0;
 }
 
+// ---- ic3_bptt_backward on an ic3_bptt_walk descriptor -------------------------------------------------
+// A comm_zero window (IRIC's LSTM cell on its stand-in, --comm_mask_zero policies): the 2 T launches of the loop below — gate launch,
+// then the copy of the d h_prev half — as ONE launch of lstm_gates_bwd_walk_kernel (gates_bwd.hip), then the encoder's window stage
+// over the ring exactly as the loop issues it.  One stream.  Everything that could refuse is asked before the launch.
+static int bptt_walk_backward(ic3_env* env, const ic3_bptt_walk* b, ic3_stream stream)
+{
+    using namespace ic3;
+    const char* const fn = "ic3_bptt_backward (ic3_bptt_walk)";
+    const std::string f = std::string(fn) + ": ";
+    if (const int rc = window_open(fn, "ic3_bptt_walk", env, b, ic3_bptt_backward_supported,
+                                   "hid_size 64 / 128 / 256, <= 64 agents, a grid whose encoder backward runs in its partial-sums form",
+                                   false);
+        rc < 0)
+        return rc;
+    if (!b->gates || !b->hs || !b->cs || !b->dhead || !b->snaps || !b->lstm_wp3_bwd || !b->w_heads || !b->dh || !b->dc || !b->dxh ||
+        !b->dbias_partials || !b->enc_work)
+        return fail(-22, f + "null argument");
+    const long long R = (long long)b->E * b->N;
+    if (b->dxh_step < R * 2 * b->H || ic3_env_encode_backward_window_work(env, b->H) <= 0)
+        return fail(-22, f + "dxh_step >= E * N * 2 * hid_size, on a configuration with ic3_env_encode_backward_window (the walk needs "
+                             "the ring)");
+    if (b->detach_gap > 0 && b->row_keep)
+        return fail(-22, f + "detach_gap > 0 with row_keep (a detached step has no dc for row_keep to scale: lock-step windows carry "
+                             "detach_gap, collection-mode windows row_live / row_keep)");
+    if (R >= (1ll << 31) || b->max_workgroups < 0) return fail(-22, f + "R < 2^31, max_workgroups >= 0");
+    if (const int rc = lstm_gates_backward_walk(b, stream); rc < 0) return rc;
+    return ic3_env_encode_backward_window(env, b->snaps, b->snap_words, b->T, b->dxh, 2 * b->H, b->dxh_step, b->H, b->enc_work,
+                                          b->enc_first, stream);
+}
+
 // envs [0, E1) run on the caller's stream, [E1, E) on the library's second stream (ic3_bptt.two_chains): E1 * N a multiple of 64,
 // so that the gate launch's row tiles — and with them its bias partials — do not straddle the border
 extern "C" int ic3_bptt_first_chain_envs(int E, int N)
@@ -901,6 +933,11 @@ extern "C" int ic3_bptt_backward(ic3_env* env, const ic3_bptt* b, ic3_stream str
     static_assert(offsetof(ic3_bptt_passes, magic) == offsetof(ic3_bptt, T), "the tag sits where ic3_bptt holds T");
     if (b && (uint32_t)b->T == IC3_BPTT_PASSES_MAGIC)
         return bptt_passes_backward(env, reinterpret_cast<const ic3_bptt_passes*>(b), stream);
+    // (likewise the walk of a comm_zero window: its own tag, and a size that neither of the other two descriptors has)
+    static_assert(offsetof(ic3_bptt_walk, magic) == offsetof(ic3_bptt, T), "the tag sits where ic3_bptt holds T");
+    static_assert(sizeof(ic3_bptt_walk) != sizeof(ic3_bptt) && sizeof(ic3_bptt_walk) != sizeof(ic3_bptt_passes),
+                  "the descriptors are told apart by their sizes too");
+    if (b && (uint32_t)b->T == IC3_BPTT_WALK_MAGIC) return bptt_walk_backward(env, reinterpret_cast<const ic3_bptt_walk*>(b), stream);
     if (const int rc = window_open("ic3_bptt_backward", "ic3_bptt", env, b, ic3_bptt_backward_supported,
                                    "hid_size 64 / 128 / 256, <= 64 agents, a grid whose encoder backward runs in its partial-sums form",
                                    false);

@@ -17,6 +17,8 @@
 // buffer descriptors' range check (their gradient is exactly 0) and their stores are dropped by it.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "ic3_common.hpp"
 
 namespace ic3 {
@@ -466,9 +468,339 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void lstm_gates_bwd_kern
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// lstm_gates_bwd_walk_kernel<H>: a comm_zero window of ic3_bptt_backward (IRIC's LSTM cell, --comm_mask_zero policies) with its T
+// steps WALKED IN ONE LAUNCH (an ic3_bptt_walk descriptor).  Without communication no row's gradient depends on another row, so
+// the workgroup that owns a 64-row tile walks s = T - 1 .. 0 by itself and finishes the tile's whole window before its next tile
+// (tile = blockIdx.x; tile += gridDim.x): no grid barrier, no flag, no atomics, nothing that waits for another workgroup.  Per step
+// the body of lstm_gates_bwd_kernel<H, 1, 1> with the input gradient, element by element in its order — the same 2 H threads, the
+// same LDS tile (the bias slots hold 64 row factors instead), the same occupancy — so the per-step call's bits.
+//   dL/dh between the steps stays ON CHIP: behind the second K half (one barrier: every wave is done with the A tile) the waves
+//     that hold the d h_prev columns of the product write them, times row_keep[s - 1] (dh_copy_kernel's factor; none behind step
+//     0), into columns [0, H) of the A tile; the barrier at the top of the next step makes them (and the step's dhead rows)
+//     visible, and the epilogue reads its own (row, column) elements there.  Five barriers per step for the per-step kernel's
+//     four.  dh crosses memory twice per tile: in from a.dh in front of step T - 1 (into the tile), out behind step 0.
+//   dL/dc goes THROUGH a.dc: the lane that writes dc_prev of (row, column) is the lane that reads it one step later, so there is
+//     no barrier; the wait for the wave's vector-memory operations in front of the step's last barrier puts the stores behind it.
+//     (32 registers per lane would hold it, but the per-step kernel already sits at the 256 registers two waves per SIMD allow,
+//     with 7 spilled: the 32 would all go to scratch inside the step loop.)  It leaves the window in a.dc as the per-step call's.
+//   A detach point, (s + 1) % detach_gap == 0: the step sees zeros for dh and dc (the per-step call passes null pointers there).
+//   The d inp half of the product goes to ring slot s; the d h_prev half of a slot is NOT written (the encoder's window stage
+//     reads the d inp columns only): H floats per row and step less.
+//   Bias partials: row `tile` is read in front of the tile's first step, per step the per-step kernel's own sum from zero and its
+//     lane-half shuffle, then one add to the running row, the row written once behind step 0 — the additions the T per-step
+//     launches make with accumulate = 1, in their order.
+//   Prefetch: step s - 1's dhead values and its row_live / row_keep factors (one per row of the tile) are requested in front of
+//     step s's product and staged in LDS, the factors as ones where the window has none (a product with 1 is exact: no branch per
+//     element, and none of the per-step kernel's 64 factor loads per lane); w_heads sits in registers for the launch.  Buffer
+//     descriptors per step from 64-bit tile bases (R < 2^31, OT <= 16).
+//   Roundings: the per-step kernel's, pinned where the compiler would choose (see the cell's derivative below) — checked bit for
+//     bit against the per-step call on the host build and on the GPU (tests/test_host_lstm_walk_cpu.py, tests/test_lstm_walk_gpu.py).
+// HBM per row and step: 4H gates, H c_prev, H dc in; 4H dgates, H dc, H d inp out = 12 H floats (+ OT) for the per-step pair's 16 H.
+struct GatesWalkArgs {
+    float* gates;            // [T][R][4H] in: the recorded activated gates, out: dgates
+    const float* cs;         // [>= T][R][H] c entering every step
+    const float* dhead;      // [T][R][OT]
+    const float* w_heads;    // [OT][H]
+    const float* row_live;   // [T][R] or null
+    const float* row_keep;   // [T][R] or null
+    const void* wb3;         // ic3_policy_pack_split_bwd's planes
+    float* dh;               // [R][H] in: arriving at step T - 1, out: leaving step 0
+    float* dc;               // [R][H] likewise (and where dL/dc crosses from step to step)
+    float* dxh;              // the ring: slot s at dxh + s * dxh_step, rows of 2H, the d inp half written
+    long long dxh_step;
+    float* dbias;            // [tiles][4H], added to
+    int R, OT, tiles, T, detach_gap;
+};
+
+template <int H>
+__global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void lstm_gates_bwd_walk_kernel(const GatesWalkArgs a)
+{
+    constexpr int K = 2 * H, LDA = K + 4, LDA4 = LDA / 4, NT = 2 * H, SDN = 64 * 16 / NT;
+    constexpr int KB16B = 4 * H / 16, NCT = 2 * H / 32, KBH = K / 16;
+    IC3_DYNAMIC_LDS(float, smem);
+    float* const As = smem;                                      // [64][LDA]
+    gb_f32x4* const As4 = reinterpret_cast<gb_f32x4*>(smem);
+    // (of the per-step kernel's [4H] bias slots) the row factors of the tile's 64 rows, 1 where the window has none — a product with
+    // 1 is exact, so the factors are applied without a branch per element:
+    float* const skp = As + 64 * LDA;                            // [64] row_keep: of step s for its dc, from the middle of step s on of
+                                                                 //      step s - 1 (what step s hands back; step s - 1's dc)
+    float* const slv = skp + 64;                                 // [64] row_live of step s
+    float* const sdh = skp + 4 * H;                              // [64][16] the step's dhead rows, zero beyond OT
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
+    const int col = 32 * w + li;
+    const int OT = a.OT, T = a.T;
+    const size_t R = (size_t)a.R;
+    const int voff = (4 * lh * H + col) * 4;
+    const int wu =__builtin_amdgcn_readfirstlane(w);            // (scalar offset: no waterfall loop around each load)
+    const bool hw = 64 * wu >= H;                                // (uniform) this wave's columns of the product are d h_prev's
+    float wh[16];                                                // w_heads[o][col] of this lane's hidden column, for the launch
+    {
+        const __amdgpu_buffer_rsrc_t rwh = gb_rsrc(a.w_heads, (long long)OT * H * 4);
+#pragma unroll
+        for (int o = 0; o < 16; ++o) wh[o] = gb_load1(rwh, (o * H + col) * 4, 0);         // (o >= OT: out of range, 0)
+    }
+    const __amdgpu_buffer_rsrc_t rwb = gb_rsrc(a.wb3, (long long)3 * 4 * H * 2 * H * 2);
+    auto wb = [&](int pl, int kg, int ct) __attribute__((always_inline)) {
+        return __builtin_amdgcn_raw_buffer_load_b128(rwb, lane * 16, ((pl * KB16B + kg) * NCT + 2 * wu + ct) * 1024, 0);
+    };
+    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        const long long r0 = (long long)tile * 64;
+        const int rows = (int)((a.R - r0) < 64 ? (a.R - r0) : 64);
+        // (rows past R read as zeros through the descriptors' range check — their gradient is exactly 0 — and their stores are dropped)
+        const long long nrec = (long long)rows * H * 4;
+        const __amdgpu_buffer_rsrc_t rdh = gb_rsrc(a.dh + r0 * H, nrec);
+        const __amdgpu_buffer_rsrc_t rdp = gb_rsrc(a.dc + r0 * H, nrec);
+        float sdv[SDN], lreg = 1.0f, kreg = 1.0f;
+        // a row factor of step s (`f` = row_live / row_keep, or null: ones) for row `tid` of the tile; rows past R: 0
+        auto factor = [&](const float* f, int s) __attribute__((always_inline)) {
+            return f ? gb_load1(gb_rsrc(f + ((size_t)s * R + r0), (long long)rows * 4), tid * 4, 0) : 1.0f;
+        };
+        auto request = [&](int s) __attribute__((always_inline)) {       // step s: the tile's dhead rows and row_live -> registers
+            const __amdgpu_buffer_rsrc_t rdd = gb_rsrc(a.dhead + ((size_t)s * R + r0) * OT, (long long)rows * OT * 4);
+#pragma unroll
+            for (int k = 0; k < SDN; ++k) {
+                const int idx = tid + k * NT, row = idx >> 4, o = idx & 15;
+                sdv[k] = o < OT ? gb_load1(rdd, (row * OT + o) * 4, 0) : 0.0f;
+            }
+            if (tid < 64) lreg = factor(a.row_live, s);
+        };
+        request(T - 1);
+        if (tid < 64) skp[tid] = factor(a.row_keep, T - 1);
+        // dL/dh arriving at the window's last step -> the lane's own slots of the tile (behind the last barrier of the tile in
+        // front: every wave is done with the A tile and the factors)
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int lc = 32 * rt + (reg & 3) + 8 * (reg >> 2);
+                As[(lc + 4 * lh) * LDA + col] = gb_load1(rdh, voff, lc * H * 4);
+            }
+        float ti = 0.f, tf = 0.f, tg = 0.f, to = 0.f;            // the tile's running partial row
+        float* const prow = a.dbias + (size_t)tile * 4 * H + col;
+        if (lh == 0) ti = prow[0], tf = prow[H], tg = prow[2 * H], to = prow[3 * H];
+#pragma unroll 1
+        for (int s = T - 1; s >= 0; --s) {
+            const bool detached = a.detach_gap > 0 && (s + 1) % a.detach_gap == 0;
+            // (the lane's coordinates once more, opaque to the optimiser: the step's few hundred LDS addresses and buffer offsets are
+            //  then formed where they are used, as in the per-step kernel — hoisted out of the step loop they do not fit the
+            //  registers and every one comes back from scratch)
+            int tq = threadIdx.x;
+            IC3_OPAQUE_VGPR(tq);
+            const int tid = tq, lane = tid & 63, li = lane & 31, lh = lane >> 5, col = 32 * (tid >> 6) + li;
+            const int voff = (4 * lh * H + col) * 4, goff = (4 * lh * 4 * H + col) * 4;
+#pragma unroll
+            for (int k = 0; k < SDN; ++k) sdh[tid + k * NT] = sdv[k];
+            if (tid < 64) slv[tid] = lreg;
+            __syncthreads();                                     // the step's dhead rows and factors; what the step behind left in the tile
+            const size_t q0 = (size_t)s * R + r0;                // the tile's first row of step s
+            const __amdgpu_buffer_rsrc_t rc = gb_rsrc(a.cs + q0 * H, nrec);
+            // (a detach point: every dc load reads 0 through an empty descriptor, as the per-step launch's null dc)
+            const __amdgpu_buffer_rsrc_t rdc = gb_rsrc(a.dc + r0 * H, detached ? 0 : nrec);
+            const __amdgpu_buffer_rsrc_t rdg = gb_rsrc(a.gates + q0 * 4 * H, 4 * nrec);
+            float keep_g[2][16], keep_o[2][16];
+            float si = 0.f, sf = 0.f, sg = 0.f, so = 0.f;
+            // ---- the cell's derivative: lstm_gates_bwd_kernel<H, 1, 1>'s epilogue, verbatim but for where dh / dc come from
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                float dhv[16], dcv[16], cold[16], gin[4][16];
+                __builtin_amdgcn_sched_barrier(0);               // (one row tile's 96 requests at a time, not both tiles' at once)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int lc = 32 * rt + (reg & 3) + 8 * (reg >> 2);
+                    const float dh_tile = As[(lc + 4 * lh) * LDA + col];
+                    dhv[reg] = detached ? 0.0f : dh_tile;
+                    dcv[reg] = gb_load1(rdc, voff, lc * H * 4);
+                    cold[reg] = gb_load1(rc, voff, lc * H * 4);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gin[k][reg] = gb_load1(rdg, goff, lc * 4 * H * 4 + k * H * 4);
+                }
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int lc = 32 * rt + (reg & 3) + 8 * (reg >> 2);
+                    const float i = gin[0][reg], f = gin[1][reg], gt = gin[2][reg], o = gin[3][reg];
+                    {                                                // dL/dh_s += dhead[row] . w_heads[:, col]
+                        const gb_f32x4* dr = reinterpret_cast<const gb_f32x4*>(sdh + (lc + 4 * lh) * 16);   // (a broadcast read)
+                        float s_ = dhv[reg];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            if (4 * q >= a.OT) break;
+                            const gb_f32x4 dv = dr[q];
+                            s_ = __builtin_fmaf(dv[0], wh[4 * q], s_);
+                            s_ = __builtin_fmaf(dv[1], wh[4 * q + 1], s_);
+                            s_ = __builtin_fmaf(dv[2], wh[4 * q + 2], s_);
+                            s_ = __builtin_fmaf(dv[3], wh[4 * q + 3], s_);
+                        }
+                        dhv[reg] = s_;
+                    }
+                    {   // collection mode: the slot's per-row cuts (ones otherwise).  The per-step kernel multiplies behind a branch,
+                        // so its products stand alone: these must not be fused into the sums that follow either
+                        const int lrow = lc + 4 * lh;
+                        float cl = cold[reg] * slv[lrow], dk = dcv[reg] * skp[lrow];
+                        IC3_OPAQUE_VGPR(cl);
+                        IC3_OPAQUE_VGPR(dk);
+                        cold[reg] = cl;
+                        dcv[reg] = dk;
+                    }
+                    const float c0 = cold[reg];
+                    float tc, dct, di, df, dg, dO, dcp;
+                    {   // The per-step kernel's roundings, pinned: of its expressions the compiler fuses ONE there, the sum in dct
+                        // (v_fma_f32 of dh o, 1 - tc^2 and dc; 1 - tc^2 itself is a product and a v_sub_f32).  Left to itself it
+                        // pairs these sums across elements inside the step loop (v_pk_add_f32) and fuses only some of them.
+#pragma clang fp contract(off)
+                        tc = fast_tanh(__builtin_fmaf(f, c0, i * gt));   // (the forward's own rounding: policy_step.hip's cell)
+#if defined(__HIP_DEVICE_COMPILE__)
+                        dct = __builtin_fmaf(dhv[reg] * o, 1.0f - tc * tc, dcv[reg]);
+#else
+                        dct = dcv[reg] + dhv[reg] * o * (1.0f - tc * tc);        // (the sources compiled for a CPU: nothing is fused)
+#endif
+                        di = dct * gt * i * (1.0f - i), df = dct * c0 * f * (1.0f - f);
+                        dg = dct * i * (1.0f - gt * gt), dO = dhv[reg] * tc * o * (1.0f - o);
+                        dcp = dct * f;
+                        si += di;
+                        sf += df;
+                        sg += dg;
+                        so += dO;
+                    }
+                    gb_store1(di, rdg, goff, lc * 4 * H * 4);
+                    gb_store1(df, rdg, goff, lc * 4 * H * 4 + H * 4);
+                    gb_store1(dg, rdg, goff, lc * 4 * H * 4 + 2 * H * 4);
+                    gb_store1(dO, rdg, goff, lc * 4 * H * 4 + 3 * H * 4);
+                    gb_store1(dcp, rdp, voff, lc * H * 4);
+                    {                                                // K-half 0 of dgates (gates i, f) -> the A tile; g, o wait in registers
+                        const int lr = lc + 4 * lh;
+                        As[lr * LDA + col] = di;
+                        As[lr * LDA + H + col] = df;
+                        keep_g[rt][reg] = dg;
+                        keep_o[rt][reg] = dO;
+                    }
+                }
+            }
+            // ---- the step's column sums (the per-step kernel's, from zero), then ONE add each to the running row
+            si += __shfl_xor(si, 32);
+            sf += __shfl_xor(sf, 32);
+            sg += __shfl_xor(sg, 32);
+            so += __shfl_xor(so, 32);
+            if (lh == 0) {
+                ti += si;
+                tf += sf;
+                tg += sg;
+                to += so;
+            }
+            // ---- what does not wait for the product: the next step's dhead rows, the factors of what this step hands back
+            if (s > 0) {
+                request(s - 1);
+                if (tid < 64) kreg = factor(a.row_keep, s - 1);
+            }
+            // ---- [d inp | d h_prev] = dgates . [W_ih | W_hh]: the per-step kernel's product, its two K halves through the A tile
+            gb_u32x4 bq2[3][2];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) bq2[pl][ct] = wb(pl, 0, ct);
+            gb_f32x16 acc[2][2];
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) acc[rt][ct][i] = 0.0f;
+            auto blockdx = [&](int kb, int kg) __attribute__((always_inline)) {
+                gb_u32x4 ap[2][3];
+                const gb_f32x4* s0 = As4 + li * LDA4 + 4 * kb + 2 * lh;
+                const gb_f32x4* s1 = As4 + (32 + li) * LDA4 + 4 * kb + 2 * lh;
+                gb_split_frag(s0[0], s0[1], ap[0]);
+                gb_split_frag(s1[0], s1[1], ap[1]);
+#pragma unroll
+                for (int pb = 0; pb < 3; ++pb)
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+                        for (int pa = 2; pa >= 0; --pa) {
+                            gb_mfma_bf16(acc[0][ct], ap[0][pa], bq2[pb][ct]);
+                            gb_mfma_bf16(acc[1][ct], ap[1][pa], bq2[pb][ct]);
+                        }
+                        if (kg + 1 < KB16B) bq2[pb][ct] = wb(pb, kg + 1, ct);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+            };
+            __syncthreads();                                     // d i, d f of every wave are in the A tile
+#pragma unroll 1
+            for (int kb = 0; kb < KBH; ++kb) blockdx(kb, kb);
+            if (s > 0 && tid < 64) skp[tid] = kreg;              // (every wave is done with row_keep[s]: its epilogue is behind it)
+            __syncthreads();                                     // every wave is done with K-half 0
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int lr = 32 * rt + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                    As[lr * LDA + col] = keep_g[rt][reg];
+                    As[lr * LDA + H + col] = keep_o[rt][reg];
+                }
+            __syncthreads();
+#pragma unroll 1
+            for (int kb = 0; kb < KBH; ++kb) blockdx(kb, KBH + kb);
+            // (the lane's dc_prev stores are behind this wait: the next step's loads of them find them; the prefetched values are in)
+            IC3_WAIT_VMEM();
+            __syncthreads();                                     // every wave is done with the A tile
+            if (!hw) {                                           // d inp -> ring slot s
+                const __amdgpu_buffer_rsrc_t rdx = gb_rsrc(a.dxh + (size_t)s * (size_t)a.dxh_step + r0 * K, (long long)rows * K * 4);
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) {
+                            const int lr = 32 * rt + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                            gb_store1(acc[rt][ct][reg], rdx, (lr * K + 64 * wu + 32 * ct + li) * 4, 0);
+                        }
+            } else if (s > 0) {                                  // d h_prev * row_keep[s - 1] -> the tile: the next step's dL/dh
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) {
+                            const int lr = 32 * rt + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                            As[lr * LDA + 64 * wu + 32 * ct + li - H] = acc[rt][ct][reg] * skp[lr];
+                        }
+            } else {                                             // behind step 0: dL/dh leaves the window
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) {
+                            const int lr = 32 * rt + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                            gb_store1(acc[rt][ct][reg], rdh, (lr * H + 64 * wu + 32 * ct + li - H) * 4, 0);
+                        }
+            }
+        }
+        if (lh == 0) prow[0] = ti, prow[H] = tf, prow[2 * H] = tg, prow[3 * H] = to;
+    }
+}
+
 }  // namespace ic3
 
 extern "C" int ic3_lstm_gates_backward_supported(int H) { return H == 64 || H == 128 || H == 256; }
+
+// The T steps of a comm_zero window as ONE launch of lstm_gates_bwd_walk_kernel (ic3_bptt_backward on an ic3_bptt_walk descriptor,
+// bptt_kernels.hip, which has checked it): at most one round of workgroup slots (two per CU at hid 64 / 128, one at 256), or
+// max_workgroups of them.
+int ic3::lstm_gates_backward_walk(const ic3_bptt_walk* b, ic3_stream stream)
+{
+    const long long R = (long long)b->E * b->N;
+    const int H = b->H, tiles = (int)((R + 63) / 64);
+    const GatesWalkArgs a{ b->gates, b->cs, b->dhead, b->w_heads, b->row_live, b->row_keep, b->lstm_wp3_bwd, b->dh, b->dc, b->dxh,
+                           b->dxh_step, b->dbias_partials, (int)R, b->OT, tiles, b->T, b->detach_gap };
+    int grid = std::min(tiles, device_cus() * (H <= 128 ? 2 : 1));
+    if (b->max_workgroups > 0) grid = std::min(grid, (int)b->max_workgroups);
+    const size_t lds = ((size_t)64 * (2 * H + 4) + 4 * H + 64 * 16) * sizeof(float);     // (the per-step launch's)
+    hipStream_t s = (hipStream_t)stream;
+    return H == 256   ? launch_kernel(lstm_gates_bwd_walk_kernel<256>, dim3(grid), dim3(512), lds, s, a)
+           : H == 128 ? launch_kernel(lstm_gates_bwd_walk_kernel<128>, dim3(grid), dim3(256), lds, s, a)
+                      : launch_kernel(lstm_gates_bwd_walk_kernel<64>, dim3(grid), dim3(128), lds, s, a);
+}
 
 static int gates_backward_impl(float* xh, int ldx, const float* h_prev, const float* lstm_wp, const void* lstm_wp3, const float* bias,
                                const float* c_prev, const float* dh, const float* dc, float* dgates, float* dc_prev,

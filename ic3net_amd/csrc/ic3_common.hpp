@@ -317,6 +317,8 @@ int tj_build_tables(int dim, int vision, int difficulty, int* h, int* w, int* ba
 // policy_ops.hip
 int sample_actions_env(const ic3_env* env, const float* logp, int ld, int A, int head, int32_t* action, float* chosen_logp,
                        hipStream_t s);
+// gates_bwd.hip: the one launch of ic3_bptt_backward on an ic3_bptt_walk descriptor (checked by its caller, bptt_kernels.hip)
+int lstm_gates_backward_walk(const ic3_bptt_walk* b, ic3_stream stream);
 // stats
 int env_stats(ic3_env* env, ic3_stats* out, hipStream_t s);
 

@@ -442,11 +442,21 @@ def _a2_grad_fill(b, a2_grad, work, Q, H, device):
 
 def bptt_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lstm_wp3_bwd, w_heads, c_weight, dh, dc, dxh,
                   dbias_partials, dcw_partials, mode_avg=True, comm_zero=False, detach_gap=0, row_live=None, row_keep=None,
-                  enc_first=True, gate_events=None, two_chains=False):
+                  enc_first=True, gate_events=None, two_chains=False, walk=False, max_workgroups=0):
     """ic3_bptt_backward: the backward through a window of T recorded steps as one host call (gate launch in place on the
     record, communication backward, encoder backward stage 1 — three launches per step).  alive / gate: lists of T tensors
     (E, N) int32 or None entries, or None.  gate_events: a list that receives (start, stop, t) DispatchEvent triples stamped
-    around every step's gate launch (measurement: bench.py --mode train)."""
+    around every step's gate launch (measurement: bench.py --mode train).
+    walk: a comm_zero window with the ring, its T steps in ONE launch (an ic3_bptt_walk descriptor: every 64-row tile walked last
+    step to first by one workgroup, dL/dh on chip) — the same dgates, d inp columns of the ring, dh, dc and bias partials bit for
+    bit; the d h_prev columns of the ring are not written.  max_workgroups > 0 caps that launch's grid (0: the library's plan)."""
+    if walk:
+        if not comm_zero:
+            raise ValueError("bptt_backward: walk=True needs comm_zero=True (a communicating policy's rows depend on each other)")
+        if dxh.dim() != 3:
+            raise ValueError("bptt_backward: walk=True needs the ring of per-step input gradients, dxh (T, R, 2H)")
+        if gate_events is not None:
+            raise ValueError("bptt_backward: walk=True is one launch: there are no per-step gate events")
     _need_cuda(gates, "bptt_backward")
     R = E * N
     assert _f32(gates, T * R * 4 * H)
@@ -461,6 +471,16 @@ def bptt_backward(env, T, E, N, H, gates, hs, cs, dhead, snaps, alive, gate, lst
         assert _dense(dcw_partials, (bptt_dcw_partials(E, N, two_chains), H, H))
         assert _dense(c_weight, (H, H))
     assert _f32(row_live, (T, R), none_ok=True) and _f32(row_keep, (T, R), none_ok=True)
+    if walk:      # (no masks, no C, one stream: the fields a comm_zero window uses)
+        b = _lib.BpttWalk(T, E, N, H, OT, int(detach_gap), int(bool(enc_first)), int(max_workgroups))
+        _set_ptrs(b, dict(gates=gates, hs=hs, cs=cs, dhead=dhead, snaps=snaps, lstm_wp3_bwd=lstm_wp3_bwd, w_heads=w_heads, dh=dh, dc=dc,
+                          dxh=dxh, dbias_partials=dbias_partials),
+                  row_live=row_live, row_keep=row_keep)
+        b.snap_words = snaps.stride(0)
+        b.dxh_step = dxh.stride(0)
+        b.enc_work = _enc_work(env, H, True)
+        check(_lib.lib().ic3_bptt_backward(env._h, C.byref(b), stream()))      # (its magic says which descriptor this is)
+        return
 
     def ptrs(ms):
         if ms is None or all(m is None for m in ms):

@@ -558,6 +558,53 @@ typedef struct ic3_bptt_passes {
     const float* keep_before; /* [R] or NULL: keep of the slot in front of this call's first one (a chunk with t_first > 0) */
 } ic3_bptt_passes;
 
+/* A comm_zero window of ic3_bptt_backward with its T steps WALKED IN ONE LAUNCH — ic3_bptt_backward handed the descriptor below in
+ * place of an ic3_bptt.  The descriptor is selected by its second word, magic = IC3_BPTT_WALK_MAGIC (where an ic3_bptt holds T), AND
+ * struct_size = sizeof(ic3_bptt_walk): a tagged descriptor of another size is refused with -EINVAL before anything else is read, an
+ * untagged one is an ic3_bptt and behaves as above.  (ABI 601 is closed: a descriptor, not a symbol.)  Error messages begin
+ * "ic3_bptt_backward (ic3_bptt_walk)".  Without communication (comm.py:40-41, comm_mask_zero — also IRIC's LSTM cell on its stand-in) no
+ * row's gradient depends on another row, so the workgroup that owns a 64-row tile walks t = T - 1 .. 0 by itself (no grid-wide
+ * barrier, no wait between workgroups, no atomics) and finishes the tile's window before its next tile: per step the arithmetic of
+ * ic3_lstm_gates_backward_given with the input gradient, element by element, and of the copy ic3_comm_backward makes with comm_zero
+ * (the d h_prev half of the product times row_keep[t - 1]) — dgates, the d inp columns of the ring, dh, dc and every row of
+ * dbias_partials are the per-step call's bits.  dL/dh stays on chip between the steps (dh crosses memory twice per tile: in at the
+ * window's last step, out behind its first); dL/dc crosses through dc, written and read back by the same lane.  Behind the launch:
+ * ic3_env_encode_backward_window over the ring, as the per-step call issues it.  One stream: the library's second stream is not touched.
+ *   The fields an ic3_bptt's comm_zero window uses, with their meaning there, EXCEPT: dxh is always the ring (dxh_step >= R * 2H), and
+ *   of a slot's rows [d inp | d h_prev] only the d inp half is WRITTEN — the d h_prev half keeps what it held (the encoder's window
+ *   stage reads the d inp columns only);  max_workgroups: 0 = the library's plan (one round of workgroup slots: two per CU at hid
+ *   64 / 128, one at 256; a workgroup walks every gridDim-th tile), > 0 caps the grid.  No alive / gate / c_weight / dcw_partials /
+ *   mode_avg / two_chains / gate_events.
+ * -EINVAL BEFORE the launch (every output and the record untouched): a tagged descriptor of another size, a null argument, dxh_step
+ * below R * 2H or a configuration without ic3_env_encode_backward_window (the walk needs the ring), detach_gap > 0 together with
+ * row_keep (as ic3_bptt_backward), OT outside 1..16, R >= 2^31.  -ENOSYS: hid_size other than 64 / 128 / 256, or
+ * ic3_bptt_backward_supported answering 0.  The launch-wide limit of rows * 4 * hid_size floats < 4 GB does not apply (buffer
+ * descriptors per step from 64-bit tile bases).  No float atomics: identical run to run. */
+#define IC3_BPTT_WALK_MAGIC 0x4b4c574cu /* "LWLK" */
+typedef struct ic3_bptt_walk {
+    uint32_t struct_size;   /* sizeof(ic3_bptt_walk) of the caller's header (checked with the tag: -EINVAL on mismatch) */
+    uint32_t magic;         /* IC3_BPTT_WALK_MAGIC */
+    int32_t T, E, N, H, OT;
+    int32_t detach_gap, enc_first;
+    int32_t max_workgroups; /* 0: the library's plan;  > 0: at most this many workgroups */
+    float* gates;           /* [T][R][4H] in: the recorded activated gates, out: dgates */
+    const float* hs;        /* [>= T][R][H] (not read by the walk: comm_zero; the weight gradient behind the call reads it) */
+    const float* cs;
+    const float* dhead;
+    const int32_t* snaps;
+    int64_t snap_words;
+    const float* row_live;
+    const float* row_keep;
+    const void* lstm_wp3_bwd;
+    const float* w_heads;
+    float* dh;
+    float* dc;
+    float* dxh;             /* the ring: step t's rows at dxh + t * dxh_step floats, the d inp half of every row written */
+    int64_t dxh_step;
+    float* dbias_partials;  /* [ceil(R / 64)][4H], ADDED to */
+    float* enc_work;
+} ic3_bptt_walk;
+
 /* The backward through a window of T recorded steps of the IC / IRIC baselines' tanh recurrence (models.py:68-92, rnn_type 'MLP':
  * h_t = tanh(affine1(obs_t) + affine2(h_{t-1})), heads and value on h_t), last step first, as ONE host call — per step ONE launch:
  *   dh_t = dh + d_t . W_heads;  dz_t = dh_t * (1 - h_t^2) -> dz slot t;  dh <- (dz_t . A2) * row_keep[t - 1];  column sums of dz_t

@@ -11,7 +11,9 @@ pp_hard_iric_tanh); WINDOW_LAUNCH_COLLECTION=1 sets args.window_launch_collectio
 = 1) too; WINDOW_LAUNCH_WIDE=1 sets args.window_launch_wide beside WINDOW_LAUNCH: the windows of a hid-256 policy too;
 PASSES_IN_LAUNCH_WIDE=1 sets args.passes_in_launch_wide: a hid-256 policy with COMM_PASSES 2..4 runs each step as one launch (and, with
 the three window switches, its windows as one launch each).  BACKWARD_WALK=1 sets args.backward_walk: the backward through time of
-pp_hard_iric_tanh as one launch per window (the line says how many windows went through it).  ROLLOUT_ONLY=1 times the rollout half of the timed updates by itself
+pp_hard_iric_tanh as one launch per window (the line says how many windows went through it).  BACKWARD_WALK_LSTM=1 sets
+args.backward_walk_lstm: the same for the LSTM policies without communication — pp_hard_iric, and any recurrent workload under
+COMM_MASK_ZERO=1 (args.comm_mask_zero).  ROLLOUT_ONLY=1 times the rollout half of the timed updates by itself
 (Trainer.run_batch between two synchronisations) and prints its time per step.  HID=<H> overrides
 the workload's hid_size (HID=256: the hid-128 workloads at the width of pp_scaled).  BATCH_WINDOWS=<k>: an update of k windows of max_steps steps (default 1; in collection mode the first starts the streams and
 the others continue them)."""
@@ -38,6 +40,8 @@ def main():
         if os.environ.get('SHARE_WEIGHTS', '0') == '1':
             over['share_weights'] = True
     shape = dict(hid_size=int(os.environ['HID'])) if os.environ.get('HID') else {}
+    if os.environ.get('COMM_MASK_ZERO', '0') == '1':
+        shape['comm_mask_zero'] = True
     tr, a = bench.build_trainer(wl, E, 0, 0, 0, **dict(over, **shape))
     if over and 'MULTIPASS_WINDOW' in os.environ:            # A/B: the window backward of comm_passes > 1 policies against the loop
         a.multipass_window_backward = os.environ['MULTIPASS_WINDOW'] == '1'
@@ -48,6 +52,7 @@ def main():
     a.window_launch_wide = int(os.environ.get('WINDOW_LAUNCH_WIDE', '0'))
     a.passes_in_launch_wide = int(os.environ.get('PASSES_IN_LAUNCH_WIDE', '0'))
     a.backward_walk = int(os.environ.get('BACKWARD_WALK', '0'))
+    a.backward_walk_lstm = int(os.environ.get('BACKWARD_WALK_LSTM', '0'))
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
     a.gate_split = bool(split)
     a.auto_reset = bool(coll)
@@ -104,7 +109,9 @@ def main():
         (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "") + \
         (" (window_launch: %d windows in one launch each)" % getattr(knet, 'window_launches', 0) if a.window_launch else "") + \
         (" (passes_in_launch_wide)" if a.passes_in_launch_wide else "") + \
-        (" (backward_walk: %d windows walked in one launch each)" % getattr(tr.policy_net, 'rnn_backward_walks', 0) if a.backward_walk else "")
+        (" (backward_walk: %d windows walked in one launch each)" % getattr(tr.policy_net, 'rnn_backward_walks', 0) if a.backward_walk else "") + \
+        (" (backward_walk_lstm: %d windows walked in one launch each)" % getattr(tr.policy_net, 'lstm_backward_walks', 0)
+         if a.backward_walk_lstm else "")
     print("train_batch [%s] %s E=%d: %.0f env-steps/s = %.2f M agent-steps/s (%.2f s per update of %d env-steps), "
           "peak mem %.1f GB, gemm %s" % (mode, label, E, steps / dt, a.nagents * steps / dt / 1e6, dt / updates,
                                          steps // updates, torch.cuda.max_memory_allocated() / 2 ** 30,
