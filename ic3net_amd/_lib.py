@@ -81,6 +81,15 @@ class PolicyWindow(_SizedStruct):
                                   ("gates", C.c_void_p), ("inp", C.c_void_p), ("snaps", C.c_void_p), ("snap_words", C.c_int64)]
 
 
+class PolicyWindowRecord(_SizedStruct):
+    """ic3_policy_window_record (include/ic3_rollout.h): an ic3_policy_window followed by the passes' record arrays; handed to
+    ic3_policy_step in place of a Policy, with inner_pass = WINDOW_PASSES_RECORD and its own struct_size — the npasses window at
+    hid 64 / 128 that also stores every pass's activated gates, inp rows and entering (h, c)."""
+    WINDOW_PASSES_RECORD = 9                   # IC3_POLICY_WINDOW_PASSES_RECORD
+    _fields_ = PolicyWindow._fields_ + [("gates_pass", C.c_void_p * 4), ("inp_pass", C.c_void_p * 4), ("h_pass", C.c_void_p * 4),
+                                        ("c_pass", C.c_void_p * 4)]
+
+
 class CommnetWindow(_SizedStruct):
     """ic3_commnet_window (include/ic3_rollout.h): an ic3_policy header followed by the operands of a window of T ic3_commnet_step
     calls; handed to ic3_policy_step in place of a Policy, with inner_pass = WINDOW (the tag that selects this form) and its own

@@ -103,12 +103,22 @@ class EpisodeRecord(object):
         # (Trainer hands slot t as ic3_commnet_step's h_out); h_fin_n = the steps that did — _backward_window_mlp reads it
         self.h_fin = None
         self.h_fin_n = 0
+        # comm_passes = P in 2..4 (Trainer._record_passes, args.window_record_passes): what every pass of every step of the window
+        # launch computed, stored by that launch itself (ops.policy_step_window's record_passes) — pass_gates (P, T, R, 4H) the
+        # activated gates, pass_inp (P, T, R, 2H) the inp half of the [inp | h] rows, pass_h / pass_c (P - 1, T, R, H) the state
+        # ENTERING pass i at entry i - 1 (pass 0 enters on slot t of hs / cs); pass_n = the steps that wrote theirs.  The window
+        # backward reads them instead of re-evaluating the passes where pass_n == n, and the gates are its dgates afterwards (it
+        # then sets pass_n back to 0: a second backward over the record re-evaluates)
+        self.pass_gates = self.pass_inp = self.pass_h = self.pass_c = None
+        self.pass_n = 0
 
     def release(self):
         """Drop the record's tensors now (tens of GB with recorded gates): the update is done with them, and whatever still
         refers to the record object — a reference cycle waiting for the garbage collector — must not keep them alive beside
         the next update's record."""
         self.hs = self.cs = self.gates = self.xh = self.snaps = self.h_last = self.out = self.h_fin = None
+        self.pass_gates = self.pass_inp = self.pass_h = self.pass_c = None
+        self.pass_n = 0
         self.alive, self.gate, self.stream = [], [], None
 
     def start_from(self, h, c):
@@ -793,20 +803,23 @@ MULTIPASS_WINDOW_DEFAULT = True       # args.multipass_window_backward where the
 MULTIPASS_WINDOW_COLLECTION_DEFAULT = False     # args.multipass_window_collection likewise: collection-mode windows keep the loop
 
 
-def _multipass_ring_floats(H, P, collection=False):
+def _multipass_ring_floats(H, P, collection=False, recorded=False):
     """Floats per row of one chunk step of _backward_window_multipass: per pass the gate record 4H, the inp rows, h and c H each and
     the dxh ring 2H; slot 0 of the h ring and the encoder ring H each; collection mode: slot 0 of a c ring too (the copy of the
-    entering c with the starting envs' rows zeroed)."""
+    entering c with the starting envs' rows zeroed).  recorded (the passes' record of the window launch stands in for the
+    re-evaluation): the dxh ring alone, and in collection mode the two copies of the entering state."""
+    if recorded:
+        return P * 2 * H + (2 * H if collection else 0)
     return P * (8 * H + ops.record_xh_width(H)) + (3 if collection else 2) * H
 
 
-def _multipass_chunk_steps(dev, T, R, H, P, most=0, collection=False):
+def _multipass_chunk_steps(dev, T, R, H, P, most=0, collection=False, recorded=False):
     """Whole steps per chunk of _backward_window_multipass — the largest count for which every launch stays inside its 32-bit limits
     (a chunk's rows x 4H floats below 4 GB: the recording forward and the gate launch's buffer offsets; rows below 2^31 - 2^16: the
     encoder's window stage) and the chunk's rings inside what _ring_fits grants; at most `most` when that is > 0; 0: not even one."""
     tc = min(T, (2 ** 32 - 1) // (R * 4 * H * 4), (2 ** 31 - 2 ** 16 - 1) // R)
     if dev.type == 'cuda':
-        tc = min(tc, (device_room(dev) // 4) // (R * _multipass_ring_floats(H, P, collection) * 4))
+        tc = min(tc, (device_room(dev) // 4) // (R * _multipass_ring_floats(H, P, collection, recorded) * 4))
     return max(min(tc, most) if most > 0 else tc, 0)
 
 
@@ -830,7 +843,19 @@ def _multipass_window_ok(args, net, raw, rec, d_out):
         return False
     if not _enc_window(args, raw, H) or not ops.bptt_passes_backward_supported(raw, H, net.comm_passes):
         return False
-    return _multipass_chunk_steps(rec.hs.device, rec.n, rec.hs.shape[1], H, net.comm_passes, collection=rec.stream is not None) >= 1
+    return _multipass_chunk_steps(rec.hs.device, rec.n, rec.hs.shape[1], H, net.comm_passes, collection=rec.stream is not None,
+                                  recorded=_passes_recorded(net, rec)) >= 1
+
+
+def _passes_recorded(net, rec):
+    """The window launch recorded every pass of every step of this record (EpisodeRecord.pass_*, args.window_record_passes): a
+    complete record at the policy's own width — hid 64 / 128, 2..4 passes.  Anything less (a window the library refused, a per-step
+    fallback, an allocation that failed) and the backward re-evaluates the passes as ever."""
+    if getattr(rec, 'pass_gates', None) is None or rec.pass_inp is None or rec.pass_h is None or rec.pass_c is None:
+        return False
+    P, H = net.comm_passes, rec.hs.shape[2]
+    return rec.n >= 1 and rec.pass_n == rec.n and 2 <= P <= 4 and H in (64, 128) and net.hid_size == H \
+        and rec.pass_gates.shape[0] == P and rec.pass_gates.shape[1] >= rec.n
 
 
 def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_chunk_steps=0, dgates_out=None):
@@ -850,7 +875,13 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
     the row of the slot in front of the chunk as keep_before, and dh is scaled by keep[T - 1] where it enters the window.  An env
     that starts an episode at slot t has nobody dead and everyone gated off in every pass of that step (masks_window) and zeros
     entering pass 0: slot 0 of the h ring and of a c ring hold the recorded rows times `live`, once per chunk over all its steps
-    (the record itself is left alone: the heads' pass beside the chain reads it)."""
+    (the record itself is left alone: the heads' pass beside the chain reads it).
+    A window whose launch recorded its passes (_passes_recorded: args.window_record_passes) skips the first two lines and the copy
+    into slot 0 of the h ring: per chunk the call is handed slices of the record — pass 0 enters on rec.hs / rec.cs (collection mode:
+    the live-scaled copies), pass i >= 1 on rec.pass_h[i - 1] / rec.pass_c[i - 1], the gates are rec.pass_gates[i][t0:t1], overwritten
+    by dgates in place — and the weight gradient runs per pass on those slices (they are not one block).  These are the values the
+    rollout's cells used; the re-evaluation rounds pass i > 0's encoder bias differently (encoder.bias + C_0.bias, then
+    C_i.bias - C_0.bias on top, where the rollout gathers with encoder.bias + C_i.bias).  Counted in net.multipass_recorded_windows."""
     fc = net._fused_cache()
     P = net.comm_passes
     T, R, H = rec.n, rec.hs.shape[1], rec.hs.shape[2]
@@ -862,13 +893,19 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
     heads = args.naction_heads
     cuts = _Cuts(args, rec, T, E, N, dev)                         # (lock-step: the detach points; collection: row factors, masks, carry)
     assert cuts.on or carry is None, "a carried gradient would be dropped: only collection-mode windows (rec.stream) take a carry"
-    Tc = _multipass_chunk_steps(dev, T, R, H, P, max_chunk_steps, collection=cuts.on)
+    recorded = _passes_recorded(net, rec)
+    Tc = _multipass_chunk_steps(dev, T, R, H, P, max_chunk_steps, collection=cuts.on, recorded=recorded)
     assert Tc >= 1, "no room for one step's rings (_multipass_window_ok answers first)"
     xw = ops.record_xh_width(H)
     empty = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
     zeros = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
-    enc, gates, inp = empty(Tc, R, H), empty(P, Tc, R, 4 * H), empty(P, Tc, R, xw)
-    hring, cring, dxh = empty(P + 1, Tc, R, H), empty(P, Tc, R, H), empty(P, Tc, R, 2 * H)     # cring[i]: c LEAVING pass i
+    if recorded:                                                  # (the record stands in for every ring but dxh's)
+        enc = gates = inp = cring = None
+        hring = empty(1, Tc, R, H) if cuts.on else None           # collection: h ENTERING pass 0, the starting envs' rows zeroed
+    else:
+        enc, gates, inp = empty(Tc, R, H), empty(P, Tc, R, 4 * H), empty(P, Tc, R, xw)
+        hring, cring = empty(P + 1, Tc, R, H), empty(P, Tc, R, H)                               # cring[i]: c LEAVING pass i
+    dxh = empty(P, Tc, R, 2 * H)
     c_in = empty(Tc, R, H) if cuts.on else None                   # collection: c ENTERING pass 0, the starting envs' rows zeroed
     dh_rec, dc_rec = zeros(R, H), zeros(R, H)
     cuts.carry_in(carry, dh_rec, dc_rec, at_border=True)
@@ -889,22 +926,29 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
         for t1 in range(T, 0, -Tc):
             t0 = max(t1 - Tc, 0)
             Tn = t1 - t0
-            for k in range(Tn):
-                raw.encode_at(rec.snaps[t0 + k], fc['wt'], fc['enc_bias'], out=enc[k], loc_table=fc['loc_table'])
             alive, gate = alive_w[t0:t1], gate_w[t0:t1]
-            alive_st, gate_st = stacked(alive), stacked(gate)
             if cuts.on:
                 torch.mul(rec.hs[t0:t1], cuts.live_rows[t0:t1], out=hring[0, :Tn])
                 torch.mul(rec.cs[t0:t1], cuts.live_rows[t0:t1], out=c_in[:Tn])
-            else:
+            elif not recorded:
                 hring[0, :Tn].copy_(rec.hs[t0:t1])
-            cs = [c_in[:Tn] if cuts.on else rec.cs[t0:t1]] + [cring[i, :Tn] for i in range(P - 1)]
-            for i in range(P):
+            if recorded:
+                g_p = [rec.pass_gates[i, t0:t1] for i in range(P)]
+                x_p = [rec.pass_inp[i, t0:t1] for i in range(P)]
+                h_p = [hring[0, :Tn] if cuts.on else rec.hs[t0:t1]] + [rec.pass_h[i, t0:t1] for i in range(P - 1)]
+                cs = [c_in[:Tn] if cuts.on else rec.cs[t0:t1]] + [rec.pass_c[i, t0:t1] for i in range(P - 1)]
+            else:
+                for k in range(Tn):
+                    raw.encode_at(rec.snaps[t0 + k], fc['wt'], fc['enc_bias'], out=enc[k], loc_table=fc['loc_table'])
+                alive_st, gate_st = stacked(alive), stacked(gate)
+                g_p, x_p, h_p = [gates[i, :Tn] for i in range(P)], [inp[i, :Tn] for i in range(P)], [hring[i, :Tn] for i in range(P)]
+                cs = [c_in[:Tn] if cuts.on else rec.cs[t0:t1]] + [cring[i, :Tn] for i in range(P - 1)]
+            for i in range(0 if recorded else P):
                 ops.policy_forward_record(fc, H, heads, mode_avg, mask_zero, enc[:Tn].view(Tn * R, H), Tn * E, N,
                                           hring[i, :Tn].view(Tn * R, H), cs[i].reshape(Tn * R, H), hring[i + 1, :Tn].view(Tn * R, H),
                                           cring[i, :Tn].view(Tn * R, H), alive_st, gate_st, gates[i, :Tn].view(Tn * R, 4 * H),
                                           inp[i, :Tn].view(Tn * R, xw), pass_index=i, enc_add=fc.get('enc_dbias_p%d' % i) if i else None)
-            ops.bptt_passes_backward(raw, Tn, E, N, H, [gates[i, :Tn] for i in range(P)], [hring[i, :Tn] for i in range(P)], cs,
+            ops.bptt_passes_backward(raw, Tn, E, N, H, g_p, h_p, cs,
                                      dhead[t0:t1], rec.snaps[t0:t1], alive, gate, fc['ps_l_wp3_bwd'], fc['w_heads'], c_weights, dh_rec,
                                      dc_rec, [dxh[i, :Tn] for i in range(P)], [bias_parts[i] for i in range(P)],
                                      None if mask_zero else [dcw_parts[i] for i in range(P)], mode_avg=mode_avg, comm_zero=mask_zero,
@@ -913,9 +957,13 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
                                      keep_before=cuts.keep_flat[t0 - 1] if cuts.on and t0 > 0 else None)
             first = False
             if dgates_out is not None:
-                dgates_out[:, t0:t1].copy_(gates[:, :Tn])
+                for i in range(P):
+                    dgates_out[i, t0:t1].copy_(g_p[i])
             split = bool(getattr(args, 'gate_split', True))
-            if Tn == Tc:                                          # the chunk's P x Tc x R rows in one launch
+            if recorded:                                          # (the record's slices of a chunk are not one block)
+                for i in range(P):
+                    ops.lstm_weight_grad(x_p[i], h_p[i], g_p[i], acc['w_cat_t'], accumulate=True, work=work, split=split)
+            elif Tn == Tc:                                        # the chunk's P x Tc x R rows in one launch
                 ops.lstm_weight_grad(inp, hring[:P], gates, acc['w_cat_t'], accumulate=True, work=work, split=split)
             else:                                                 # (a short last chunk: the passes' rows are not one block)
                 for i in range(P):
@@ -931,6 +979,9 @@ def _backward_window_multipass(args, net, raw, rec, d_out, acc, carry=None, max_
             if not mask_zero:
                 acc['c_w_p'][i].add_(dcw_parts[i].sum(0))
     net.multipass_window_backwards = getattr(net, 'multipass_window_backwards', 0) + 1
+    if recorded:
+        net.multipass_recorded_windows = getattr(net, 'multipass_recorded_windows', 0) + 1
+        rec.pass_n = 0                                            # (pass_gates holds dgates now)
     net.multipass_window_chunk = Tc
     return (dh_rec, dc_rec)
 

@@ -765,23 +765,27 @@ class CommNetMLP(nn.Module):
         """args.passes_in_launch_wide: comm_passes 2..4 at hid 256 run as the in-launch pass loop too (step_env, step_env_window)."""
         return bool(int(getattr(self.args, 'passes_in_launch_wide', 0)))
 
-    def window_supported(self, env, wide=False, wide_passes=False):
+    def window_supported(self, env, wide=False, wide_passes=False, record_passes=False):
         """step_env_window() may play a recorded training window on this env: the one-launch step at this hidden size itself (a
         zero-padded twin answers no), the split gate product, hid 64 / 128; one communication pass, or 2..4 where every step would be
         the in-launch pass loop (step_env: ops.policy_step_passes_supported and args.passes_in_launch; share_weights or not).
         wide: hid 256 with one pass as well (ops.policy_step_window's wide form; --window_launch_wide).  wide_passes, together with
         wide: hid 256 with 2..4 passes as well, where step_env runs them in one launch (ops.policy_step_window's wide_passes form;
-        --passes_in_launch_wide).  A zero-padded twin and comm_passes > 4 keep answering no."""
+        --passes_in_launch_wide).  A zero-padded twin and comm_passes > 4 keep answering no.  record_passes: the window may also
+        record what its passes computed (step_env_window's record_passes; --window_record_passes) — hid 64 / 128 with 2..4 passes,
+        nothing else."""
         if torch.is_grad_enabled() or self._twin() is not None or not self.mega_supported(env):
             return False
         if self.comm_passes != 1 and not (self._multi_pass_ok() and getattr(self.args, 'passes_in_launch', True)):
             return False
         H = self.hid_size
+        if record_passes:
+            return ops.policy_step_window_supported(env, self._fused_cache(), H, passes=self.comm_passes, record_passes=True)
         wp = bool(wide_passes) and bool(wide) and H == 256 and self.comm_passes != 1 and self._passes_wide()
         return ops.policy_step_window_supported(env, self._fused_cache(), H, passes=self.comm_passes, wide=bool(wide) and H == 256,
                                                 wide_passes=wp)
 
-    def step_env_window(self, env, info, T, hs, cs, out, action, reward, done, alive, is_completed, gates, inp, snaps):
+    def step_env_window(self, env, info, T, hs, cs, out, action, reward, done, alive, is_completed, gates, inp, snaps, record_passes=None):
         """T consecutive step_env() calls of the recorded training rollout in ONE launch (ic3_policy_step on an ic3_policy_window):
         hs / cs (T+1, R, H) the (h, c) record — step t reads slot t, writes slot t+1 —, out (T, R, OT), action (T, heads, E, N),
         reward / alive / is_completed (T, E, N), done (T, E), gates (T, R, 4H) / inp (T, R, 2H; hid 256: H) the gate record, snaps (T, words) the
@@ -790,7 +794,9 @@ class CommNetMLP(nn.Module):
         (args.comm_action_one).  No dense observation rows.  Returns [(action_out, value)] per step, views of `out`.  -38 from the
         library surfaces as NotImplementedError before anything was launched.  comm_passes 2..4: every step runs its passes inside
         the launch (the inner passes hand c on through slot t+1); gates and inp are None — that rollout keeps no gate record (hid 256:
-        the descriptor tagged WINDOW_WIDE_PASSES, where window_supported answered yes with wide_passes)."""
+        the descriptor tagged WINDOW_WIDE_PASSES, where window_supported answered yes with wide_passes).  record_passes: dict(gates=,
+        inp=, h=, c=) indexable by the pass, as ops.policy_step_window takes it — hid 64 / 128 with 2..4 passes, where
+        window_supported answered yes with record_passes: the launch also stores every pass's gates, inp rows and entering (h, c)."""
         n, H, a = self.nagents, self.hid_size, self.args
         assert self._twin() is None and 1 <= self.comm_passes <= 4, "window_supported() answers first"
         assert self.comm_passes == 1 or (gates is None and inp is None)
@@ -802,7 +808,7 @@ class CommNetMLP(nn.Module):
         ops.policy_step_window(env, fc, H, heads, mode_avg, mz, T, hs, cs, alive_in, comm_in, out, action, reward, done, alive,
                                is_completed, gates=gates, inp=inp, snaps=snaps, alive_prev=env.dims.kind == 2, comm_mode=comm_mode,
                                passes=self.comm_passes, wide=H == 256 and self.comm_passes == 1,
-                               wide_passes=H == 256 and self.comm_passes != 1)
+                               wide_passes=H == 256 and self.comm_passes != 1, record_passes=record_passes)
         self.window_launches = getattr(self, 'window_launches', 0) + 1
         return [self._split_out(out[t], batch, n) for t in range(T)]
 

@@ -110,7 +110,21 @@ struct StepArgs {
     int32_t* win_snaps;         // [T][win_snap_words] or null: the state entering step t, stored by the tiles that own it
     long long win_snap_words;
     int win_off[16], win_per[16];
+    // MP + WIN + REC = 2 (ic3_policy_window_record): the passes' records, bases of step 0 — pass i's activated gates [T][R][4H], its
+    // inp rows [T][R][2H] (the inp half written), and for i >= 1 the (h, c) ENTERING pass i [T][R][H].  window_step_args() picks the
+    // pass's and moves them to step t: gates_out / xh_out of the pass, and rec_h_next / rec_c_next — where THIS pass's h', c' go
+    // besides (an inner pass: the next pass's entry; the last pass: null).
+    float* rec_gates[4];
+    float* rec_inp[4];
+    float* rec_h[4];
+    float* rec_c[4];
+    float* rec_h_next;
+    float* rec_c_next;
 };
+// (by VALUE: a conditional between two members of the argument block is an lvalue — a selected address, then one load — and an address
+//  the optimiser cannot resolve keeps the whole block in scratch)
+template <class T>
+__device__ __forceinline__ T ps_pick4(int i, T v0, T v1, T v2, T v3) { return i == 0 ? v0 : i == 1 ? v1 : i == 2 ? v2 : v3; }
 
 // zero-store slots of one K block: 16 slots (one behind every pair of MFMAs of a full tile), S of them in use, evenly
 constexpr bool ps_zslot(int S, int i) { return S > 0 && ((i + 1) * S / 16) > (i * S / 16); }
@@ -160,8 +174,10 @@ __device__ __forceinline__ TileGeom tile_geom(const StepArgs& a, int tile_id)
 
 // The arguments of step t of a window (WIN): every per-step pointer moved by t steps, offsets in 64 bits; the masks of a step
 // t >= 1 are what step t - 1 wrote (Trainer._after_launch / _commit_step hand over the same tensors between two per-step calls).
-template <int H>
-__device__ __forceinline__ void window_step_args(StepArgs& a, int t)
+// REC = 2: also the record pointers of communication pass `pass` (scalar selects, as c_wp_now / enc_bias_now: indexing the arrays with
+// `pass` would put the argument block in scratch), into the fields the one-pass record's store code reads.
+template <int H, int REC = 0>
+__device__ __forceinline__ void window_step_args(StepArgs& a, int t, int pass = 0)
 {
     const long long R = (long long)a.E * a.N;
     const int32_t* const alive0 = a.so.alive_out;
@@ -181,6 +197,17 @@ __device__ __forceinline__ void window_step_args(StepArgs& a, int t)
     if (t > 0) {
         a.alive_in = a.win_alive == IC3_WINDOW_ALIVE_PREV ? alive0 + (t - 1) * R : nullptr;
         a.comm_in = a.win_comm == IC3_WINDOW_COMM_LAST_HEAD ? action0 + ((long long)(t - 1) * a.nheads + a.nheads - 1) * R : nullptr;
+    }
+    if constexpr (REC == 2) {
+        float* const gp = ps_pick4(pass, a.rec_gates[0], a.rec_gates[1], a.rec_gates[2], a.rec_gates[3]);
+        float* const xp = ps_pick4(pass, a.rec_inp[0], a.rec_inp[1], a.rec_inp[2], a.rec_inp[3]);
+        float* const hn = ps_pick4(pass, a.rec_h[1], a.rec_h[2], a.rec_h[3], a.rec_h[3]);   // (read by an inner pass only: pass <= 2)
+        float* const cn = ps_pick4(pass, a.rec_c[1], a.rec_c[2], a.rec_c[3], a.rec_c[3]);
+        const bool inner = pass + 1 < a.npass;
+        a.gates_out = gp + t * R * 4 * H;
+        a.xh_out = xp + t * R * 2 * H;
+        a.rec_h_next = inner ? hn + t * R * H : nullptr;
+        a.rec_c_next = inner ? cn + t * R * H : nullptr;
     }
 }
 
@@ -209,8 +236,9 @@ template <int H, int KIND, int SPLIT = 0, int MP = 0, int REC = 0, int WIN = 0>
 __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(const StepArgs a_in)
 {
     static_assert(!MP || (SPLIT && KIND != 0), "the in-launch pass loop exists for the split gate product on an env handle");
-    static_assert(!REC || (SPLIT && KIND == 0 && !MP), "the recording pass exists for the split gate product on a caller's encoder output");
-    static_assert(!WIN || (SPLIT && KIND != 0 && !REC), "the window form exists for the split gate product on an env handle");
+    static_assert(REC != 1 || (SPLIT && KIND == 0 && !MP), "the recording pass exists for the split gate product on a caller's encoder output");
+    static_assert(!WIN || (SPLIT && KIND != 0 && REC != 1), "the window form exists for the split gate product on an env handle");
+    static_assert(REC != 2 || (MP && WIN && H <= 128), "the passes' record exists for the in-launch passes of a window at hid 64 / 128");
     constexpr int K = 2 * H, LDA = K + 4, LDA4 = LDA / 4, BM = 64, NT = 2 * H, NW = H / 32, H4 = H / 4;
     IC3_DYNAMIC_LDS(float, smem);
     float* const As = smem;                                      // [BM][LDA]: cols [0,H) enc / comm / inp, [H,2H) h / h'
@@ -253,7 +281,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
     {
         StepArgs a_re;                                               // MP: the arguments again for every pass (kernarg segment),
         if constexpr (MP != 0 || WIN != 0) reload_args(a_re);        // nothing of them lives across a pass
-        if constexpr (WIN != 0) window_step_args<H>(a_re, (MP && WIN) ? wstep : pass);
+        if constexpr (WIN != 0) window_step_args<H, REC>(a_re, (MP && WIN) ? wstep : pass, pass);
         const StepArgs& a = (MP || WIN) ? a_re : a_in;
         int tid_v = threadIdx.x;
         if constexpr (MP != 0 || WIN != 0) IC3_OPAQUE_VGPR(tid_v);               // (per pass: nothing derived from it is hoisted out of the pass loop)
@@ -567,7 +595,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                     As[lr * LDA + col] = accC[rt][reg];
                 }
             }
-            if constexpr ((KIND != 0 && MP == 0) || REC != 0) {
+            if constexpr ((KIND != 0 && MP == 0) || REC != 0) {   // (REC = 2: the pass's inp record, MP or not)
                 if (a.xh_out) {   // (uniform; ic3_env_set_record_out) the same values -> the inp half of the record's [inp | h] rows
                     // (hid 256: inp rows alone, row stride H — the window backward reads h from the (h, c) record, and the wide
                     //  layout would not fit beside the gate record at the shapes hid 256 is trained at)
@@ -820,7 +848,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
     {
         StepArgs a;
         reload_args(a);
-        if constexpr (WIN != 0) window_step_args<H>(a, (MP && WIN) ? wstep : pass);
+        if constexpr (WIN != 0) window_step_args<H, REC>(a, (MP && WIN) ? wstep : pass, pass);
         int tid = threadIdx.x;
         IC3_OPAQUE_VGPR(tid);
         const bool first = !MP || pass == 0, last = !MP || pass + 1 == a.npass;
@@ -850,7 +878,14 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
             //  pass reads it back in its last gate block — instead of occupying 32 registers across that pass)
             const uint32_t nrec = (uint32_t)rows * H * 4u;
             const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(static_cast<void*>(a.c_out + r0 * H), 0, nrec, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(static_cast<void*>(a.h_out + r0 * H), 0, last ? nrec : 0u, 0x00020000);
+            // (REC = 2, an inner pass: h' also goes to the record of the state entering the next pass, c' to c_out as ever AND to that record)
+            float* const h_to = a.h_out;
+            float* const c_to = a.c_out;
+            float* const h_next = (REC == 2 && !last) ? a.rec_h_next : h_to;      // (values, not members: see ps_pick4)
+            float* const c_next = (REC == 2 && !last) ? a.rec_c_next : c_to;
+            const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(static_cast<void*>(h_next + r0 * H), 0, (last || REC == 2) ? nrec : 0u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rc2 = __builtin_amdgcn_make_buffer_rsrc(static_cast<void*>(c_next + r0 * H), 0, (REC == 2 && !last) ? nrec : 0u, 0x00020000);
+            (void)rc2;
             const int voff = (4 * lh * H + col) * 4;
             const float bi = slb[col], bf = slb[H + col], bg = slb[2 * H + col], bo = slb[3 * H + col];
             // (cold[]: requested in front of the C product; every load this wave issued after them has been waited for
@@ -902,6 +937,7 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
                         const int lc = 32 * rt + (reg & 3) + 8 * (reg >> 2);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, c1), rc, voff + lc * H * 4, 0, 0);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, h1), rh, voff + lc * H * 4, 0, 0);
+                        if constexpr (REC == 2) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, c1), rc2, voff + lc * H * 4, 0, PS_ZSTORE_AUX);
                         if constexpr (GS) {
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, si), rg, goff + lc * 4 * H * 4, 0, PS_ZSTORE_AUX);
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, sf), rg, goff + lc * 4 * H * 4 + H * 4, 0, PS_ZSTORE_AUX);
@@ -914,9 +950,10 @@ __global__ __launch_bounds__(2 * H, (H <= 128) ? 2 : 1) void policy_step_kernel(
             };
             const int ze = obs_here ? a.zepi : 0;
             // (the host arms gates_out for the SPLIT, one-pass, env instantiations only, and leaves the epilogue no zero-store
-            //  slots then)
-            constexpr bool GS_BUILT = SPLIT == 1 && MP == 0 && (KIND != 0 || REC != 0);
-            if (GS_BUILT && a.gates_out) {
+            //  slots then; REC = 2: every pass of the window records, and the window has no obs rows to fill)
+            constexpr bool GS_BUILT = SPLIT == 1 && ((MP == 0 && (KIND != 0 || REC == 1)) || REC == 2);
+            if constexpr (REC == 2) cell(std::integral_constant<int, 0>{}, std::true_type{});
+            else if (GS_BUILT && a.gates_out) {
                 if constexpr (GS_BUILT) cell(std::integral_constant<int, 0>{}, std::true_type{});
             } else if (ze <= 0) cell(std::integral_constant<int, 0>{}, std::false_type{});
             else if (ze == 1) cell(std::integral_constant<int, 1>{}, std::false_type{});
@@ -1458,12 +1495,14 @@ extern "C" int ic3_policy_forward(const ic3_policy* p, const float* enc, int E, 
 // `passes`: the descriptor is tagged IC3_POLICY_WINDOW_PASSES — npasses = 2..4 communication passes per step (the MP + WIN
 // instantiations), no gate / inp record.  `wide`: tagged IC3_POLICY_WINDOW_WIDE — the one-pass window at hid 256 and nothing else
 // (one workgroup of 512 threads per CU; the inp record has row stride H).  `passes` and `wide`: tagged IC3_POLICY_WINDOW_WIDE_PASSES —
-// the npasses window at hid 256 and nothing else (the MP + WIN instantiations at 256).
+// the npasses window at hid 256 and nothing else (the MP + WIN instantiations at 256).  `rec` (with `passes`, not `wide`): the descriptor is an
+// ic3_policy_window_record tagged IC3_POLICY_WINDOW_PASSES_RECORD — the npasses window at hid 64 / 128 that also stores every pass's
+// activated gates, inp rows and entering (h, c) (the MP + WIN + REC = 2 instantiations).
 static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool passes, bool wide, float* h, float* c, const int32_t* alive_in,
                               const int32_t* comm_in, float* out, int32_t* action, float* obs, float* reward, int32_t* done,
-                              int32_t* alive, int32_t* is_completed, ic3_stream stream)
+                              int32_t* alive, int32_t* is_completed, ic3_stream stream, const ic3_policy_window_record* rec = nullptr)
 {
-    const std::string who = passes ? (wide ? "ic3_policy_step (ic3_policy_window, wide passes)" : "ic3_policy_step (ic3_policy_window, passes)")
+    const std::string who = rec ? "ic3_policy_step (ic3_policy_window, passes record)" : passes ? (wide ? "ic3_policy_step (ic3_policy_window, wide passes)" : "ic3_policy_step (ic3_policy_window, passes)")
                             : wide ? "ic3_policy_step (ic3_policy_window, wide)" : "ic3_policy_step (ic3_policy_window)";
     if (!env) return fail(-22, who + ": null handle");
     // the one-shots of the per-step call have no meaning here (the descriptor names the record): disarmed, and the call refused
@@ -1493,6 +1532,9 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool pas
     const int H = p->H;
     const int lds = policy_step_lds(env, H);
     auto shape_ok = [&]() {
+        if (rec && H == 256)
+            return fail(-38, who + ": hid_size 256 is not part of the passes record (tag the descriptor IC3_POLICY_WINDOW_WIDE_PASSES; the update "
+                                   "re-evaluates the passes there)");
         const std::string narrow = passes ? "IC3_POLICY_WINDOW_PASSES" : "IC3_POLICY_WINDOW";
         if (wide && (H == 64 || H == 128))
             return fail(-38, who + ": " + (passes ? "IC3_POLICY_WINDOW_WIDE_PASSES" : "IC3_POLICY_WINDOW_WIDE") + " is the window at hid_size 256 (hid_size 64 / 128: tag the descriptor " + narrow + ")");
@@ -1513,8 +1555,23 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool pas
     }
     StepArgs a{};
     if (int frc = fill_policy(a, p, who.c_str())) return frc;
+    if (rec) {   // (npasses is 2..4 here)
+        for (int i = 0; i < a.npass; ++i) {
+            if (!rec->gates_pass[i] || !rec->inp_pass[i]) return fail(-22, who + ": gates_pass[i] and inp_pass[i] are needed for every pass i < npasses");
+            if (i >= 1 && (!rec->h_pass[i] || !rec->c_pass[i])) return fail(-22, who + ": h_pass[i] and c_pass[i] are needed for every pass 1 <= i < npasses");
+        }
+        if (rec->h_pass[0] || rec->c_pass[0]) return fail(-22, who + ": h_pass[0] and c_pass[0] must be NULL (the state entering pass 0 is slot t of (h, c))");
+    }
     if (passes) {
         if (int src = shape_ok()) return src;
+    }
+    if (rec) {
+        for (int i = 0; i < a.npass; ++i) {
+            a.rec_gates[i] = rec->gates_pass[i];
+            a.rec_inp[i] = rec->inp_pass[i];
+            a.rec_h[i] = rec->h_pass[i];
+            a.rec_c[i] = rec->c_pass[i];
+        }
     }
     a.h = a.h_out = h;
     a.c = a.c_out = c;
@@ -1544,6 +1601,11 @@ static int policy_step_window(ic3_env* env, const ic3_policy_window* w, bool pas
     const bool pp = env->kind == IC3_ENV_PP;
     hipStream_t s = (hipStream_t)stream;
     const int tiles = plan_tiles(a, H, p, s);
+    if (rec) {
+        if (H == 128)
+            return pp ? launch_step<128, IC3_ENV_PP, 1, 1, 2, 1>(a, tiles, lds, s) : launch_step<128, IC3_ENV_TJ, 1, 1, 2, 1>(a, tiles, lds, s);
+        return pp ? launch_step<64, IC3_ENV_PP, 1, 1, 2, 1>(a, tiles, lds, s) : launch_step<64, IC3_ENV_TJ, 1, 1, 2, 1>(a, tiles, lds, s);
+    }
     if (passes) {
         if (wide) return pp ? launch_step<256, IC3_ENV_PP, 1, 1, 0, 1>(a, tiles, lds, s) : launch_step<256, IC3_ENV_TJ, 1, 1, 0, 1>(a, tiles, lds, s);
         if (H == 128)
@@ -1593,6 +1655,15 @@ extern "C" int ic3_policy_step(ic3_env* env, const ic3_policy* p, float* h, floa
                                  ", this library's ic3_policy_window has " + std::to_string(sizeof(ic3_policy_window)) + " bytes");
         return policy_step_window(env, reinterpret_cast<const ic3_policy_window*>(p), true, true, h, c, alive_in, comm_in, out, action, obs,
                                   reward, done, alive, is_completed, stream);
+    }
+    // (the npasses window at hid 64 / 128 that records the passes' gates: a descriptor of its own behind the window's, tag and size together)
+    if (p && p->struct_size >= sizeof(ic3_policy) && p->inner_pass == IC3_POLICY_WINDOW_PASSES_RECORD) {
+        if (p->struct_size != sizeof(ic3_policy_window_record))
+            return fail(-22, "ic3_policy_step (ic3_policy_window, passes record): struct_size is " + std::to_string(p->struct_size) +
+                                 ", this library's ic3_policy_window_record has " + std::to_string(sizeof(ic3_policy_window_record)) + " bytes");
+        const ic3_policy_window_record* const r = reinterpret_cast<const ic3_policy_window_record*>(p);
+        return policy_step_window(env, &r->window, true, false, h, c, alive_in, comm_in, out, action, obs, reward, done, alive, is_completed,
+                                  stream, r);
     }
     // (likewise the window of ic3_commnet_step's families, played by commnet_fwd.hip's kernel; IC3_COMMNET_WINDOW_WIDE: at hid 256)
     if (p && p->struct_size >= sizeof(ic3_policy) && (p->inner_pass == IC3_COMMNET_WINDOW || p->inner_pass == IC3_COMMNET_WINDOW_WIDE)) {

@@ -97,7 +97,18 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  # buffer) — lock-step and collection windows, the same parameter gradients bit for bit.  0 (default): two launches
                  # per recorded step and chain.  Policies that communicate, comm_passes > 1, windows without the ring of input
                  # gradients and bench's per-gate timing keep their per-step path whatever this says
-                 ('backward_walk_lstm', int, 0)]
+                 ('backward_walk_lstm', int, 0),
+                 # 1: the recorded training window of a recurrent CommNet / IC3Net policy with comm_passes 2..4 at hid 64 / 128 — the
+                 # one launch of --window_launch, which this flag acts together with — also stores what every pass of every step
+                 # computed: its activated gates, its inp rows and the (h, c) it entered on (the library's
+                 # IC3_POLICY_WINDOW_PASSES_RECORD descriptor; P * 6H + (P - 1) * 2H floats per agent row and step, allocated where
+                 # they fit in half of what the device can still give).  The update (bptt._backward_window_multipass) then reads
+                 # that record instead of re-evaluating the passes: no encoder ring, no recording forward, and the values are the
+                 # ones the rollout's cells used.  Collection windows too, under --auto_reset with --window_launch_collection 1 and
+                 # --multipass_window_collection 1.  0 (default): the update re-evaluates the passes.  hid 256, zero-padded twins,
+                 # comm_passes > 4, passes_in_launch = False, a window the library refused and every per-step fallback keep the
+                 # re-evaluation whatever this says
+                 ('window_record_passes', int, 0)]
 
 
 def build_parser(argv):

@@ -261,10 +261,10 @@ class RNN(MLP):
         n = self._kernel()
         return n is not None and self.record_inplace_ok() and n.window_supported(env, wide=wide, **kw)
 
-    def step_env_window(self, env, info, T, *bufs):
+    def step_env_window(self, env, info, T, *bufs, **kw):
         """A recorded training window of T steps in ONE launch (CommNetMLP.step_env_window on the stand-in)."""
         n = self._stand_in.get()
-        out = n.step_env_window(env, info, T, *bufs)
+        out = n.step_env_window(env, info, T, *bufs, **kw)
         self._stand_in.done()
         self.window_launches = getattr(self, 'window_launches', 0) + 1
         return out

@@ -927,11 +927,15 @@ def policy_step(env, fc, H, head_sizes, mode_avg, comm_zero, h, c, alive_in, com
 WINDOW_COMM_MODES = dict(all=_lib.PolicyWindow.COMM_ALL, last_head=_lib.PolicyWindow.COMM_LAST_HEAD, ones=_lib.PolicyWindow.COMM_ONES)
 
 
-def policy_step_window_supported(env, fc, H, passes=1, wide=False, wide_passes=False):
+def policy_step_window_supported(env, fc, H, passes=1, wide=False, wide_passes=False, record_passes=False):
     """ic3_policy_step on an ic3_policy_window can run this env / hid_size: the split gate product, hid 64 / 128, a tile that fits;
     passes 2..4: the form tagged WINDOW_PASSES, where the per-step call would be the in-launch pass loop.  wide: the form tagged
     WINDOW_WIDE — hid 256 and one pass, nothing else (hid 64 / 128 are the narrow tag's).  wide_passes: the form tagged
-    WINDOW_WIDE_PASSES — hid 256 and passes 2..4, nothing else (every other shape is answered as without it)."""
+    WINDOW_WIDE_PASSES — hid 256 and passes 2..4, nothing else (every other shape is answered as without it).  record_passes: the
+    form tagged WINDOW_PASSES_RECORD — hid 64 / 128 and passes 2..4, nothing else."""
+    if record_passes:
+        return H in (64, 128) and 2 <= int(passes) <= 4 and fc.get('ps_l_wp3') is not None and \
+            policy_step_passes_supported(fc, H, passes) and policy_step_supported(env, H)
     if wide_passes and H == 256 and passes != 1:
         return policy_step_passes_supported(fc, H, passes, wide_passes=True) and policy_step_supported(env, H)
     if passes != 1 and not policy_step_passes_supported(fc, H, passes):
@@ -943,7 +947,7 @@ def policy_step_window_supported(env, fc, H, passes=1, wide=False, wide_passes=F
 
 def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, alive_in, comm_in, out, action, reward, done,
                        alive=None, is_completed=None, gates=None, inp=None, snaps=None, alive_prev=False, comm_mode='all', passes=1,
-                       wide=False, wide_passes=False):
+                       wide=False, wide_passes=False, record_passes=None):
     """T consecutive policy_step calls of the recorded training rollout in ONE launch — ic3_policy_step on an ic3_policy_window.
     hs, cs (T+1, E*N, H): step t reads slot t and writes slot t+1; alive_in / comm_in: the masks of step 0; out (T, E*N, OT); action
     (T, heads, E, N) int32; reward / alive / is_completed (T, E, N); done (T, E); gates (T, E*N, 4H) with inp (T, E*N, 2H) or both
@@ -953,6 +957,10 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     many communication passes inside the launch (the descriptor tagged WINDOW_PASSES, the passes' weights from `fc` as policy_step
     takes them); no gate record then.  wide: the descriptor tagged WINDOW_WIDE — hid 256, one pass, and inp (T, E*N, H): the inp rows
     alone (record_xh_width).  wide_passes: the descriptor tagged WINDOW_WIDE_PASSES — hid 256, passes 2..4, no gate record.
+    record_passes: dict(gates=, inp=, h=, c=) — the descriptor tagged WINDOW_PASSES_RECORD (hid 64 / 128, passes 2..4): the same
+    window, which also stores pass i's activated gates to gates[i] (T, E*N, 4H), its inp rows to inp[i] (T, E*N, 2H) (the inp half)
+    and, for i >= 1, the (h, c) entering pass i to h[i] / c[i] (T, E*N, H); every argument is indexable by the pass, entries 0 of h
+    and c are not read.
     NotImplementedError where the library answers -ENOSYS."""
     _need_cuda(hs, "policy_step_window")
     T = int(T)
@@ -971,15 +979,25 @@ def policy_step_window(env, fc, H, head_sizes, mode_avg, comm_zero, T, hs, cs, a
     passes = int(passes)
     assert passes == 1 or gates is None, "the in-launch passes keep no gate record"
     pol = _policy_struct(fc, H, head_sizes, mode_avg, comm_zero, passes=passes)
-    win = _lib.PolicyWindow()
+    win = _lib.PolicyWindow() if record_passes is None else _lib.PolicyWindowRecord()
     C.memmove(C.addressof(win), C.addressof(pol), C.sizeof(pol))
-    win.struct_size, win.inner_pass = C.sizeof(win), win.WINDOW_WIDE_PASSES if wide_passes else win.WINDOW_WIDE if wide else \
-        win.WINDOW if passes == 1 else win.WINDOW_PASSES
+    PW = _lib.PolicyWindow
+    win.struct_size, win.inner_pass = C.sizeof(win), PW.WINDOW_WIDE_PASSES if wide_passes else PW.WINDOW_WIDE if wide else \
+        PW.WINDOW if passes == 1 else PW.WINDOW_PASSES
     win.T = T
-    win.alive_mode = win.ALIVE_PREV if alive_prev else win.ALIVE_ALL
+    win.alive_mode = PW.ALIVE_PREV if alive_prev else PW.ALIVE_ALL
     win.comm_mode = WINDOW_COMM_MODES[comm_mode]
     _set_ptrs(win, dict(), gates=gates, inp=inp, snaps=snaps)
     win.snap_words = int(snaps.shape[1]) if snaps is not None else 0
+    if record_passes is not None:
+        assert H in (64, 128) and 2 <= passes <= 4 and not wide and not wide_passes, "WINDOW_PASSES_RECORD is the 2..4-pass window at hid 64 / 128"
+        win.inner_pass = win.WINDOW_PASSES_RECORD
+        for i in range(passes):
+            assert _dense(record_passes['gates'][i], (T, R, 4 * H)) and _dense(record_passes['inp'][i], (T, R, 2 * H))
+            win.gates_pass[i], win.inp_pass[i] = record_passes['gates'][i].data_ptr(), record_passes['inp'][i].data_ptr()
+            if i >= 1:
+                assert _dense(record_passes['h'][i], (T, R, H)) and _dense(record_passes['c'][i], (T, R, H))
+                win.h_pass[i], win.c_pass[i] = record_passes['h'][i].data_ptr(), record_passes['c'][i].data_ptr()
     check(_lib.lib().ic3_policy_step(env._h, C.cast(C.byref(win), C.POINTER(_lib.Policy)), ptr(hs), ptr(cs), ptr(alive_in),
                                      ptr(comm_in), ptr(out), ptr(action), None, ptr(reward), ptr(done), ptr(alive),
                                      ptr(is_completed), stream()))

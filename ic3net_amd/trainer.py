@@ -208,11 +208,18 @@ class Trainer(object):
                     return False
             if rec.out is None:
                 rec.out = torch.empty((T, E * args.nagents, sum(int(o) for o in args.naction_heads) + 1), dtype=torch.float32, device=dev)
+            # args.window_record_passes: the launch also stores what every pass computed (begin_episode allocated the arrays where
+            # _record_passes said yes); entries 0 of h / c are never read — pass 0 enters on slot t of the (h, c) record
+            rp = {}
+            if multipass and rec.pass_gates is not None:
+                rp = dict(record_passes=dict(gates=rec.pass_gates, inp=rec.pass_inp, h=[None] + list(rec.pass_h),
+                                             c=[None] + list(rec.pass_c)))
+            rec.pass_n = 0
             try:
                 if lstm:
                     outs = net.step_env_window(raw, info, T, rec.hs, rec.cs, rec.out, buf['action'], buf['reward'], buf['done'],
                                                buf['alive'], buf['is_completed'], None if multipass else rec.gates,
-                                               None if multipass else rec.xh, rec.snaps)
+                                               None if multipass else rec.xh, rec.snaps, **rp)
                 else:
                     # ic3_commnet_step's families.  The tanh recurrence runs in the record itself: slot 0 = the zero state the
                     # episode enters with, or the h the previous window ended with (the per-step bodies copy theirs into slot t),
@@ -240,6 +247,8 @@ class Trainer(object):
                 info['comm_action'] = buf['action'][t][-1] if not args.comm_action_one else self._ones_comm
             self._step_out[t] = (None, outs[t][0], outs[t][1], None)
         rec.n = rec.out_n = T
+        if rp:
+            rec.pass_n = T
         if multipass:
             # what T step bodies of this family leave: the final state in tensors of its own (finish() then keeps h_last beside
             # the record, and the heads' gradient takes the same two passes over the rows as behind a per-step rollout)
@@ -404,6 +413,14 @@ class Trainer(object):
                     self._rec.xh = torch.empty((T, E * N, ops.record_xh_width(knet.hid_size)), dtype=torch.float32, device=dev)
                 except torch.cuda.OutOfMemoryError:                # (the budget above is an estimate: recompute instead)
                     self._rec.gates = self._rec.xh = None
+            if self._record_passes(knet, T, E * N):
+                P, H, R = self._window_passes(), knet.hid_size, E * N
+                z = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+                try:
+                    self._rec.pass_gates, self._rec.pass_inp = z(P, T, R, 4 * H), z(P, T, R, 2 * H)
+                    self._rec.pass_h, self._rec.pass_c = z(P - 1, T, R, H), z(P - 1, T, R, H)
+                except torch.cuda.OutOfMemoryError:                # (the budget is an estimate: no record, the update re-evaluates)
+                    self._rec.pass_gates = self._rec.pass_inp = self._rec.pass_h = self._rec.pass_c = None
             if self._record_h_fin(T, E * N):
                 try:
                     self._rec.h_fin = torch.empty((T, E * N, args.hid_size), dtype=torch.float32, device=dev)
@@ -454,6 +471,31 @@ class Trainer(object):
         # allocator holds unused, half of it at most (the backward's own buffers, the graph pools and other ranks on the device
         # need room too); an allocation that fails anyway falls back to the recomputing backward (begin_episode)
         return T * R * (4 * H + ops.record_xh_width(H)) * 4 <= bptt.device_room(torch.cuda.current_device()) // 2
+
+    def _record_passes(self, knet, T, R):
+        """args.window_record_passes: let the window launch of a comm_passes 2..4 policy store what its passes computed in the
+        episode record (EpisodeRecord.pass_*; CommNetMLP.step_env_window's record_passes), so that the update skips its recording
+        forward — where --window_launch is set and the coming window would play through the passes form of the window launch
+        (_window_launch_ok), the policy runs at its own width (no zero-padded twin) and answers window_supported with
+        record_passes (hid 64 / 128; a policy that does not know the argument is not asked for a record), and the arrays stay
+        within half of what the device can still give (the rule of _record_gates)."""
+        a = self.args
+        raw = getattr(self.env, 'env', None)
+        P = self._window_passes()
+        if not int(getattr(a, 'window_record_passes', 0)) or not getattr(a, 'window_launch', False) or raw is None \
+                or knet is not self.policy_net or not 2 <= P <= 4:
+            return False
+        H = knet.hid_size
+        if H not in (64, 128) or not self._window_launch_ok(int(getattr(a, 'done_check_every', 0))):
+            return False
+        ok = getattr(self.policy_net, 'window_supported', None)
+        try:
+            with torch.no_grad():
+                if ok is None or not bool(ok(raw, record_passes=True)):
+                    return False
+        except TypeError:                                          # (a policy that knows nothing of the record: as before)
+            return False
+        return T * R * (P * (4 * H + 2 * H) + (P - 1) * 2 * H) * 4 <= bptt.device_room(torch.cuda.current_device()) // 2
 
     def _record_h_fin(self, T, R):
         """Native update of the IC baseline (models.MLP): let every step launch of the recorded rollout store the hidden state it

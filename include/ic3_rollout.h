@@ -1053,6 +1053,36 @@ typedef struct ic3_commnet_window {
  * other hid_size, no gate_split / lstm_wp3, an env tile or a state field that does not fit: -ENOSYS.
  * Error messages begin "ic3_policy_step (ic3_policy_window, wide passes)". */
 #define IC3_POLICY_WINDOW_WIDE_PASSES 8
+/* The npasses window at hid_size 64 / 128 that RECORDS what its passes computed — an ic3_policy_window followed by the passes' record
+ * arrays: policy.inner_pass = IC3_POLICY_WINDOW_PASSES_RECORD AND policy.struct_size = sizeof(ic3_policy_window_record) (the rule of
+ * tags 2..8: a tag of its own, checked together with its size; no new symbol, ABI 601 stays).  It means exactly
+ * IC3_POLICY_WINDOW_PASSES, plus these stores at step offset t for every pass i < npasses (offsets in 64 bits; one step's block keeps
+ * the per-step call's 32-bit limits):
+ *   gates_pass[i] [T][E*N][4H]   the activated gates i | f | g | o of pass i's LSTM cell, exactly what its cell update used
+ *   inp_pass[i]   [T][E*N][2H]   row stride 2H, the inp half written (encoder + biases of pass i + C_i(comm)), the h half untouched:
+ *                                ic3_env_set_record_out's layout
+ *   h_pass[i], c_pass[i] [T][E*N][H], i >= 1   the (h, c) ENTERING pass i = the h', c' pass i - 1 produced; entries [0] must be NULL
+ *                                (the state entering pass 0 is slot t of (h, c), as ever)
+ * The last pass's h', c' still go to slot t + 1, the inner passes keep handing c' on through that slot, and everything else the launch
+ * writes — out, action, reward, done, alive, is_completed, the (h, c) record, the snapshots, the state left in the handle — is the
+ * SAME BITS as under tag 5 on a twin handle.  With this record the update of a comm_passes > 1 policy needs no second forward: the
+ * values are the ones the rollout's cells consumed (the per-pass ic3_policy_forward re-evaluation rounds pass i > 0's encoder bias
+ * differently).  Costs P * 6H + (P - 1) * 2H floats of stores per agent row and step.
+ * Checked before any launch: the checks of tag 5 in tag 5's order (window.gates = window.inp = NULL among them); a tagged
+ * descriptor of any other size: -EINVAL (so is a plain ic3_policy whose inner_pass carries 9; pass 1 for an inner pass), and every
+ * other entry point refuses the struct by its size; a missing gates_pass[i] / inp_pass[i] for i < npasses, a missing h_pass[i] /
+ * c_pass[i] for 1 <= i < npasses, a non-NULL h_pass[0] / c_pass[0]: -EINVAL; hid_size 256: -ENOSYS with a message that says so (the
+ * in-launch pass loop at that width has no registers left for the record; use IC3_POLICY_WINDOW_WIDE_PASSES).
+ * Error messages begin "ic3_policy_step (ic3_policy_window, passes record)". */
+#define IC3_POLICY_WINDOW_PASSES_RECORD 9
+typedef struct ic3_policy_window_record {
+    ic3_policy_window window;  /* as for IC3_POLICY_WINDOW_PASSES: window.gates = window.inp = NULL */
+    float* gates_pass[4];      /* pass i: [T][E*N][4H] activated gates i|f|g|o, exactly what its cell update used */
+    float* inp_pass[4];        /* pass i: [T][E*N][2H] row stride 2H, the inp half written, the h half untouched
+                                  (ic3_env_set_record_out's layout) */
+    float* h_pass[4];          /* pass i >= 1: [T][E*N][H] h ENTERING pass i (= h' of pass i-1); [0] must be NULL */
+    float* c_pass[4];          /* pass i >= 1: [T][E*N][H] c ENTERING pass i; [0] must be NULL */
+} ic3_policy_window_record;
 
 /* The NON-recurrent CommNet module after the encoder (comm.py:127-129,179-205,220-224,228-239), every communication pass
  * in ONE launch:  x = tanh(enc);  h_0 = x;  h_{i+1} = tanh(x + f_modules[i](h_i) + C_modules[i](comm(h_i)));

@@ -10,7 +10,9 @@ many windows went through it: the LSTM policies' ic3_policy_window, and the ic3_
 pp_hard_iric_tanh); WINDOW_LAUNCH_COLLECTION=1 sets args.window_launch_collection beside it: the windows of collection mode (argument 7
 = 1) too; WINDOW_LAUNCH_WIDE=1 sets args.window_launch_wide beside WINDOW_LAUNCH: the windows of a hid-256 policy too;
 PASSES_IN_LAUNCH_WIDE=1 sets args.passes_in_launch_wide: a hid-256 policy with COMM_PASSES 2..4 runs each step as one launch (and, with
-the three window switches, its windows as one launch each).  BACKWARD_WALK=1 sets args.backward_walk: the backward through time of
+the three window switches, its windows as one launch each).  WINDOW_RECORD_PASSES=1 sets args.window_record_passes beside WINDOW_LAUNCH:
+the window launch of a COMM_PASSES 2..4 policy at hid 64 / 128 records its passes and the update reads that record instead of
+re-evaluating them (the line says how many windows' backwards did).  BACKWARD_WALK=1 sets args.backward_walk: the backward through time of
 pp_hard_iric_tanh as one launch per window (the line says how many windows went through it).  BACKWARD_WALK_LSTM=1 sets
 args.backward_walk_lstm: the same for the LSTM policies without communication — pp_hard_iric, and any recurrent workload under
 COMM_MASK_ZERO=1 (args.comm_mask_zero).  ROLLOUT_ONLY=1 times the rollout half of the timed updates by itself
@@ -51,6 +53,7 @@ def main():
     a.window_launch_collection = int(os.environ.get('WINDOW_LAUNCH_COLLECTION', '0'))
     a.window_launch_wide = int(os.environ.get('WINDOW_LAUNCH_WIDE', '0'))
     a.passes_in_launch_wide = int(os.environ.get('PASSES_IN_LAUNCH_WIDE', '0'))
+    a.window_record_passes = int(os.environ.get('WINDOW_RECORD_PASSES', '0'))
     a.backward_walk = int(os.environ.get('BACKWARD_WALK', '0'))
     a.backward_walk_lstm = int(os.environ.get('BACKWARD_WALK_LSTM', '0'))
     a.train_dense_obs = bool(dense) and len(sys.argv) > 5     # (default since round 5: the training rollout assembles no obs rows)
@@ -109,6 +112,8 @@ def main():
         (" (collection mode: %d whole episodes)" % int(st['num_episodes']) if coll else "") + \
         (" (window_launch: %d windows in one launch each)" % getattr(knet, 'window_launches', 0) if a.window_launch else "") + \
         (" (passes_in_launch_wide)" if a.passes_in_launch_wide else "") + \
+        (" (window_record_passes: %d windows' backwards read the launch's record)" % getattr(knet, 'multipass_recorded_windows', 0)
+         if a.window_record_passes else "") + \
         (" (backward_walk: %d windows walked in one launch each)" % getattr(tr.policy_net, 'rnn_backward_walks', 0) if a.backward_walk else "") + \
         (" (backward_walk_lstm: %d windows walked in one launch each)" % getattr(tr.policy_net, 'lstm_backward_walks', 0)
          if a.backward_walk_lstm else "")
