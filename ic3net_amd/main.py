@@ -90,13 +90,14 @@ _ENGINE_FLAGS = [('nenvs', int, 32), ('device', int, -1), ('hip_graph', 'hip_gra
                  # windows, the same parameter gradients bit for bit where a workgroup of the per-step launch owns one tile.
                  # 0 (default): one launch per recorded step.  Every other policy keeps its path whatever this says
                  ('backward_walk', int, 0),
-                 # 1: the update of a recurrent LSTM policy WITHOUT communication — IRIC with the LSTM cell (models.RNN, rnn_type
-                 # 'LSTM', on its stand-in) and any recurrent CommNet / IC3Net policy under --comm_mask_zero; hid 64 / 128 / 256 —
-                 # walks a recorded window's backward through time in ONE launch (bptt._backward_window_native on the library's
-                 # ic3_bptt_walk descriptor: a workgroup walks its 64-row tiles last step to first, dL/dh on chip, dL/dc through its
-                 # buffer) — lock-step and collection windows, the same parameter gradients bit for bit.  0 (default): two launches
-                 # per recorded step and chain.  Policies that communicate, comm_passes > 1, windows without the ring of input
-                 # gradients and bench's per-gate timing keep their per-step path whatever this says
+                 # 1: the update of a recurrent LSTM policy WITHOUT communication walks a recorded window's backward through time in
+                 # ONE launch: IRIC with the LSTM cell (models.RNN, rnn_type 'LSTM', on its stand-in) at hid 64 / 128, and any
+                 # recurrent CommNet / IC3Net policy under --comm_mask_zero at hid 64 / 128 / 256 (bptt._backward_window_native on
+                 # the library's ic3_bptt_walk descriptor: a workgroup walks its 64-row tiles last step to first, dL/dh on chip,
+                 # dL/dc through its buffer) — lock-step and collection windows, the same parameter gradients bit for bit.
+                 # 0 (default): two launches per recorded step and chain.  Policies that communicate, comm_passes > 1, IRIC's LSTM
+                 # cell at hid 256 (its rollout keeps no gate record there: Trainer._record_gates), windows without the ring of
+                 # input gradients and bench's per-gate timing keep their per-step path whatever this says
                  ('backward_walk_lstm', int, 0),
                  # 1: the recorded training window of a recurrent CommNet / IC3Net policy with comm_passes 2..4 at hid 64 / 128 — the
                  # one launch of --window_launch, which this flag acts together with — also stores what every pass of every step

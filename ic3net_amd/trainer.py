@@ -396,8 +396,9 @@ class Trainer(object):
                     ph = self._static['prev_hid'] = torch.empty((E, args.nagents, args.hid_size), dtype=torch.float32, device=dev)
                 ph.zero_()
                 self._prev_hid = ph
-            else:
-                self._prev_hid = torch.zeros((E, args.nagents, args.hid_size), dtype=torch.float32, device=dev)
+            else:                                                  # (the parameters' dtype: an fp64 policy under autograd)
+                self._prev_hid = torch.zeros((E, args.nagents, args.hid_size), device=dev,
+                                             dtype=self.params[0].dtype if self.params else torch.float32)
         self._step_out = [(None, None, None, None)] * T          # (state, action_out, value, next_state) per step
         self._rec = None
         if self._records is not None:                              # native update: what the backward pass needs later
